@@ -22,6 +22,9 @@ Extra objects on the JSON line:
   configs      — the other BASELINE.json configurations (the T=1000 half of the metric, the
                  projected T=500 loop, the batch-1 planning call), one timed loop each in the same
                  invocation, each with its own ms_per_step / roofline / cpu_baseline.
+
+--dump-outputs DIR writes the headline loop's plans of its last timed step (seed 1000 + warmup + steps - 1;
+weights, conditions and Philox noise all come from fixed seeds) to DIR/plans.npy, for comparing two builds.
 """
 from __future__ import annotations
 
@@ -97,7 +100,33 @@ def parse_args():
                     help="independent sampling loops kept in flight on separate HIP streams "
                          "(diagnostic: shows how much of a step is dependency bubbles; the "
                          "headline number uses 1)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the plans the headline loop returned in its last "
+                         "timed step to DIR/plans.npy (float32; every rank's plans when N>1)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.inflight > 1:
+        ap.error("--dump-outputs needs --inflight 1 (the other loops in flight return nothing)")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """--dump-outputs: each tensor as out_dir/<name>.npy in float32.  Every workload's plans fit whole
+    (Door at 128 plans per GPU on 8 ranks: 8.8 MB), so nothing is sampled."""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes over the {DUMP_LIMIT_BYTES >> 20} MB limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def self_launch(args) -> int:
@@ -351,14 +380,16 @@ def main() -> None:
         gathered = torch.empty(world * batch, 32, td, device=device) if world > 1 else None
 
         def one_step(k: int):
+            """One sampling loop; returns the finished plans of every rank (this rank's alone on one GPU)."""
             diff.seed = 1000 + k                                  # fresh noise every loop
             plans = policy.sample_loop(batch_size=batch, conditions=cond, row_offset=rank * batch)
             if dist is not None:                                   # collect finished plans (RCCL)
                 if host_collectives:                               # gloo rehearsal: stage through host
                     parts = [torch.empty(plans.shape) for _ in range(world)]
                     dist.all_gather(parts, plans.cpu())
-                else:
-                    dist.all_gather_into_tensor(gathered, plans)
+                    return torch.cat(parts)
+                dist.all_gather_into_tensor(gathered, plans)
+                return gathered
             return plans
 
         extra = []
@@ -397,6 +428,9 @@ def main() -> None:
         elapsed = max_over_ranks(time.perf_counter() - t0)
         assert torch.isfinite(plans).all()
         loop_s = elapsed / steps
+        if headline and rank == 0 and args.dump_outputs:
+            # copied now: the passes below run the same loop again, and a replayed graph reuses its buffers
+            dump_outputs(args.dump_outputs, {"plans": plans})
 
         roof = None
         if rank == 0:

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from dynamics_aware_diffusion_amd import GaussianDiffusion, GuidedPolicy, TemporalUnet
 from dynamics_aware_diffusion_amd.utils import synth

@@ -3,7 +3,7 @@ hipcc ... -DDAD_WG_STAMPS -o profiles/micro/_lib_stamps.so; DAD_LIB=that python3
 Block (0,0,0), thread 0, s_memrealtime (100 MHz): entry, first chunk staged, every chunk's end, after the K-group
 reduction, after the stores."""
 import os, sys, ctypes as C
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from dynamics_aware_diffusion_amd import GaussianDiffusion, TemporalUnet, _engine
 from dynamics_aware_diffusion_amd.utils import synth
