@@ -224,8 +224,14 @@ __device__ __forceinline__ void store_f4_sc1(float* p, const float4 v) {
 // PADDED: the zero-padded forms (dad_model_set_horizon / dad_model_set_group_channels) as their own instantiations —
 // as runtime branches of the one kernel they cost the BASELINE configurations 0.4-0.8 % (A/B of two builds on one
 // box): the unpadded kernels are instruction for instruction what they were.
+// WIN: windowed tiles for layers longer than any tile (Lout > BN, horizons 256 / 512).  A tile is BN consecutive
+// positions of ONE sample: its X stage holds BN * STRIDE rows plus the halo, the halo rows read the neighbouring
+// positions of the same sample (zeros only past either end of it).  A (sample, group) pair then spans several
+// tiles, so the kernel stops at conv + bias: the GroupNorm -> Mish -> time embedding -> residual tail of such a
+// layer is a second launch over whole pairs (conv_gn_pass.hpp).  Windowed kernels are always PADDED instantiations
+// (the masks are runtime branches there; no existing configuration runs them).
 template <int BM, int BN, int SK, int KC, int TAPS, int STRIDE, bool RAGGED, bool X3 = false, bool BDIR = false,
-          bool RES = false, bool PADDED = false>
+          bool RES = false, bool PADDED = false, bool WIN = false>
 __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32(const ConvParams p) {
     constexpr int TMW = BM / 32;                 // wave tiles along M
     constexpr int TNW = BN / 32;                 // wave tiles along N
@@ -245,6 +251,9 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
     static_assert(KC % KU == 0 && G % SK == 0 && GW >= 1, "K chunk must split evenly over the SK waves");
     static_assert(!BDIR || (BN == 32 && SK == 1 && !RAGGED && KC >= 16), "direct-B tiles");
     static_assert(!RES || (!X3 && !BDIR && (TAPS & 1) == 1 && TAPS >= 3 && STRIDE == 1), "the residual ride exists for fp32 stride-1 convs of the net's kernel size");
+    static_assert(!WIN || (PADDED && !X3 && !BDIR && !RES), "windowed tiles: fp32, LDS-staged, no ride");
+    constexpr int BN_SH = BN == 32 ? 5 : BN == 64 ? 6 : 7;
+    static_assert((1 << BN_SH) == BN, "BN is 32, 64 or 128");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // Vector accesses go through these views with an index in vector units: every offset below
@@ -284,10 +293,12 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
     const int tile = mt * p.ntiles_n + nt;       // id for the split-K slab / ticket
 
     const int Lin = p.Lin, Lout = p.Lout;
-    const int SPT = BN >> p.lshift;              // whole samples per tile
-    const int SEG = Lin + 2 * PAD;
+    const int SPT = WIN ? 1 : BN >> p.lshift;    // whole samples per tile (windowed: part of one)
+    const int SEG = WIN ? BN * STRIDE + 2 * PAD : Lin + 2 * PAD;
     const int XROWS = SPT * SEG;
-    const int s0 = nt * SPT;                     // first sample of this tile
+    const int wsh = WIN ? p.lshift - BN_SH : 0;  // windowed: log2(windows per sample)
+    const int s0 = WIN ? nt >> wsh : nt * SPT;   // first sample of this tile
+    const int w0 = WIN ? (nt & ((1 << wsh) - 1)) << BN_SH : 0;   // first output position of the window
     const int m0 = mt * BM;                      // first output channel of this tile
     const int M = p.M;
     const int nvalid = min(SPT, p.B - s0);
@@ -302,8 +313,9 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
     // Transposed conv as two 2-tap phases: even outputs read positions (l-1, l), odd outputs
     // (l, l+1); the M tile's phase shifts the first row by one.
     const int phase_shift = (TAPS == 2 && p.interleave && m0 >= (p.M >> 1)) ? 1 : 0;
-    const int arow = ((n_loc >> p.lshift) * SEG + (n_loc & (Lout - 1)) * STRIDE + phase_shift) * KP + 4 * h +
-                     (int)((p.xswz >> (4 * (n_loc >> p.lshift))) & 15) * 4;
+    const int arow = WIN ? (n_loc * STRIDE + phase_shift) * KP + 4 * h
+                         : ((n_loc >> p.lshift) * SEG + (n_loc & (Lout - 1)) * STRIDE + phase_shift) * KP + 4 * h +
+                               (int)((p.xswz >> (4 * (n_loc >> p.lshift))) & 15) * 4;
     // B operand (weights): lane's output channel
     const int brow = XF + (tm * 32 + l32) * KP + 4 * h;
 
@@ -329,9 +341,9 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
     constexpr int W_PER_T = BDIR ? 0 : (W_F4 + NT - 1) / NT;   // staged W items (none in direct-B mode)
     constexpr int W_ARR = W_PER_T ? W_PER_T : 1;
     constexpr int KQ = KC / 4;                              // float4 per row
-    constexpr int X_F4_MAX = BN * STRIDE * KQ;              // SPT*Lin == BN*STRIDE rows
+    constexpr int X_F4_MAX = (BN * STRIDE + (WIN ? 2 * PAD : 0)) * KQ;   // SPT*Lin == BN*STRIDE rows (+ halo)
     constexpr int X_PER_T = (X_F4_MAX + NT - 1) / NT;
-    const int xrows_real = SPT * Lin;
+    const int xrows_real = WIN ? SEG : SPT * Lin;          // windowed: the halo rows are staged too
     float4 wreg[W_ARR];
     float4 xreg[X_PER_T];
     // Per-thread staging addresses are chunk-invariant up to a uniform stride: computed once.
@@ -354,10 +366,11 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
         const int e = tid + i * NT;
         const int row = e / KQ;                             // s*Lin + l
         const int q = e - row * KQ;
-        const int s = row >> p.lshift_in;                   // Lin is a power of two
-        const int l = row - (s << p.lshift_in);
-        const bool ok = e < xrows_real * KQ && s < nvalid;
-        x_grow[i] = ok ? s0 * Lin + row : -1;
+        const int s = WIN ? 0 : row >> p.lshift_in;         // Lin is a power of two
+        int l = row - (s << p.lshift_in);
+        if constexpr (WIN) l = w0 * STRIDE - PAD + row;     // input position of stage row `row` (halo included)
+        const bool ok = e < xrows_real * KQ && s < nvalid && (!WIN || (l >= 0 && l < Lin));
+        x_grow[i] = ok ? (WIN ? s0 * Lin + l : s0 * Lin + row) : -1;
         if constexpr (PADDED)
             if (p.src_len > 0)                              // external trajectory of a zero-padded horizon
                 x_grow[i] = (ok && l < p.src_len) ? (s0 + s) * p.src_len + l : -1;
@@ -366,7 +379,7 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
         const int qoff = X3 ? (q >> 2) * 16 + (q & 3) * 2 : q * 4;
         // float4 units (fp32 rows) or float2 units (split-f16 rows: a float4 becomes 8 bytes of hi
         // halves and, 8 floats further, 8 bytes of lo halves)
-        const int xo = (s * SEG + PAD + l) * KP + qoff + (int)((p.xswz >> (4 * s)) & 15) * 4;
+        const int xo = WIN ? row * KP + qoff : (s * SEG + PAD + l) * KP + qoff + (int)((p.xswz >> (4 * s)) & 15) * 4;
         x_loff[i] = e < xrows_real * KQ ? (X3 ? xo >> 1 : xo >> 2) : -1;
     }
     DAD_PSTAMP(6);
@@ -504,7 +517,7 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
 #ifdef DAD_ABLATE_GN
     const bool has_gn = false;
 #else
-    const bool has_gn = p.gamma != nullptr;
+    const bool has_gn = !WIN && p.gamma != nullptr;  // windowed: the tail is the GroupNorm pass's
 #endif
     const int cpg = has_gn ? p.cpg : BM;
     const int cq = cpg >> 2;                           // float4 per row of a pair
@@ -530,7 +543,7 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
         erow[k] = ps * Lout + r;                       // tile row (position)
         ecol[k] = pg * cpg + (j & (cq - 1)) * 4;       // tile column (channel)
         const int s = erow[k] >> p.lshift;
-        const int l = erow[k] & (Lout - 1);
+        const int l = w0 + (erow[k] & (Lout - 1));
         const int em = m0 + ecol[k];
         if (!p.interleave) {
             eoff[k] = ((s0 + s) * Lout + l) * M + em;
@@ -575,7 +588,7 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
     // rows — including those of samples beyond the batch, which get zeros — are rewritten in full
     // by every chunk's staging, so nothing else needs clearing and, the two sets of rows being
     // disjoint, no barrier separates this from the first stores.
-    if constexpr (PAD > 0) {
+    if constexpr (PAD > 0 && !WIN) {
         constexpr int KP4 = KP / 4;
         const int nz = SPT * (2 * PAD) * KP4;
         for (int i = tid; i < nz; i += NT) {
@@ -898,7 +911,7 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * SK) void conv_gemm_f32
     for (int k = 0; k < F4PL; ++k) {
         if (eoff[k] < 0) continue;
         if constexpr (PADDED) {                        // zero-padded horizon: the padding stays zero
-            if (p.lreal > 0 && (erow[k] & (Lout - 1)) >= p.lreal) {
+            if (p.lreal > 0 && w0 + (erow[k] & (Lout - 1)) >= p.lreal) {
                 store_f4_sc1(p.dst + eoff[k], make_float4(0.f, 0.f, 0.f, 0.f));
                 continue;
             }

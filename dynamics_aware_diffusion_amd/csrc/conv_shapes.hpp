@@ -15,9 +15,10 @@ namespace dad {
 constexpr int kXSwzPad = 64;    // floats: room for the per-sample slot shifts of the X stage
 constexpr size_t kLdsBytes = 160 * 1024;   // LDS of one gfx950 CU
 
-// Rows of the X stage: every sample of the tile with its zero halo.
+// Rows of the X stage: every sample of the tile with its zero halo, or (layers longer than the tile:
+// windowed tiles) BN output positions' worth of input rows of one sample plus the halo on both sides.
 DAD_HD inline int conv_xrows(int BN, int Lin, int Lout, int taps) {
-    return (BN / Lout) * (Lin + 2 * (taps / 2));
+    return Lout > BN ? BN * (Lin / Lout) + 2 * (taps / 2) : (BN / Lout) * (Lin + 2 * (taps / 2));
 }
 // LDS floats of one block (the host sizes the dynamic allocation with the same formula).
 // wtaps: weight rows staged per chunk, in taps (taps + 1 when a 1x1 residual conv rides along).

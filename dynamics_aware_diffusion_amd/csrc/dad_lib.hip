@@ -21,6 +21,7 @@
 #include "../../include/dad.h"
 #include "host_plan.hpp"
 #include "conv_gemm.hpp"
+#include "conv_gn_pass.hpp"
 #include "pointwise.hpp"
 #include "conv_cc.hpp"
 #include "conv_ccw.hpp"
@@ -146,22 +147,22 @@ void free_device(dad_model* m) {
 // ---------------------------------------------------------------------- kernel registry
 // Every conv-GEMM instantiation the planner can ask for, keyed by what plan_launch decides.
 using KernFn = void (*)(const ConvParams);
-using KernKey = std::tuple<int, int, int, bool, bool, bool, bool, bool>;   // cfg, taps, stride, x3, bdir, ragged, res, padded
+using KernKey = std::tuple<int, int, int, bool, bool, bool, bool, bool, bool>;   // cfg, taps, stride, x3, bdir, ragged, res, padded, windowed
 using KernTable = std::map<KernKey, KernFn>;
 
 template <int CFG> struct Tile {
     static constexpr int BM = kTiles[CFG].BM, BN = kTiles[CFG].BN, SK = kTiles[CFG].SK, KC = kTiles[CFG].KC;
 };
 
-template <int CFG, int TAPS, int STRIDE, bool X3, bool BDIR, bool RES, bool PADDED = false>
+template <int CFG, int TAPS, int STRIDE, bool X3, bool BDIR, bool RES, bool PADDED = false, bool WIN = false>
 void reg_kernel(KernTable& t) {
     using T = Tile<CFG>;
     constexpr int KC = eff_kc(T::KC, T::BM, TAPS, T::SK, X3, BDIR, T::BN);
-    t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, false, RES, PADDED)] =
-        dad::conv_gemm_f32<T::BM, T::BN, T::SK, KC, TAPS, STRIDE, false, X3, BDIR, RES, PADDED>;
+    t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, false, RES, PADDED, WIN)] =
+        dad::conv_gemm_f32<T::BM, T::BN, T::SK, KC, TAPS, STRIDE, false, X3, BDIR, RES, PADDED, WIN>;
     if constexpr (!BDIR && STRIDE == 1 && (TAPS & 1) == 1)             // general staging path
-        t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, true, RES, PADDED)] =
-            dad::conv_gemm_f32<T::BM, T::BN, T::SK, KC, TAPS, STRIDE, true, X3, BDIR, RES, PADDED>;
+        t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, true, RES, PADDED, WIN)] =
+            dad::conv_gemm_f32<T::BM, T::BN, T::SK, KC, TAPS, STRIDE, true, X3, BDIR, RES, PADDED, WIN>;
 }
 // Zero-padded nets (dad_model_set_horizon / dad_model_set_group_channels): fp32, no ride, on the tiles the heuristic
 // picks (kPaddedTiles of host_plan.hpp)
@@ -180,6 +181,18 @@ void reg_tile_padded(KernTable& t) {
         reg_kernel<CFG, 3, 1, false, true, false, true>(t);
         reg_kernel<CFG, 7, 1, false, true, false, true>(t);
     }
+}
+// Windowed tiles (layers longer than any tile: kWinTiles of host_plan.hpp): fp32, PADDED, every conv form of the
+// forward and backward passes
+template <int CFG>
+void reg_tile_windowed(KernTable& t) {
+    reg_kernel<CFG, 5, 1, false, false, false, true, true>(t);
+    reg_kernel<CFG, 3, 1, false, false, false, true, true>(t);
+    reg_kernel<CFG, 7, 1, false, false, false, true, true>(t);
+    reg_kernel<CFG, 3, 2, false, false, false, true, true>(t);
+    reg_kernel<CFG, 5, 2, false, false, false, true, true>(t);   // backward of Upsample1d
+    reg_kernel<CFG, 2, 1, false, false, false, true, true>(t);
+    reg_kernel<CFG, 1, 1, false, false, false, true, true>(t);
 }
 template <int CFG>
 void reg_tile(KernTable& t) {
@@ -216,6 +229,7 @@ const KernTable& kernel_table() {
         reg_tile<8>(t); reg_tile<9>(t);
         reg_tile_padded<0>(t); reg_tile_padded<1>(t); reg_tile_padded<2>(t); reg_tile_padded<3>(t);
         reg_tile_padded<4>(t); reg_tile_padded<8>(t); reg_tile_padded<9>(t);
+        reg_tile_windowed<0>(t); reg_tile_windowed<1>(t); reg_tile_windowed<2>(t);
         return t;
     }();
     return table;
@@ -262,22 +276,27 @@ const void* ccw_kernel(int taps, bool res, bool ride_in, int rows) {
 // conv_wgrad instantiations by (taps, block tile): tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32
 // (eight); tile 3 = 32 x 32 with the general staging path (operands that are not whole aligned float4 rows)
 constexpr int kWgradTiles = 4;
-template <int TAPS>
+// (win: the windowed form for layers longer than a chunk stages, conv_wgrad WIN)
+template <int TAPS, bool WIN>
 const void* wgrad_kernel_t(int tile) {
-    return tile == 0 ? (const void*)dad::conv_wgrad<TAPS, 2, 2, true>
-         : tile == 1 ? (const void*)dad::conv_wgrad<TAPS, 2, 1, true>
-         : tile == 2 ? (const void*)dad::conv_wgrad<TAPS, 1, 1, true>
-                     : (const void*)dad::conv_wgrad<TAPS, 1, 1, false>;
+    return tile == 0 ? (const void*)dad::conv_wgrad<TAPS, 2, 2, true, WIN>
+         : tile == 1 ? (const void*)dad::conv_wgrad<TAPS, 2, 1, true, WIN>
+         : tile == 2 ? (const void*)dad::conv_wgrad<TAPS, 1, 1, true, WIN>
+                     : (const void*)dad::conv_wgrad<TAPS, 1, 1, false, WIN>;
 }
-const void* wgrad_kernel(int taps, int tile) {
+template <bool WIN>
+const void* wgrad_kernel_w(int taps, int tile) {
     switch (taps) {
-        case 1: return wgrad_kernel_t<1>(tile);
-        case 3: return wgrad_kernel_t<3>(tile);
-        case 4: return wgrad_kernel_t<4>(tile);
-        case 5: return wgrad_kernel_t<5>(tile);
-        case 7: return wgrad_kernel_t<7>(tile);
+        case 1: return wgrad_kernel_t<1, WIN>(tile);
+        case 3: return wgrad_kernel_t<3, WIN>(tile);
+        case 4: return wgrad_kernel_t<4, WIN>(tile);
+        case 5: return wgrad_kernel_t<5, WIN>(tile);
+        case 7: return wgrad_kernel_t<7, WIN>(tile);
     }
     return nullptr;
+}
+const void* wgrad_kernel(int taps, int tile, bool win = false) {
+    return win ? wgrad_kernel_w<true>(taps, tile) : wgrad_kernel_w<false>(taps, tile);
 }
 
 int configure_kernels() {
@@ -313,7 +332,9 @@ int configure_kernels() {
     HIP_TRY(hipFuncSetAttribute((const void*)dad::chain_l0_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
     for (int taps : {1, 3, 4, 5, 7})
         for (int tile = 0; tile < kWgradTiles; ++tile)
-            HIP_TRY(hipFuncSetAttribute(wgrad_kernel(taps, tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
+            for (int win = 0; win < 2; ++win)
+                HIP_TRY(hipFuncSetAttribute(wgrad_kernel(taps, tile, win != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)dad::kLdsBytes));
     HIP_TRY(hipFuncSetAttribute((const void*)dad::project_kernel<4, 16>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
     HIP_TRY(hipFuncSetAttribute((const void*)dad::project_kernel<1, 16>,
@@ -366,10 +387,37 @@ int run_conv(dad_model* m, const Plan& plan, const ConvOp& op, const float* xext
     return launch_conv(m, op, batch, io, st);
 }
 
+// GroupNorm -> Mish -> + time embedding -> + residual of a windowed layer (conv_gn_pass.hpp), after its conv
+int launch_gn_pass(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hipStream_t st) {
+    dad::GnPassParams q{};
+    q.src = io.pre != nullptr ? io.pre : io.dst;
+    q.dst = io.dst;
+    q.gamma = op.d_gamma; q.beta = op.d_beta;
+    q.temb = io.temb; q.trow = io.trow; q.temb_stride = m->plan.temb_width;
+    q.res = io.res; q.stats = io.stats;
+    q.C = op.cout; q.L = op.Lout; q.cpg = op.cout / 8; q.lreal = op.lreal; q.cpg_real = op.gn_real;
+    const long elems = (long)q.cpg * q.L;
+    const dim3 grid(8, (unsigned)batch), block(dad::GNP_THREADS);
+    const long per = dad::GNP_THREADS * 4L;              // elements per float4 of every thread
+    if (op.kind != CONV_K5 || q.cpg % 4 != 0 || elems > per * dad::kGnPassMaxNpt)
+        return fail(DAD_E_INVALID, "%s: no GroupNorm pass for %ld-element pairs", op.name.c_str(), elems);
+    if (elems <= per) hipLaunchKernelGGL(dad::gn_pass_kernel<1>, grid, block, 0, st, q);
+    else if (elems <= 2 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<2>, grid, block, 0, st, q);
+    else if (elems <= 4 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<4>, grid, block, 0, st, q);
+    else if (elems <= 8 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<8>, grid, block, 0, st, q);
+    else if (elems <= 16 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<16>, grid, block, 0, st, q);
+    else hipLaunchKernelGGL(dad::gn_pass_kernel<32>, grid, block, 0, st, q);
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
 int launch_conv(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hipStream_t st) {
     LaunchGeom g;
     int rc = plan_launch(*m, op, batch, g);
     if (rc != DAD_OK) return rc;
+    // windowed tiles of a GroupNorm'd layer: the conv stores conv + bias (into the pre-activation buffer when
+    // the training forward keeps one), the pass over whole (sample, group) pairs finishes the block
+    const bool gn_pass = g.windowed && !op.norm.empty();
     ConvParams p{};
     p.src0 = io.src0;
     p.src1 = io.src1;
@@ -379,6 +427,12 @@ int launch_conv(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hip
     p.res = io.res;
     p.dst = io.dst;
     p.pre = io.pre; p.stats = io.stats;
+    if (gn_pass) {
+        p.gamma = p.beta = p.temb = p.res = nullptr;
+        p.trow = nullptr;
+        p.pre = nullptr; p.stats = nullptr;
+        if (io.pre != nullptr) p.dst = io.pre;
+    }
     p.cin0 = op.cin0; p.cin1 = op.cin1; p.cin_pad = op.cin_pad;
     p.M = op.M; p.cpg = op.norm.empty() ? 0 : op.cout / 8; p.cpg_real = op.gn_real;
     p.lreal = op.lreal; p.src_len = op.src_len;
@@ -408,13 +462,14 @@ int launch_conv(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hip
                    ? g_stamps + (size_t)(&op - &m->plan.convs[0]) * 4096 * 8 : nullptr;
 #endif
     const auto& table = kernel_table();
-    const auto it = table.find(KernKey(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded));
+    const auto it = table.find(KernKey(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded, g.windowed));
     if (it == table.end())
         return fail(DAD_E_INVALID, "no kernel for %s (tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d)",
                     op.name.c_str(), g.cfg, op.taps, op.stride, (int)op.x3, (int)op.bdir, (int)g.ragged, (int)g.fused);
     void* args[] = {&p};
     HIP_TRY(hipLaunchKernel((const void*)it->second, dim3(g.gx, g.gy, g.gz), dim3(g.threads), args,
                             g.lds_bytes, st));
+    if (gn_pass) return launch_gn_pass(m, op, batch, io, st);
     return DAD_OK;
 }
 
@@ -1294,6 +1349,15 @@ int dad_train_grad_info(const dad_model* m, int32_t i, const char** key, int64_t
 namespace {
 
 struct WgradGeom { int spc, ksplit, sps, tile, tm, tn; unsigned gx, gy; size_t lds; };
+// Layers longer than a chunk stages (more than 128 rows of G or Z per sample: horizons 256 / 512) run the windowed
+// kernel over windows of kWgradWindow rows of G (and the matching rows of Z) as if they were samples.
+constexpr int kWgradWindow = 64;
+struct WgradShape { int B, Lg, Lz, wshift; };
+inline WgradShape wgrad_shape(int B, int Lg, int Lz) {
+    if (Lg <= 128 && Lz <= 128) return {B, Lg, Lz, 0};
+    const int nw = Lg / kWgradWindow;
+    return {B * nw, kWgradWindow, Lz / nw, ilog2(nw)};
+}
 // Block tile: the largest of 64 x 64 / 64 x 32 / 32 x 32 that still gives the layer 32 tiles (the smaller tiles
 // split K inside the block instead of over the grid: fewer partial slabs to write and add); the batch is then split
 // over blockIdx.z until `target` blocks exist (one block = 8 waves = two per SIMD).
@@ -1334,7 +1398,8 @@ TrainScratch train_scratch(const dad_model& m, int B) {
     t.part += (long)B * round_up(td, 4);
     long ws = 0, tmp = 0, bs = 0;
     auto wg = [&](int M, int C0, int C1, int Lg, int Lz, int taps, int pad, long numel) {
-        const WgradGeom g = wgrad_geom(M, C0 + C1, B, Lg, Lz, taps, pad, m.wgrad_blocks, ((M | C0 | C1) & 3) != 0);
+        const WgradShape ws_ = wgrad_shape(B, Lg, Lz);
+        const WgradGeom g = wgrad_geom(M, C0 + C1, ws_.B, ws_.Lg, ws_.Lz, taps, pad, m.wgrad_blocks, ((M | C0 | C1) & 3) != 0);
         if (g.ksplit > 1) ws = std::max(ws, (long)g.ksplit * numel);
     };
     for (size_t i = 0; i < P.convs.size(); ++i) {
@@ -1503,19 +1568,22 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
     auto wgrad = [&](const float* Gp, int ldg, int M, const float* Z0, int C0, const float* Z1, int C1, float* out,
                      int taps, int stride, int pad, int Lg, int Lz) -> int {
         const bool ragged = ((ldg | C0 | C1 | M) & 3) != 0;      // rows that are not whole aligned float4s (ld == width everywhere)
-        const WgradGeom g = wgrad_geom(M, C0 + C1, B, Lg, Lz, taps, pad, m->wgrad_blocks, ragged);
+        const WgradShape sh = wgrad_shape(B, Lg, Lz);            // windows of long layers run as samples
+        Lg = sh.Lg; Lz = sh.Lz;
+        const WgradGeom g = wgrad_geom(M, C0 + C1, sh.B, Lg, Lz, taps, pad, m->wgrad_blocks, ragged);
         const int kgroups = 8 / (g.tm * g.tn);
         if (g.lds > dad::kLdsBytes || g.spc * Lg > dad::WG_MAX_GROWS || g.spc * dad::wgrad_segz(Lz, taps, pad) > dad::WG_MAX_ZROWS ||
             (g.spc * Lg) % (4 * kgroups) != 0)
             return fail(DAD_E_INVALID, "wgrad: a chunk of %d samples x %d rows does not fit the kernel's staging", g.spc, Lz);
-        const void* fn = wgrad_kernel(taps, g.tile);
+        const void* fn = wgrad_kernel(taps, g.tile, sh.wshift > 0);
         if (fn == nullptr) return fail(DAD_E_INVALID, "wgrad: %d taps", taps);
         dad::WgradParams p{};
         p.G = Gp; p.ldg = ldg; p.M = M;
         p.Z0 = Z0; p.ldz0 = C0; p.C0 = C0; p.Z1 = Z1; p.ldz1 = C1; p.C1 = C1;
         p.out_numel = (long)M * (C0 + C1) * taps;
         p.out = g.ksplit > 1 ? wslab : out;
-        p.B = B; p.Lg = Lg; p.Lz = Lz; p.lg_shift = ilog2(Lg); p.stride = stride; p.pad = pad;
+        p.B = sh.B; p.Lg = Lg; p.Lz = Lz; p.lg_shift = ilog2(Lg); p.stride = stride; p.pad = pad;
+        p.wshift = sh.wshift;
         p.ksplit = g.ksplit; p.samples_per_split = g.sps; p.spc = g.spc;
         p.zero = m->d_zero;
         const dim3 grid(g.gx, g.gy, (unsigned)g.ksplit);
@@ -1677,12 +1745,12 @@ int dad_debug_kernel_table_consistent(void) {
     for (int cfg = 0; cfg < kNumTiles; ++cfg)
         for (int taps = 1; taps <= 7; ++taps)
             for (int stride = 1; stride <= 2; ++stride)
-                for (int f = 0; f < 32; ++f) {
-                    const bool x3 = f & 1, bdir = f & 2, ragged = f & 4, res = f & 8, padded = f & 16;
-                    const bool have = t.count(KernKey(cfg, taps, stride, x3, bdir, ragged, res, padded)) != 0;
-                    if (have != kernel_registered(cfg, taps, stride, x3, bdir, ragged, res, padded)) {
-                        fail(DAD_E_INVALID, "kernel table mismatch at tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d padded=%d (registry %d)",
-                             cfg, taps, stride, (int)x3, (int)bdir, (int)ragged, (int)res, (int)padded, (int)have);
+                for (int f = 0; f < 64; ++f) {
+                    const bool x3 = f & 1, bdir = f & 2, ragged = f & 4, res = f & 8, padded = f & 16, win = f & 32;
+                    const bool have = t.count(KernKey(cfg, taps, stride, x3, bdir, ragged, res, padded, win)) != 0;
+                    if (have != kernel_registered(cfg, taps, stride, x3, bdir, ragged, res, padded, win)) {
+                        fail(DAD_E_INVALID, "kernel table mismatch at tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d padded=%d windowed=%d (registry %d)",
+                             cfg, taps, stride, (int)x3, (int)bdir, (int)ragged, (int)res, (int)padded, (int)win, (int)have);
                         return 0;
                     }
                     hits += have;

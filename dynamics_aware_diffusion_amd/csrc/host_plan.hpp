@@ -120,6 +120,19 @@ constexpr TileCfg kTiles[kNumTiles] = {
     {32, 128, 2, 32},   // 8: layers of 128 positions (horizon 128, QUICKSTART.md:82): one sample per tile
     {64, 128, 1, 16},   // 9: the same with 64-channel tiles (GroupNorm groups of 64 channels)
 };
+constexpr int kMaxTileBN = 128;   // the longest layer a whole-sample tile holds
+// Layers longer than kMaxTileBN (horizons 256 / 512 and the levels above 128 positions) run on WINDOWED tiles:
+// BN consecutive positions of one sample per tile (conv_gemm.hpp, WIN), the GroupNorm tail as a second launch
+// over whole (sample, group) pairs (conv_gn_pass.hpp).  Tiles with windowed instantiations:
+constexpr bool kWinTiles[kNumTiles] = {true, true, true, false, false, false, false, false, false, false};
+constexpr int kGnPassMaxPair = 256 * 4 * 32;   // elements of a (sample, group) pair the GroupNorm pass holds
+inline bool windowed_layer(const ConvOp& op) { return op.Lout > kMaxTileBN; }
+// N tiles of a launch: whole samples per tile, or Lout / BN windows per sample
+inline long tiles_n(const ConvOp& op, int BN, int batch) {
+    if (op.Lout > BN) return (long)batch * (op.Lout / BN);
+    const int spt = BN / op.Lout;
+    return (batch + spt - 1) / spt;
+}
 
 // 1x1 convs have one (tap, group) unit per 8 channels: a deep K chunk keeps enough MFMAs between
 // barriers (128 channels; 64 for the 128-row tile, whose stage would not fit LDS twice).
@@ -253,8 +266,11 @@ inline void decide_kernel_families(HostModel* m) {
         const int cin_all = op.cin0 + op.cin1;
         op.bdir = op.kc == 8 && op.kind == CONV_K5 &&
                   (op.cin0 % 32) == 0 && (cin_all % 32) == 0 && op.cin_pad == cin_all;
-        op.ride = !op.rname.empty() && !op.bdir && m->precision == DAD_PREC_FP32 && !padded_net;
-        op.x3 = !padded_net && ((op.bdir && m->precision == DAD_PREC_F16X3) ||
+        // windowed layers (longer than any tile) run fp32 kernels only, without the ride: split-f16 nets mix them
+        // with the split kernels of their shorter layers
+        const bool win = windowed_layer(op);
+        op.ride = !op.rname.empty() && !op.bdir && m->precision == DAD_PREC_FP32 && !padded_net && !win;
+        op.x3 = !padded_net && !win && ((op.bdir && m->precision == DAD_PREC_F16X3) ||
                 (m->precision == DAD_PREC_F16X3 && op.kc == 16 &&
                  ((op.kind == CONV_K5 && op.taps == 5) || op.kind == CONV_1X1 ||
                   ((op.kind == CONV_DOWN || op.kind == CONV_UP) && (op.cin0 & 63) == 0 && (cin_all & 63) == 0))));
@@ -734,6 +750,16 @@ inline int pack_bwd_final(HostModel* m, std::vector<float>& out) {
 constexpr bool kPaddedTiles[kNumTiles] = {true, true, true, true, true, false, false, false, true, true};
 inline bool tile_valid(const ConvOp& op, int cfg) {
     const TileCfg& t = kTiles[cfg];
+    if (windowed_layer(op)) {
+        // windowed route, only where no whole-sample tile exists: no GroupNorm constraint on the tile (the pass
+        // after the conv owns whole pairs), fp32 LDS-staged kernels
+        if (!kWinTiles[cfg] || op.x3 || op.bdir || op.kc != 16 || op.Lout % t.BN != 0) return false;
+        if ((op.kind == CONV_UP ? op.M / 2 : op.M) % t.BM != 0) return false;
+        if (!op.norm.empty() && (long)(op.cout / 8) * op.Lout > kGnPassMaxPair) return false;
+        const int kc = eff_kc(t.KC, t.BM, op.taps, t.SK, false, false, t.BN);
+        return dad::conv_lds_floats(t.BM, t.BN, kc, op.taps, op.Lin, op.Lout, t.SK, false, op.taps) * sizeof(float) <=
+               dad::kLdsBytes;
+    }
     if (op.net_padded && !kPaddedTiles[cfg]) return false;      // (PADDED kernels exist for the heuristic's tiles)
     const int Mrows = op.kind == CONV_UP ? op.M / 2 : op.M;
     const int cpg = op.norm.empty() ? 1 : op.cout / 8;
@@ -754,8 +780,7 @@ inline int choose_tile(const HostModel& m, const ConvOp& op, int batch) {
     auto valid = [&](int cfg) { return tile_valid(op, cfg); };
     auto blocks = [&](int cfg) {
         const TileCfg& t = kTiles[cfg];
-        const int spt = t.BN / op.Lout;
-        return (long)((batch + spt - 1) / spt) * (op.M / t.BM);
+        return tiles_n(op, t.BN, batch) * (op.M / t.BM);
     };
     if (op.kc == 8) return valid(3) ? 3 : -1;
     if (m.force_tile >= 0 && m.force_tile < kNumTiles && valid(m.force_tile)) return m.force_tile;
@@ -823,8 +848,7 @@ inline uint64_t find_xswz(HostModel& m, int L, int stride, int pad, int kp4, int
 struct SplitPlan { int kslices, chunks_per_slice; long slab_floats; };
 inline SplitPlan plan_split(const HostModel& m, const ConvOp& op, int cfg, int batch) {
     const TileCfg& t = kTiles[cfg];
-    const int spt = t.BN / op.Lout;
-    const long tiles = (long)((batch + spt - 1) / spt) * (op.M / t.BM);
+    const long tiles = tiles_n(op, t.BN, batch) * (op.M / t.BM);
     const int kc = eff_kc(t.KC, t.BM, op.taps, t.SK, op.x3, op.bdir, t.BN);
     const int nchunks = (op.cin0 + op.cin1 + kc - 1) / kc;      // chunks holding real channels
     SplitPlan sp{1, nchunks, 0};
@@ -868,7 +892,8 @@ struct LaunchGeom {
     unsigned gx = 1, gy = 1, gz = 1;
     int xcd_gn = 0, xcd_mts = 0, xcd_ntn = 0;
     bool fused = false;      // the residual conv rides in this launch
-    bool padded = false;     // PADDED instantiation (zero-padded rows / channels)
+    bool padded = false;     // PADDED instantiation (zero-padded rows / channels; every windowed launch)
+    bool windowed = false;   // windowed tiles (layer longer than the tile); a GroupNorm'd layer adds conv_gn_pass
     SplitPlan split{1, 0, 0};
     uint64_t xswz = 0;
 };
@@ -889,8 +914,15 @@ inline bool fused_at(const HostModel& m, const ConvOp& op, int batch) {
 // Which conv-GEMM instantiations exist (the registry of dad_lib.hip, reg_tile, restated on the host so that the
 // planner — and the sanitizer harness, which has no device code — refuses a launch no kernel was compiled for;
 // dad_debug_kernel_table_consistent() compares the two).
-inline bool kernel_registered(int cfg, int taps, int stride, bool x3, bool bdir, bool ragged, bool res, bool padded = false) {
+inline bool kernel_registered(int cfg, int taps, int stride, bool x3, bool bdir, bool ragged, bool res, bool padded = false,
+                              bool windowed = false) {
     if (cfg < 0 || cfg >= kNumTiles) return false;
+    if (windowed) {
+        if (!kWinTiles[cfg] || !padded || x3 || bdir || res) return false;
+        const bool odd = taps == 3 || taps == 5 || taps == 7 || taps == 1;
+        if (ragged) return stride == 1 && odd;
+        return (stride == 1 && (odd || taps == 2)) || (stride == 2 && (taps == 3 || (taps == 5 && kTiles[cfg].KC >= 16)));
+    }
     if (padded && (!kPaddedTiles[cfg] || x3 || res)) return false;
     const bool kc16 = kTiles[cfg].KC >= 16;
     const bool k357 = taps == 3 || taps == 5 || taps == 7;
@@ -930,19 +962,24 @@ inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g)
     if (op.cin_pad % g.kc != 0 && !g.ragged)
         return fail(DAD_E_INVALID, "%s: padded channel count %d is not a multiple of the K chunk %d",
                     op.name.c_str(), op.cin_pad, g.kc);
-    g.padded = op.net_padded;
-    if (!kernel_registered(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded))
-        return fail(DAD_E_INVALID, "no kernel for %s (tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d padded=%d)",
-                    op.name.c_str(), g.cfg, op.taps, op.stride, (int)op.x3, (int)op.bdir, (int)g.ragged, (int)g.fused, (int)g.padded);
+    g.windowed = op.Lout > t.BN;
+    g.padded = op.net_padded || g.windowed;
+    if (!kernel_registered(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded, g.windowed))
+        return fail(DAD_E_INVALID, "no kernel for %s (tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d padded=%d windowed=%d)",
+                    op.name.c_str(), g.cfg, op.taps, op.stride, (int)op.x3, (int)op.bdir, (int)g.ragged, (int)g.fused, (int)g.padded,
+                    (int)g.windowed);
+    if (g.windowed && !op.norm.empty() && (long)(op.cout / 8) * op.Lout > kGnPassMaxPair)
+        return fail(DAD_E_INVALID, "%s: GroupNorm pair of %ld elements (the pass holds %d)", op.name.c_str(),
+                    (long)(op.cout / 8) * op.Lout, kGnPassMaxPair);
     g.threads = 64 * (t.BM / 32) * (t.BN / 32) * t.SK;
     g.lds_bytes = dad::conv_lds_floats(t.BM, t.BN, g.kc, op.taps, op.Lin, op.Lout, t.SK, op.bdir,
                                        op.taps + (g.fused ? 1 : 0)) * sizeof(float);
     if (g.lds_bytes > dad::kLdsBytes)
         return fail(DAD_E_INVALID, "%s: tile %d needs %zu bytes of LDS", op.name.c_str(), g.cfg, g.lds_bytes);
-    const int spt = t.BN / op.Lout;
-    g.ntiles_n = (batch + spt - 1) / spt;
+    const long ntn = tiles_n(op, t.BN, batch);
+    if (ntn > 65535) return fail(DAD_E_INVALID, "batch too large for one launch (%ld N tiles)", ntn);
+    g.ntiles_n = (int)ntn;
     g.mtiles = op.M / t.BM;
-    if (g.ntiles_n > 65535) return fail(DAD_E_INVALID, "batch too large for one launch (%d N tiles)", g.ntiles_n);
     g.split = plan_split(m, op, g.cfg, batch);
     if (g.split.kslices > 1 && (long)g.mtiles * g.ntiles_n > kMaxSplitTiles)
         return fail(DAD_E_INVALID, "%s: %ld tiles exceed the split-K ticket table", op.name.c_str(),

@@ -36,6 +36,7 @@ struct WgradParams {
     int32_t stride, pad;
     int32_t ksplit, samples_per_split, spc;  // batch split over blockIdx.z; samples per staged chunk
     const float* zero;                       // >= 16 bytes of zeros (what the LDS-DMA fetches for halo rows)
+    int32_t wshift;                          // WIN kernels: log2(windows per sample); B, Lg, Lz then count windows
 };
 
 constexpr int WG_THREADS = 512;              // 8 waves: TM x TN wave tiles of 32 x 32 (x TAPS), the rest split K
@@ -86,7 +87,11 @@ __device__ unsigned long long g_wg_stamps[32];
 // loop's back edge: hipcc put copies of the destination registers behind the loads, each with its `s_waitcnt` — a
 // memory round trip per chunk, 12 us per chunk against 5 us of MFMAs by the in-kernel stamps.)
 // !ALIGNED: registers, loaded before the chunk's MFMAs and written to the other stage behind them.
-template <int TAPS, int TM, int TN, bool ALIGNED>
+// WIN: layers longer than a chunk can stage (more than 128 G rows or 160 Z rows per sample: horizons 256 / 512).
+// Every sample is cut into windows of Lg rows of G (the matching Lz rows of Z), consecutive in memory, and the
+// kernel runs over windows as it runs over samples (B, Lg, Lz of the parameters count windows; one per chunk) —
+// except that a window's Z halo rows are the neighbouring rows of its sample, zero only past the sample's ends.
+template <int TAPS, int TM, int TN, bool ALIGNED, bool WIN = false>
 __global__ __launch_bounds__(WG_THREADS) void conv_wgrad(const WgradParams p) {
     constexpr int NT = TM * TN, KG = 8 / NT;
     constexpr int WMW = 32 * TM, WNW = 32 * TN;              // staged columns of G / Z
@@ -127,6 +132,9 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad(const WgradParams p) {
     // (no lambdas or macros over these arrays: a capture by reference puts them on a scratch segment)
     int g_off[WG_GI], z_off[WG_ZI];              // ALIGNED: element offsets from the chunk's first row, -1 = zero
     int g_smp[WG_GI], z_smp[WG_ZI];              // ALIGNED: sample of the chunk; Z: + 4096 when the source is Z1
+    int z_side[WG_ZI];                           // ALIGNED, WIN: 1 / 2 = left / right halo row (exists unless the
+                                                 //   window is the first / last of its sample), 0 = inside the window
+    const int wmask = WIN ? (1 << p.wshift) - 1 : 0;
     float4 gr[WG_GI], zr[WG_ZI];                 // !ALIGNED: the next chunk on its way
     if constexpr (ALIGNED) {
 #pragma unroll
@@ -141,9 +149,10 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad(const WgradParams p) {
             const int i = tid + k * WG_THREADS;
             const int row = i / ZQ, q = i % ZQ, c = c0 + 4 * q;
             const int sl = row / SEGZ, pz = row - sl * SEGZ - p.pad;
-            const bool ok = i < n_z && pz >= 0 && pz < Lz && c < Ctot;
+            const bool ok = i < n_z && (WIN || (pz >= 0 && pz < Lz)) && c < Ctot;
             const bool second = c >= p.C0;
             z_smp[k] = sl + (second ? 4096 : 0);
+            z_side[k] = pz < 0 ? 1 : pz >= Lz ? 2 : 0;
             z_off[k] = !ok ? -1 : second ? (sl * Lz + pz) * p.ldz1 + (c - p.C0) : (sl * Lz + pz) * p.ldz0 + c;
         }
     }
@@ -185,7 +194,12 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad(const WgradParams p) {
                 for (int k = 0; k < WG_ZI; ++k) {
                     const int at = wave * 64 + k * WG_THREADS;
                     if (at < n_z) {
-                        const bool ok = z_off[k] >= 0 && nb + (z_smp[k] & 4095) < s_hi;
+                        bool ok = z_off[k] >= 0 && nb + (z_smp[k] & 4095) < s_hi;
+                        if constexpr (WIN) {                    // (z_off may be negative there: a halo row)
+                            const int w = (nb + (z_smp[k] & 4095)) & wmask;
+                            ok = z_off[k] != -1 && nb + (z_smp[k] & 4095) < s_hi &&
+                                 !(z_side[k] == 1 && w == 0) && !(z_side[k] == 2 && w == wmask);
+                        }
                         const float* src = ok ? (z_smp[k] >= 4096 ? zb1 : zb0) + z_off[k] : p.zero;
                         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                          (__attribute__((address_space(3))) void*)(next + zs_at + 4 * at), 16, 0, 0);
@@ -211,7 +225,9 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad(const WgradParams p) {
                         const int row = i / ZQ, q = i % ZQ;
                         const int sl = row / SEGZ, pz = row - sl * SEGZ - p.pad;
                         const int smp = nb + sl, c = c0 + 4 * q;
-                        if (smp < s_hi && pz >= 0 && pz < Lz && c < Ctot) {
+                        const bool in = WIN ? (pz >= 0 || (smp & wmask) != 0) && (pz < Lz || (smp & wmask) != wmask)
+                                            : pz >= 0 && pz < Lz;
+                        if (smp < s_hi && in && c < Ctot) {
                             if (c < p.C0) v = wg_load4(p.Z0 + (long)(smp * Lz + pz) * p.ldz0, c, p.C0, z0vec);
                             else v = wg_load4(p.Z1 + (long)(smp * Lz + pz) * p.ldz1, c - p.C0, p.C1, z1vec);
                         }
