@@ -33,6 +33,22 @@ DAD_HD inline size_t conv_lds_floats(int BM, int BN, int KC, int taps, int Lin, 
     return k > epi ? k : epi;
 }
 
+// conv_wgrad (train_bwd.hpp)
+constexpr int WG_THREADS = 512;              // 8 waves: TM x TN wave tiles of 32 x 32 (x TAPS), the rest split K
+constexpr int WG_ROWS = 64;                  // G rows per staged chunk: spc = max(1, 64 / Lg) whole samples
+constexpr int WG_MAX_GROWS = 128, WG_MAX_ZROWS = 160;      // rows one chunk may stage (registers of chunk_load)
+
+DAD_HD inline int wgrad_segz(int Lz, int taps, int pad) { return Lz + pad + (taps - 1 - pad); }
+DAD_HD inline int wgrad_round64(int v) { return (v + 63) / 64 * 64; }
+// LDS floats: two stages of a chunk (G rows [spc * Lg][32 TM], Z rows with halo [spc * SEGZ][32 TN], each part
+// rounded up to whole 64-float4 wave-instructions of the LDS-DMA), and afterwards the K-group reduction tree, whose
+// first round parks half of the block's accumulators: 4 waves x TAPS x 16 x 64.
+DAD_HD inline size_t wgrad_lds_floats(int spc, int Lg, int Lz, int taps, int pad, int tm, int tn) {
+    const size_t stage = 2 * ((size_t)wgrad_round64(spc * Lg * 8 * tm) * 4 + (size_t)wgrad_round64(spc * wgrad_segz(Lz, taps, pad) * 8 * tn) * 4);
+    const size_t red = (size_t)4 * taps * 16 * 64;
+    return stage > red ? stage : red;
+}
+
 // conv_cc.hpp: rows of a block's X stage — whole samples with their zero halo, or (layers of more than `nr`
 // positions: windowed tiles) `nr` rows of one sample plus the halo on both sides.
 DAD_HD inline int cc_xrows(int taps, int Lin, int Lout, int nr) {

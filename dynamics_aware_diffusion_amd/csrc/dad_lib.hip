@@ -330,7 +330,7 @@ int configure_kernels() {
     HIP_TRY(hipFuncSetAttribute((const void*)dad::chain_l0_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
     HIP_TRY(hipFuncSetAttribute((const void*)dad::chain_l0_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
     HIP_TRY(hipFuncSetAttribute((const void*)dad::chain_l0_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
-    for (int taps : {1, 3, 4, 5, 7})
+    for (int taps : kWgradTaps)
         for (int tile = 0; tile < kWgradTiles; ++tile)
             for (int win = 0; win < 2; ++win)
                 HIP_TRY(hipFuncSetAttribute(wgrad_kernel(taps, tile, win != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1348,119 +1348,41 @@ int dad_train_grad_info(const dad_model* m, int32_t i, const char** key, int64_t
 
 namespace {
 
-struct WgradGeom { int spc, ksplit, sps, tile, tm, tn; unsigned gx, gy; size_t lds; };
-// Layers longer than a chunk stages (more than 128 rows of G or Z per sample: horizons 256 / 512) run the windowed
-// kernel over windows of kWgradWindow rows of G (and the matching rows of Z) as if they were samples.
-constexpr int kWgradWindow = 64;
-struct WgradShape { int B, Lg, Lz, wshift; };
-inline WgradShape wgrad_shape(int B, int Lg, int Lz) {
-    if (Lg <= 128 && Lz <= 128) return {B, Lg, Lz, 0};
-    const int nw = Lg / kWgradWindow;
-    return {B * nw, kWgradWindow, Lz / nw, ilog2(nw)};
-}
-// Block tile: the largest of 64 x 64 / 64 x 32 / 32 x 32 that still gives the layer 32 tiles (the smaller tiles
-// split K inside the block instead of over the grid: fewer partial slabs to write and add); the batch is then split
-// over blockIdx.z until `target` blocks exist (one block = 8 waves = two per SIMD).
-WgradGeom wgrad_geom(int M, int Ctot, int B, int Lg, int Lz, int taps, int pad, int target = 256, bool ragged = false) {
-    WgradGeom g{};
-    g.spc = std::max(1, dad::WG_ROWS / Lg);
-    while (g.spc > 1 && g.spc * dad::wgrad_segz(Lz, taps, pad) > dad::WG_MAX_ZROWS) g.spc /= 2;
-    static const int tms[3] = {2, 2, 1}, tns[3] = {2, 1, 1};
-    long tiles = 0;
-    for (g.tile = ragged ? 2 : 0; g.tile < 3; ++g.tile) {
-        g.tm = tms[g.tile]; g.tn = tns[g.tile];
-        g.gx = (unsigned)((M + 32 * g.tm - 1) / (32 * g.tm));
-        g.gy = (unsigned)((Ctot + 32 * g.tn - 1) / (32 * g.tn));
-        tiles = (long)g.gx * g.gy;
-        const int kgroups = 8 / (g.tm * g.tn);
-        if ((tiles >= 32 && (g.spc * Lg) % (4 * kgroups) == 0) || g.tile == 2) break;
-    }
-    const int chunks = (B + g.spc - 1) / g.spc;
-    int want = (int)std::max(1L, target / tiles);
-    want = std::min(want, chunks);
-    g.sps = (chunks + want - 1) / want * g.spc;                // samples per split: whole chunks
-    g.ksplit = (B + g.sps - 1) / g.sps;
-    g.lds = dad::wgrad_lds_floats(g.spc, Lg, Lz, taps, pad, g.tm, g.tn) * sizeof(float);
-    if (ragged) g.tile = 3;
-    return g;
-}
-
-// scratch of dad_unet_backward, in floats: gradient mirror of the training plan | per-sample partial sums
-// | wgrad split slabs | padded d x | staging of a down-sampling conv's data gradient | split-K slabs
-struct TrainScratch { long mirror, part, wslab, dxpad, tmp, bslab, total; };
-TrainScratch train_scratch(const dad_model& m, int B) {
-    TrainScratch t{};
-    const Plan& P = m.tplan;
-    const int H = m.cfg.horizon, td = m.cfg.transition_dim;
-    t.mirror = P.floats_per_sample * (long)B;
-    t.part = 0;                                            // every layer's per-sample partial sums, side by side
-    for (const ConvOp& f : P.convs) t.part += (f.norm.empty() ? 1L : 3L) * B * round_up(f.cout, 4);
-    t.part += (long)B * round_up(td, 4);
-    long ws = 0, tmp = 0, bs = 0;
-    auto wg = [&](int M, int C0, int C1, int Lg, int Lz, int taps, int pad, long numel) {
-        const WgradShape ws_ = wgrad_shape(B, Lg, Lz);
-        const WgradGeom g = wgrad_geom(M, C0 + C1, ws_.B, ws_.Lg, ws_.Lz, taps, pad, m.wgrad_blocks, ((M | C0 | C1) & 3) != 0);
-        if (g.ksplit > 1) ws = std::max(ws, (long)g.ksplit * numel);
-    };
-    for (size_t i = 0; i < P.convs.size(); ++i) {
-        const ConvOp& f = P.convs[i];
-        const int cin = f.cin0 + f.cin1;
-        switch (f.kind) {
-            case CONV_K5: case CONV_1X1: wg(f.cout, f.cin0, f.cin1, f.Lin, f.Lin, f.taps, f.taps / 2, (long)f.cout * cin * f.taps); break;
-            case CONV_DOWN: wg(f.cout, cin, 0, f.Lout, f.Lin, 3, 1, (long)f.cout * cin * 3);
-                tmp = std::max(tmp, (long)B * f.Lin * cin); break;
-            case CONV_UP: wg(cin, f.cout, 0, f.Lin, 2 * f.Lin, 4, 1, (long)cin * f.cout * 4); break;
-        }
-        for (int k = 0; k < m.bconvs[i].n; ++k) {
-            const ConvOp& b = m.bconvs[i].op[k];
-            const int cfg = choose_tile(m, b, B);
-            if (cfg >= 0) bs = std::max(bs, plan_split(m, b, cfg, B).slab_floats);
-        }
-    }
-    wg(td, m.cfg.dim, 0, H, H, 1, 0, (long)td * m.cfg.dim);
-    {
-        const int cfg = choose_tile(m, m.bfinal, B);
-        if (cfg >= 0) bs = std::max(bs, plan_split(m, m.bfinal, cfg, B).slab_floats);
-    }
-    t.wslab = ws; t.tmp = tmp; t.bslab = bs;
-    t.dxpad = (long)B * H * round_up(td, 32);
-    if (m.real_horizon > 0 && m.real_horizon != H) t.dxpad += 2L * B * H * round_up(td, 4);      // zero-padded copies of x and d out
-    auto al = [](long v) { return (v + 63) / 64 * 64; };
-    t.mirror = al(t.mirror); t.part = al(t.part); t.wslab = al(t.wslab); t.dxpad = al(t.dxpad);
-    t.tmp = al(t.tmp); t.bslab = al(t.bslab);
-    t.total = t.mirror + t.part + t.wslab + t.dxpad + t.tmp + t.bslab;
-    return t;
-}
-
 size_t train_saved_bytes(const dad_model& m, int B) {
     return ((size_t)m.tplan.floats_per_sample * (size_t)B + (size_t)slab_floats_for(m, B)) * sizeof(float);
 }
 
-// dst[b][l][c] (l < Hp) = l < Hr ? src[b][l][c] : 0      (the trajectory into the zero-padded layout)
-__global__ void pad_rows_kernel(float* dst, const float* src, long B, int Hp, int Hr, int cols) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * Hp * cols) return;
-    const int c = (int)(i % cols);
-    const long r = i / cols;
-    const int l = (int)(r % Hp);
-    const long b = r / Hp;
-    dst[i] = l < Hr ? src[(b * Hr + l) * cols + c] : 0.0f;
+// weight-gradient step `s` of the backward plan, geometry `w` (train_scratch); split batches go through `wslab`
+int launch_wgrad(const dad_model* m, const BwdStep& s, const TrainScratch::Wgrad& w, const float* G, const float* Z0,
+                 const float* Z1, float* out, float* wslab, hipStream_t st) {
+    const WgradGeom& g = w.g;
+    dad::WgradParams p{};
+    p.G = G; p.ldg = s.M; p.M = s.M;                    // ld == width everywhere
+    p.Z0 = Z0; p.ldz0 = s.C0; p.C0 = s.C0; p.Z1 = Z1; p.ldz1 = s.C1; p.C1 = s.C1;
+    p.out_numel = (long)s.M * (s.C0 + s.C1) * s.taps;
+    p.out = g.ksplit > 1 ? wslab : out;
+    p.B = w.sh.B; p.Lg = w.sh.Lg; p.Lz = w.sh.Lz; p.lg_shift = ilog2(w.sh.Lg); p.stride = s.stride; p.pad = s.pad;
+    p.wshift = w.sh.wshift;
+    p.ksplit = g.ksplit; p.samples_per_split = g.sps; p.spc = g.spc;
+    p.zero = m->d_zero;
+    void* args[] = {&p};
+    HIP_TRY(hipLaunchKernel(wgrad_kernel(s.taps, g.tile, w.sh.wshift > 0), dim3(g.gx, g.gy, (unsigned)g.ksplit),
+                            dim3(dad::WG_THREADS), args, g.lds, st));
+    if (g.ksplit > 1) {
+        const long n4 = p.out_numel / 4;
+        hipLaunchKernelGGL(dad::sum_slabs_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, out, wslab, n4, g.ksplit);
+        HIP_TRY(hipGetLastError());
+    }
+    return DAD_OK;
 }
-// dst[b][l][c] (l < Hr, c < cols) = src[(b * Hp + l) * ld + c]
-__global__ void slice_rows_cols_kernel(float* dst, const float* src, long B, int Hp, int Hr, int cols, int ld) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * Hr * cols) return;
-    const int c = (int)(i % cols);
-    const long r = i / cols;
-    const int l = (int)(r % Hr);
-    const long b = r / Hr;
-    dst[i] = src[(b * Hp + l) * ld + c];
-}
-__global__ void slice_cols_kernel(float* dst, const float* src, long rows, int cols, int ld) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * cols) return;
-    const long r = i / cols;
-    dst[i] = src[r * ld + (i - r * cols)];
+
+// y += x over n floats (n a multiple of 4), or y = x (BW_SET)
+int accumulate(float* y, const float* x, long n, BwdWrite how, hipStream_t st) {
+    if (how == BW_SET) { HIP_TRY(hipMemcpyAsync(y, x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st)); return DAD_OK; }
+    const long n4 = n / 4;
+    hipLaunchKernelGGL(dad::add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, y, x, n4);
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
 }
 
 int check_train(const dad_model* m, int batch) {
@@ -1478,7 +1400,11 @@ extern "C" {
 int dad_train_workspace_bytes(const dad_model* m, int32_t batch, size_t* saved_bytes, size_t* scratch_bytes) {
     if (!m || batch <= 0) return fail(DAD_E_INVALID, "bad argument");
     if (saved_bytes) *saved_bytes = train_saved_bytes(*m, batch);
-    if (scratch_bytes) *scratch_bytes = (size_t)train_scratch(*m, batch).total * sizeof(float);
+    if (scratch_bytes) {
+        TrainScratch ts;
+        train_scratch(*m, batch, ts);          // a batch the backward pass refuses is refused there, not here
+        *scratch_bytes = (size_t)ts.total * sizeof(float);
+    }
     return DAD_OK;
 }
 
@@ -1508,15 +1434,18 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
     for (int32_t i = 0; i < n_grad_tensors; ++i)
         if (!grad_tensors[i]) return fail(DAD_E_INVALID, "gradient tensor %d ('%s') is null", i, m->grad_slots[i].key.c_str());
     const int B = batch;
-    const TrainScratch ts = train_scratch(*m, B);
+    TrainScratch ts;
+    const int geom_rc = train_scratch(*m, B, ts);
     if (saved_bytes < train_saved_bytes(*m, B) || scratch_bytes < (size_t)ts.total * sizeof(float))
         return fail(DAD_E_WORKSPACE, "backward workspaces too small (saved %zu / %zu, scratch %zu / %zu bytes)", saved_bytes,
                     train_saved_bytes(*m, B), scratch_bytes, (size_t)ts.total * sizeof(float));
+    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
+    if (geom_rc != DAD_OK) return geom_rc;
+    if (d_x != nullptr && !m->bdx) return fail(DAD_E_STATE, "backward: no gradient reached the trajectory");
+
     hipStream_t st = (hipStream_t)stream;
     const Plan& P = m->tplan;
-    const std::vector<ConvOp>& convs = P.convs;
-    const dad_cfg& c = m->cfg;
-    const int H = c.horizon, td = c.transition_dim, tdp = round_up(td, 32);
+    const int H = m->cfg.horizon, td = m->cfg.transition_dim, tdp = round_up(td, 32);
     float* const saved = (float*)saved_v;
     float* const mirror = (float*)scratch_v;
     float* const part = mirror + ts.mirror;
@@ -1524,15 +1453,6 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
     float* const dxpad = wslab + ts.wslab;
     float* const tmp = dxpad + ts.dxpad;
     float* const bslab = tmp + ts.tmp;
-    auto act = [&](int id) -> float* { return id >= 0 ? saved + P.bufs[id].offset * (long)B : nullptr; };
-    std::vector<int> alias(P.bufs.size(), -1);       // gradient of this buffer IS the gradient of that one
-    std::vector<char> written(P.bufs.size(), 0);
-    auto resolve = [&](int id) { while (alias[id] >= 0) id = alias[id]; return id; };
-    auto grd = [&](int id) -> float* { return mirror + P.bufs[resolve(id)].offset * (long)B; };
-    std::vector<int> owner(P.bufs.size(), -1);
-    for (size_t i = 0; i < convs.size(); ++i) owner[convs[i].dst] = (int)i;
-    bool dx_written = false;
-    auto G = [&](const std::string& key) -> float* { return grad_tensors[m->grad_index.at(key)]; };
     // zero-padded horizon: the trajectory and d loss / d out arrive in their real shape (B, H_real, td); the pass runs on
     // copies in the padded layout (zero rows behind the real ones), d x goes back through the same row map
     const int Hr = traj_horizon(m);
@@ -1540,186 +1460,99 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
         float* const xpad = dxpad + (long)B * H * tdp;
         float* const dopad = xpad + (long)B * H * round_up(td, 4);
         const long n = (long)B * H * td;
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xpad, x, (long)B, H, Hr, td);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dopad, d_out, (long)B, H, Hr, td);
+        hipLaunchKernelGGL(dad::pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xpad, x, (long)B, H, Hr, td);
+        hipLaunchKernelGGL(dad::pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dopad, d_out, (long)B, H, Hr, td);
         HIP_TRY(hipGetLastError());
         x = xpad; d_out = dopad;
     }
-
-    // y += x over n floats (n a multiple of 4), or y = x when y holds nothing yet
-    auto accumulate = [&](float* y, const float* xs, long n, bool have) -> int {
-        if (!have) { HIP_TRY(hipMemcpyAsync(y, xs, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st)); return DAD_OK; }
-        const long n4 = n / 4;
-        hipLaunchKernelGGL(dad::add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, y, xs, n4);
-        HIP_TRY(hipGetLastError());
-        return DAD_OK;
-    };
-    // per-sample partial sums of every layer live side by side in `part`; ONE launch at the end reduces them all
-    std::vector<std::tuple<float*, const float*, int>> sums;      // (out[C], part[B][C], C)
-    long part_used = 0;
-    auto part_take = [&](int C) -> float* { float* q = part + part_used; part_used += (long)B * round_up(C, 4); return q; };
-    auto bias_grad = [&](float* out, const float* g, int rows_per_sample, int C) -> int {
-        float* q = part_take(C);
-        hipLaunchKernelGGL(dad::row_partial_sums_kernel, dim3(B), dim3(256), 0, st, q, g, rows_per_sample, C, C);
-        HIP_TRY(hipGetLastError());
-        sums.emplace_back(out, q, C);
-        return DAD_OK;
-    };
-    auto wgrad = [&](const float* Gp, int ldg, int M, const float* Z0, int C0, const float* Z1, int C1, float* out,
-                     int taps, int stride, int pad, int Lg, int Lz) -> int {
-        const bool ragged = ((ldg | C0 | C1 | M) & 3) != 0;      // rows that are not whole aligned float4s (ld == width everywhere)
-        const WgradShape sh = wgrad_shape(B, Lg, Lz);            // windows of long layers run as samples
-        Lg = sh.Lg; Lz = sh.Lz;
-        const WgradGeom g = wgrad_geom(M, C0 + C1, sh.B, Lg, Lz, taps, pad, m->wgrad_blocks, ragged);
-        const int kgroups = 8 / (g.tm * g.tn);
-        if (g.lds > dad::kLdsBytes || g.spc * Lg > dad::WG_MAX_GROWS || g.spc * dad::wgrad_segz(Lz, taps, pad) > dad::WG_MAX_ZROWS ||
-            (g.spc * Lg) % (4 * kgroups) != 0)
-            return fail(DAD_E_INVALID, "wgrad: a chunk of %d samples x %d rows does not fit the kernel's staging", g.spc, Lz);
-        const void* fn = wgrad_kernel(taps, g.tile, sh.wshift > 0);
-        if (fn == nullptr) return fail(DAD_E_INVALID, "wgrad: %d taps", taps);
-        dad::WgradParams p{};
-        p.G = Gp; p.ldg = ldg; p.M = M;
-        p.Z0 = Z0; p.ldz0 = C0; p.C0 = C0; p.Z1 = Z1; p.ldz1 = C1; p.C1 = C1;
-        p.out_numel = (long)M * (C0 + C1) * taps;
-        p.out = g.ksplit > 1 ? wslab : out;
-        p.B = sh.B; p.Lg = Lg; p.Lz = Lz; p.lg_shift = ilog2(Lg); p.stride = stride; p.pad = pad;
-        p.wshift = sh.wshift;
-        p.ksplit = g.ksplit; p.samples_per_split = g.sps; p.spc = g.spc;
-        p.zero = m->d_zero;
-        const dim3 grid(g.gx, g.gy, (unsigned)g.ksplit);
-        void* args[] = {&p};
-        HIP_TRY(hipLaunchKernel(fn, grid, dim3(dad::WG_THREADS), args, g.lds, st));
-        if (g.ksplit > 1) {
-            if (p.out_numel % 4 != 0) return fail(DAD_E_INVALID, "wgrad: %ld gradient elements (not a multiple of 4)", p.out_numel);
-            const long n4 = p.out_numel / 4;
-            hipLaunchKernelGGL(dad::sum_slabs_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, out, wslab, n4, g.ksplit);
-            HIP_TRY(hipGetLastError());
+    auto ptr = [&](const BwdRef& r) -> float* {
+        switch (r.sp) {
+            case BSP_ACT: return saved + P.bufs[r.buf].offset * (long)B;
+            case BSP_GRAD: return mirror + P.bufs[r.buf].offset * (long)B;
+            case BSP_X: return const_cast<float*>(x);                 // read only
+            case BSP_DOUT: return const_cast<float*>(d_out);          // read only
+            case BSP_DX: return dxpad;
+            default: return nullptr;
         }
-        return DAD_OK;
-    };
-    // data gradient `bop` of dH into buffer `target` (-2: the trajectory), adding to what is there
-    auto dgrad = [&](const ConvOp& bop, const float* dH, int target, long target_floats) -> int {
-        float* dst;
-        bool have;
-        if (target == -2) { dst = dxpad; have = dx_written; dx_written = true; }
-        else { dst = grd(target); have = written[resolve(target)]; written[resolve(target)] = 1; }
-        ConvIO io;
-        io.src0 = dH; io.slab = bslab;
-        if (bop.kind == CONV_UP && have) {                 // the interleaving store has no residual operand
-            io.dst = tmp;
-            int r = launch_conv(m, bop, B, io, st);
-            if (r != DAD_OK) return r;
-            return accumulate(dst, tmp, target_floats, true);
-        }
-        io.dst = dst;
-        io.res = have ? dst : nullptr;
-        return launch_conv(m, bop, B, io, st);
     };
 
-    // ---- final_conv[1] (1x1, dim -> td; forward in final_posterior_kernel)
-    {
-        if ((rc = bias_grad(G("final_conv.1.bias"), d_out, H, td)) != DAD_OK) return rc;
-        if ((rc = wgrad(d_out, td, td, act(P.final_act), c.dim, nullptr, 0, G("final_conv.1.weight"), 1, 1, 0, H, H)) != DAD_OK)
-            return rc;
-        if ((rc = dgrad(m->bfinal, d_out, P.final_act, (long)B * H * c.dim)) != DAD_OK) return rc;
-    }
-    for (int i = (int)convs.size() - 1; i >= 0; --i) {
-        const ConvOp& f = convs[i];
-        if (!written[resolve(f.dst)])
-            return fail(DAD_E_STATE, "backward: no gradient reached the output of %s", f.name.c_str());
-        const float* gout = grd(f.dst);
-        const int out_rows = f.kind == CONV_UP ? 2 * f.Lout : f.Lout;      // rows per sample of the output
-        const long out_floats = (long)B * out_rows * f.cout;
-        const float* dH = gout;
-        if (!f.norm.empty()) {
-            if (f.res == -2) {                             // identity residual of the trajectory itself (td == C)
-                if ((rc = accumulate(dxpad, gout, out_floats, dx_written)) != DAD_OK) return rc;
-                dx_written = true;
-            } else if (f.cat0 >= 0) {                      // identity residual over [cat0 | cat1]: each side takes its columns
-                const long rows = (long)B * out_rows;
-                const int ids[2] = {f.cat0, f.cat1}, cs[2] = {f.cat_c0, f.cat_c1};
-                for (int k = 0, off = 0; k < 2; off += cs[k], ++k) {
-                    const int r = resolve(ids[k]);
-                    const long n4 = rows * (cs[k] / 4);
-                    hipLaunchKernelGGL(dad::take_cols_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                                       grd(ids[k]), gout, rows, cs[k], f.cout, off, (int)written[r]);
-                    written[r] = 1;
+    // the steps of the backward plan (build_backward_plan), in order
+    size_t nw = 0;
+    for (const BwdStep& s : m->bsteps) {
+        switch (s.kind) {
+            case BK_BIAS:
+                hipLaunchKernelGGL(dad::row_partial_sums_kernel, dim3(B), dim3(256), 0, st, part + s.part * B, ptr(s.in),
+                                   s.rows, s.C, s.C);
+                HIP_TRY(hipGetLastError());
+                break;
+            case BK_WGRAD:
+                if ((rc = launch_wgrad(m, s, ts.wgrads[nw++], ptr(s.in), ptr(s.z0), ptr(s.z1), grad_tensors[s.slot], wslab, st)) != DAD_OK)
+                    return rc;
+                break;
+            case BK_DGRAD: {
+                ConvIO io;
+                io.src0 = ptr(s.in); io.slab = bslab;
+                io.dst = s.write == BW_STAGE ? tmp : ptr(s.out);
+                io.res = s.write == BW_ADD ? io.dst : nullptr;
+                if ((rc = launch_conv(m, bwd_op(*m, s), B, io, st)) != DAD_OK) return rc;
+                if (s.write == BW_STAGE && (rc = accumulate(ptr(s.out), tmp, s.n * B, BW_ADD, st)) != DAD_OK) return rc;
+                break;
+            }
+            case BK_GN: {
+                const ConvOp& f = P.convs[s.conv];
+                const long c4 = round_up(f.cout, 4);
+                dad::GnBwdParams gp{};
+                gp.dA = ptr(s.in); gp.h = saved + P.bufs[f.pre].offset * (long)B; gp.stats = saved + P.bufs[f.stats].offset * (long)B;
+                gp.gamma = f.d_gamma; gp.beta = f.d_beta;
+                gp.dH = ptr(s.out);
+                gp.part_dgamma = part + s.part * B; gp.part_dbeta = gp.part_dgamma + c4 * B; gp.part_dbias = gp.part_dbeta + c4 * B;
+                gp.dtemb = f.temb_off >= 0 ? d_temb_rows + f.temb_off : nullptr;
+                gp.temb_stride = P.temb_width;
+                gp.C = f.cout; gp.L = f.Lout; gp.cpg = f.cout / 8; gp.lreal = f.lreal; gp.cpg_real = f.gn_real;
+                gp.B = B;
+                const dim3 wgrid((unsigned)((B * 8 + 3) / 4));
+                switch (s.nv) {
+                    case 1: hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<1>, wgrid, dim3(256), 0, st, gp); break;
+                    case 2: hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<2>, wgrid, dim3(256), 0, st, gp); break;
+                    case 4: hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<4>, wgrid, dim3(256), 0, st, gp); break;
+                    case 8: hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<8>, wgrid, dim3(256), 0, st, gp); break;
+                    case 16: hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<16>, wgrid, dim3(256), 0, st, gp); break;
+                    default: hipLaunchKernelGGL(dad::gn_mish_bwd_kernel, dim3(B, 8), dim3(dad::GNB_THREADS), 0, st, gp);
                 }
                 HIP_TRY(hipGetLastError());
-            } else if (f.res >= 0) {
-                const int q = owner[f.res];
-                const bool conv_out = q >= 0 && convs[q].kind == CONV_1X1 && convs[q].norm.empty();
-                if (conv_out) { alias[f.res] = resolve(f.dst); }         // the 1x1 residual conv's output gradient
-                else {
-                    const int r = resolve(f.res);
-                    if ((rc = accumulate(grd(f.res), gout, out_floats, written[r])) != DAD_OK) return rc;
-                    written[r] = 1;
-                }
+                break;
             }
-            dad::GnBwdParams gp{};
-            gp.dA = gout; gp.h = act(f.pre); gp.stats = act(f.stats);
-            gp.gamma = f.d_gamma; gp.beta = f.d_beta;
-            gp.dH = mirror + P.bufs[f.pre].offset * (long)B;
-            gp.part_dgamma = part_take(f.cout); gp.part_dbeta = part_take(f.cout); gp.part_dbias = part_take(f.cout);
-            gp.dtemb = f.temb_off >= 0 ? d_temb_rows + f.temb_off : nullptr;
-            gp.temb_stride = P.temb_width;
-            gp.C = f.cout; gp.L = f.Lout; gp.cpg = f.cout / 8; gp.lreal = f.lreal; gp.cpg_real = f.gn_real;
-            gp.B = B;
-            {   // one wave per (sample, group) pair while the pair fits its registers, else one block per pair
-                const int f4 = gp.cpg / 4 * gp.L;
-                const dim3 wgrid((unsigned)((B * 8 + 3) / 4));
-                if (f4 <= 64) hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<1>, wgrid, dim3(256), 0, st, gp);
-                else if (f4 <= 128) hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<2>, wgrid, dim3(256), 0, st, gp);
-                else if (f4 <= 256) hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<4>, wgrid, dim3(256), 0, st, gp);
-                else if (f4 <= 512) hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<8>, wgrid, dim3(256), 0, st, gp);
-                else if (f4 <= 1024) hipLaunchKernelGGL(dad::gn_mish_bwd_wave_kernel<16>, wgrid, dim3(256), 0, st, gp);
-                else hipLaunchKernelGGL(dad::gn_mish_bwd_kernel, dim3(B, 8), dim3(dad::GNB_THREADS), 0, st, gp);
+            case BK_RESID:
+                if ((rc = accumulate(ptr(s.out), ptr(s.in), s.n * B, s.write, st)) != DAD_OK) return rc;
+                break;
+            case BK_COLS: {
+                const long rows = (long)B * s.rows, n4 = rows * (s.C / 4);
+                hipLaunchKernelGGL(dad::take_cols_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
+                                   ptr(s.out), ptr(s.in), rows, s.C, s.ld, s.off, (int)(s.write == BW_ADD));
+                HIP_TRY(hipGetLastError());
+                break;
             }
-            HIP_TRY(hipGetLastError());
-            sums.emplace_back(G(f.norm + ".weight"), gp.part_dgamma, f.cout);
-            sums.emplace_back(G(f.norm + ".bias"), gp.part_dbeta, f.cout);
-            sums.emplace_back(G(f.name + ".bias"), gp.part_dbias, f.cout);
-            dH = gp.dH;
-        } else {
-            if ((rc = bias_grad(G(f.name + ".bias"), dH, out_rows, f.cout)) != DAD_OK) return rc;
-        }
-        const float* s0 = f.src0 == -2 ? x : act(f.src0);
-        const float* s1 = act(f.src1);
-        float* gw = G(f.name + ".weight");
-        switch (f.kind) {
-            case CONV_K5: case CONV_1X1:
-                rc = wgrad(dH, f.cout, f.cout, s0, f.cin0, s1, f.cin1, gw, f.taps, 1, f.taps / 2, f.Lin, f.Lin); break;
-            case CONV_DOWN:
-                rc = wgrad(dH, f.cout, f.cout, s0, f.cin0, nullptr, 0, gw, 3, 2, 1, f.Lout, f.Lin); break;
-            case CONV_UP:
-                rc = wgrad(s0, f.cin0, f.cin0, dH, f.cout, nullptr, 0, gw, 4, 2, 1, f.Lin, 2 * f.Lin); break;
-        }
-        if (rc != DAD_OK) return rc;
-        const HostModel::BwdConv& b = m->bconvs[i];
-        for (int k = 0; k < b.n; ++k) {
-            const int target = k == 0 ? f.src0 : f.src1;
-            if ((rc = dgrad(b.op[k], dH, target, (long)B * f.Lin * b.c_n[k])) != DAD_OK) return rc;
         }
     }
-    if (part_used > ts.part) return fail(DAD_E_WORKSPACE, "backward: partial sums overran their region (%ld > %ld floats)", part_used, ts.part);
-    for (size_t at = 0; at < sums.size(); at += dad::COLS_MAX) {
+    // every layer's per-sample partial sums, reduced over the batch by as few launches as the argument block allows
+    for (size_t at = 0; at < m->bsums.size(); at += dad::COLS_MAX) {
         dad::ColSumsMany cs{};
-        const int n = (int)std::min<size_t>(dad::COLS_MAX, sums.size() - at);
+        const int n = (int)std::min<size_t>(dad::COLS_MAX, m->bsums.size() - at);
         int widest = 0;
         for (int k = 0; k < n; ++k) {
-            cs.out[k] = std::get<0>(sums[at + k]); cs.part[k] = std::get<1>(sums[at + k]); cs.C[k] = std::get<2>(sums[at + k]);
-            widest = std::max(widest, cs.C[k]);
+            const BwdSum& q = m->bsums[at + k];
+            cs.out[k] = grad_tensors[q.slot]; cs.part[k] = part + q.part * B; cs.C[k] = q.C;
+            widest = std::max(widest, q.C);
         }
         hipLaunchKernelGGL(dad::col_sums_many_kernel, dim3((unsigned)((widest + 31) / 32), (unsigned)n), dim3(256), 0, st, cs, B);
         HIP_TRY(hipGetLastError());
     }
     if (d_x != nullptr) {
-        if (!dx_written) return fail(DAD_E_STATE, "backward: no gradient reached the trajectory");
         const long n = (long)B * Hr * td;
         if (Hr != H)
-            hipLaunchKernelGGL(slice_rows_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_x, dxpad, (long)B, H, Hr, td, tdp);
+            hipLaunchKernelGGL(dad::slice_rows_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_x, dxpad, (long)B, H, Hr, td, tdp);
         else
-            hipLaunchKernelGGL(slice_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_x, dxpad, (long)B * H, td, tdp);
+            hipLaunchKernelGGL(dad::slice_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_x, dxpad, (long)B * H, td, tdp);
         HIP_TRY(hipGetLastError());
     }
     return DAD_OK;

@@ -1,7 +1,8 @@
 // host_plan.hpp — everything libdad_hip.so decides on the HOST before a kernel is launched:
 // validation of the architecture, the launch plan of TemporalUnet.forward, workspace layout,
 // weight packing (fp32 and split-f16 images), tile choice, grid-level split-K, the LDS slot
-// shifts and the launch geometry of every conv-GEMM.  Plain C++17, no HIP: dad_lib.hip includes
+// shifts, the launch geometry of every conv-GEMM, and the backward pass as a list of steps with its
+// per-batch geometry.  Plain C++17, no HIP: dad_lib.hip includes
 // it for the product, tests/sanitize/host_check.cpp compiles it host-only under
 // -fsanitize=address,undefined.
 #pragma once
@@ -13,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <iterator>
 #include <map>
 #include <string>
 #include <vector>
@@ -145,6 +147,40 @@ constexpr int eff_kc(int cfg_kc, int bm, int taps, int sk = 1, bool x3 = false, 
                                        : cfg_kc;
 }
 
+// ---- the backward pass as a list of steps (build_backward_plan), replayed by dad_unet_backward
+// Operand of a step: a training-plan buffer's saved activation or its gradient (aliases resolved), or one of the
+// pass's external tensors: the trajectory x, d loss / d out, the padded d x.
+enum BwdSpace : int8_t { BSP_NONE, BSP_ACT, BSP_GRAD, BSP_X, BSP_DOUT, BSP_DX };
+struct BwdRef { BwdSpace sp = BSP_NONE; int buf = -1; };
+enum BwdKind : int8_t {
+    BK_BIAS,     // per-sample partial sums of a bias gradient (row_partial_sums_kernel)
+    BK_WGRAD,    // weight gradient (conv_wgrad)
+    BK_DGRAD,    // data gradient: a conv-GEMM launch of BwdConv::op / bfinal
+    BK_GN,       // GroupNorm + Mish backward, with the partial sums of d gamma, d beta, d bias
+    BK_RESID,    // identity residual: the block's gradient into d x or a buffer
+    BK_COLS,     // identity residual over a concat: one side's columns of the block's gradient
+};
+// How a step writes `out`: the first write of a gradient overwrites, later ones accumulate; a CONV_UP data gradient
+// (its interleaving store has no residual operand) accumulates by staging through `tmp` and adding.
+enum BwdWrite : int8_t { BW_SET, BW_ADD, BW_STAGE };
+struct BwdStep {
+    BwdKind kind;
+    BwdWrite write = BW_SET;
+    int conv = -1;          // forward conv (index into tplan.convs); -1: final_conv[1]
+    int sub = 0;            // DGRAD: which data-gradient launch of that conv
+    BwdRef in, out;         // the gradient read (WGRAD: the G operand) and the tensor written
+    BwdRef z0, z1;          // WGRAD: the Z operands
+    int slot = -1;          // WGRAD: gradient slot of the weight
+    long part = 0;          // BIAS / GN: first partial-sum row, in units of B floats (GN: d gamma, d beta, d bias)
+    long n = 0;             // RESID / DGRAD: floats per sample of `out`
+    int rows = 0, C = 0;    // BIAS / COLS: rows per sample and channels (COLS: taken at column `off` of `ld`)
+    int off = 0, ld = 0;
+    int M = 0, C0 = 0, C1 = 0, taps = 0, stride = 0, pad = 0, Lg = 0, Lz = 0;   // WGRAD: the GEMM
+    int nv = 0;             // GN: float4 per lane of gn_mish_bwd_wave_kernel<nv>; 0: gn_mish_bwd_kernel
+};
+// col_sums_many_kernel entry: gradient slot <- the sum over the batch of C partial-sum columns at `part`
+struct BwdSum { int slot; long part; int C; };
+
 // Host half of a model: what exists before any device allocation.
 struct HostModel {
     dad_cfg cfg{};
@@ -190,8 +226,12 @@ struct HostModel {
     struct GradSlot { std::string key; long offset, numel; };
     std::vector<GradSlot> grad_slots;        // flat gradient buffer: reference state_dict keys, torch layouts
     long grad_numel = 0;
-    std::map<std::string, long> grad_at;     // key -> offset
-    std::map<std::string, int> grad_index;   // key -> index into grad_slots
+    std::vector<BwdStep> bsteps;             // the backward pass in launch order
+    std::vector<BwdSum> bsums;               // the column sums that end it, in order
+    long bpart = 0;                          // partial-sum rows of the pass, in units of B floats
+    bool bdx = false;                        // a gradient reaches the trajectory
+    int bwd_rc = DAD_OK;                     // structural error of the pass, reported by dad_unet_backward
+    std::string bwd_err;
     int max_cout = 0;                        // widest conv output (per-sample partial sums)
     int max_bwd_m = 0;                       // widest data-gradient launch (zero bias row)
 };
@@ -486,16 +526,18 @@ inline ConvOp make_bwd_op(const ConvOp& f, const char* tag, ConvKind kind, int t
     return b;
 }
 inline int build_backward_plan(HostModel* m) {
-    const std::vector<ConvOp>& convs = m->tplan.convs;
+    const Plan& P = m->tplan;
+    const std::vector<ConvOp>& convs = P.convs;
+    const dad_cfg& c = m->cfg;
     m->bconvs.assign(convs.size(), HostModel::BwdConv());
-    m->grad_slots.clear(); m->grad_at.clear(); m->grad_index.clear(); m->grad_numel = 0;
-    m->max_cout = m->cfg.dim; m->max_bwd_m = m->cfg.dim;
+    m->grad_slots.clear(); m->grad_numel = 0;
+    m->max_cout = c.dim; m->max_bwd_m = c.dim;
     auto slot = [&](const std::string& key, long numel) {
-        m->grad_index[key] = (int)m->grad_slots.size();
         m->grad_slots.push_back({key, m->grad_numel, numel});
-        m->grad_at[key] = m->grad_numel;
         m->grad_numel += (numel + 3) / 4 * 4;
+        return (int)m->grad_slots.size() - 1;
     };
+    std::vector<int> wslot(convs.size()), bslot(convs.size()), gslot(convs.size(), -1);   // gslot + 1: GroupNorm bias
     for (size_t i = 0; i < convs.size(); ++i) {
         const ConvOp& f = convs[i];
         HostModel::BwdConv& b = m->bconvs[i];
@@ -508,17 +550,17 @@ inline int build_backward_plan(HostModel* m) {
                     b.c_n[s] = s == 0 ? f.cin0 : f.cin1;
                     b.op[s] = make_bwd_op(f, s == 0 ? ".dgrad0" : ".dgrad1", f.kind, f.taps, 1, f.cout, b.c_n[s], f.Lin, f.Lin);
                 }
-                slot(f.name + ".weight", (long)f.cout * cin * f.taps);
+                wslot[i] = slot(f.name + ".weight", (long)f.cout * cin * f.taps);
                 break;
             case CONV_DOWN:
                 b.n = 1; b.c_lo[0] = 0; b.c_n[0] = cin;
                 b.op[0] = make_bwd_op(f, ".dgrad0", CONV_UP, 2, 1, f.cout, cin, f.Lout, f.Lout);
-                slot(f.name + ".weight", (long)f.cout * cin * 3);
+                wslot[i] = slot(f.name + ".weight", (long)f.cout * cin * 3);
                 break;
             case CONV_UP:
                 b.n = 1; b.c_lo[0] = 0; b.c_n[0] = cin;
                 b.op[0] = make_bwd_op(f, ".dgrad0", CONV_DOWN, 5, 2, f.cout, cin, 2 * f.Lin, f.Lin);
-                slot(f.name + ".weight", (long)cin * f.cout * 4);
+                wslot[i] = slot(f.name + ".weight", (long)cin * f.cout * 4);
                 break;
         }
         // zero-padded horizon: the data gradient is zero-padded like every activation (its launches store zeros
@@ -530,19 +572,125 @@ inline int build_backward_plan(HostModel* m) {
             b.op[s].lreal = (real_rows > 0 && real_rows != rows) ? real_rows : 0;
             b.op[s].net_padded = f.net_padded;
         }
-        slot(f.name + ".bias", f.cout);
-        if (!f.norm.empty()) { slot(f.norm + ".weight", f.cout); slot(f.norm + ".bias", f.cout); }
+        bslot[i] = slot(f.name + ".bias", f.cout);
+        if (!f.norm.empty()) { gslot[i] = slot(f.norm + ".weight", f.cout); slot(f.norm + ".bias", f.cout); }
         m->max_cout = std::max(m->max_cout, f.cout);
         for (int s = 0; s < b.n; ++s) m->max_bwd_m = std::max(m->max_bwd_m, b.op[s].M);
     }
-    {   // final_conv[1]: 1x1, dim -> transition_dim; its data gradient is a 1x1 conv transition_dim -> dim
+    // final_conv[1]: 1x1, dim -> transition_dim; its data gradient is a 1x1 conv transition_dim -> dim
+    {
         ConvOp f;
         f.name = "final_conv.1";
-        m->bfinal = make_bwd_op(f, ".dgrad0", CONV_1X1, 1, 1, m->cfg.transition_dim, m->cfg.dim, m->cfg.horizon, m->cfg.horizon);
-        if (m->real_horizon > 0 && m->real_horizon != m->cfg.horizon) { m->bfinal.lreal = m->real_horizon; m->bfinal.net_padded = true; }
-        slot("final_conv.1.weight", (long)m->cfg.transition_dim * m->cfg.dim);
-        slot("final_conv.1.bias", m->cfg.transition_dim);
+        m->bfinal = make_bwd_op(f, ".dgrad0", CONV_1X1, 1, 1, c.transition_dim, c.dim, c.horizon, c.horizon);
+        if (m->real_horizon > 0 && m->real_horizon != c.horizon) { m->bfinal.lreal = m->real_horizon; m->bfinal.net_padded = true; }
     }
+    const int fw = slot("final_conv.1.weight", (long)c.transition_dim * c.dim);
+    const int fb = slot("final_conv.1.bias", c.transition_dim);
+
+    // ---- the pass itself: final_conv[1], then the convs in reverse.  Gradients that meet in one tensor accumulate
+    // in the order of this walk; the gradient of a 1x1 residual conv's output IS its block's gradient (an alias).
+    std::vector<BwdStep>& S = m->bsteps;
+    S.clear(); m->bsums.clear(); m->bpart = 0;
+    m->bwd_rc = DAD_OK; m->bwd_err.clear();
+    std::vector<int> alias(P.bufs.size(), -1), owner(P.bufs.size(), -1);
+    std::vector<char> written(P.bufs.size(), 0);
+    char dx = 0;
+    for (size_t i = 0; i < convs.size(); ++i) owner[convs[i].dst] = (int)i;
+    auto resolve = [&](int id) { while (alias[id] >= 0) id = alias[id]; return id; };
+    auto grad = [&](int id) { return BwdRef{BSP_GRAD, resolve(id)}; };
+    auto act = [&](int id) { return id == -2 ? BwdRef{BSP_X, -1} : id >= 0 ? BwdRef{BSP_ACT, id} : BwdRef{}; };
+    auto write = [&](BwdStep& s, int id) {                 // s writes the gradient of buffer id (-2: the trajectory)
+        char& w = id == -2 ? dx : written[resolve(id)];
+        s.out = id == -2 ? BwdRef{BSP_DX, -1} : grad(id);
+        s.write = w ? BW_ADD : BW_SET;
+        w = 1;
+    };
+    auto part_take = [&](int C) { const long q = m->bpart; m->bpart += round_up(C, 4); return q; };
+    auto bias = [&](BwdRef in, int rows, int C, int slot_) {
+        BwdStep s{BK_BIAS};
+        s.in = in; s.rows = rows; s.C = C; s.part = part_take(C);
+        S.push_back(s);
+        m->bsums.push_back({slot_, s.part, C});
+    };
+    auto wgrad = [&](BwdRef G, int M, BwdRef z0, int C0, BwdRef z1, int C1, int slot_, int taps, int stride, int pad,
+                     int Lg, int Lz) {
+        BwdStep s{BK_WGRAD};
+        s.in = G; s.M = M; s.z0 = z0; s.C0 = C0; s.z1 = z1; s.C1 = C1; s.slot = slot_;
+        s.taps = taps; s.stride = stride; s.pad = pad; s.Lg = Lg; s.Lz = Lz;
+        S.push_back(s);
+    };
+    auto dgrad = [&](int conv, int sub, BwdRef dH, int target, long per_sample) {
+        BwdStep s{BK_DGRAD};
+        s.conv = conv; s.sub = sub; s.in = dH; s.n = per_sample;
+        write(s, target);
+        const ConvOp& op = conv < 0 ? m->bfinal : m->bconvs[conv].op[sub];
+        if (op.kind == CONV_UP && s.write == BW_ADD) s.write = BW_STAGE;
+        S.push_back(s);
+    };
+
+    const int H = c.horizon, td = c.transition_dim;
+    const BwdRef dout{BSP_DOUT, -1};
+    bias(dout, H, td, fb);
+    wgrad(dout, td, act(P.final_act), c.dim, BwdRef{}, 0, fw, 1, 1, 0, H, H);
+    dgrad(-1, 0, dout, P.final_act, (long)H * c.dim);
+    for (int i = (int)convs.size() - 1; i >= 0; --i) {
+        const ConvOp& f = convs[i];
+        if (!written[resolve(f.dst)] && m->bwd_rc == DAD_OK) {
+            m->bwd_rc = fail(DAD_E_STATE, "backward: no gradient reached the output of %s", f.name.c_str());
+            m->bwd_err = g_err;
+        }
+        const BwdRef gout = grad(f.dst);
+        const int out_rows = f.kind == CONV_UP ? 2 * f.Lout : f.Lout;      // rows per sample of the output
+        BwdRef dH = gout;
+        if (!f.norm.empty()) {
+            auto resid = [&](int target) {
+                BwdStep s{BK_RESID};
+                s.in = gout; s.n = (long)out_rows * f.cout;
+                write(s, target);
+                S.push_back(s);
+            };
+            if (f.res == -2) {                            // identity residual of the trajectory itself (td == C)
+                resid(-2);
+            } else if (f.cat0 >= 0) {                     // identity residual over [cat0 | cat1]: each side takes its columns
+                const int ids[2] = {f.cat0, f.cat1}, cs[2] = {f.cat_c0, f.cat_c1};
+                for (int k = 0, off = 0; k < 2; off += cs[k], ++k) {
+                    BwdStep s{BK_COLS};
+                    s.in = gout; s.rows = out_rows; s.C = cs[k]; s.off = off; s.ld = f.cout;
+                    write(s, ids[k]);
+                    S.push_back(s);
+                }
+            } else if (f.res >= 0) {
+                const int q = owner[f.res];
+                if (q >= 0 && convs[q].kind == CONV_1X1 && convs[q].norm.empty()) alias[f.res] = resolve(f.dst);
+                else resid(f.res);
+            }
+            BwdStep s{BK_GN};
+            s.conv = i; s.in = gout; s.out = BwdRef{BSP_GRAD, f.pre};
+            s.part = part_take(f.cout); part_take(f.cout); part_take(f.cout);
+            // one wave per (sample, group) pair while the pair fits its registers, else one block per pair
+            const int f4 = f.cout / 8 / 4 * f.Lout;
+            s.nv = f4 <= 64 ? 1 : f4 <= 128 ? 2 : f4 <= 256 ? 4 : f4 <= 512 ? 8 : f4 <= 1024 ? 16 : 0;
+            S.push_back(s);
+            const long c4 = round_up(f.cout, 4);
+            m->bsums.push_back({gslot[i], s.part, f.cout});
+            m->bsums.push_back({gslot[i] + 1, s.part + c4, f.cout});
+            m->bsums.push_back({bslot[i], s.part + 2 * c4, f.cout});
+            dH = s.out;
+        } else {
+            bias(dH, out_rows, f.cout, bslot[i]);
+        }
+        switch (f.kind) {
+            case CONV_K5: case CONV_1X1:
+                wgrad(dH, f.cout, act(f.src0), f.cin0, act(f.src1), f.cin1, wslot[i], f.taps, 1, f.taps / 2, f.Lin, f.Lin); break;
+            case CONV_DOWN:
+                wgrad(dH, f.cout, act(f.src0), f.cin0, BwdRef{}, 0, wslot[i], 3, 2, 1, f.Lout, f.Lin); break;
+            case CONV_UP:
+                wgrad(act(f.src0), f.cin0, dH, f.cout, BwdRef{}, 0, wslot[i], 4, 2, 1, f.Lin, 2 * f.Lin); break;
+        }
+        const HostModel::BwdConv& b = m->bconvs[i];
+        for (int k = 0; k < b.n; ++k) dgrad(i, k, dH, k == 0 ? f.src0 : f.src1, (long)f.Lin * b.c_n[k]);
+    }
+    m->bdx = dx != 0;
     return DAD_OK;
 }
 // Why a model cannot be trained on this engine, or nullptr.
@@ -875,6 +1023,99 @@ inline long slab_floats_for(const HostModel& m, int batch) {
         best = std::max(best, plan_split(m, op, cfg, batch).slab_floats);
     }
     return best;
+}
+
+// ------------------------------------------------------------------ backward pass: per-batch geometry
+// conv_wgrad instantiations exist for these tap counts (dad_lib.hip, wgrad_kernel)
+constexpr int kWgradTaps[] = {1, 3, 4, 5, 7};
+struct WgradGeom { int spc, ksplit, sps, tile, tm, tn; unsigned gx, gy; size_t lds; };
+// Layers longer than a chunk stages (more than 128 rows of G or Z per sample: horizons 256 / 512) run the windowed
+// kernel over windows of kWgradWindow rows of G (and the matching rows of Z) as if they were samples.
+constexpr int kWgradWindow = 64;
+struct WgradShape { int B, Lg, Lz, wshift; };
+inline WgradShape wgrad_shape(int B, int Lg, int Lz) {
+    if (Lg <= 128 && Lz <= 128) return {B, Lg, Lz, 0};
+    const int nw = Lg / kWgradWindow;
+    return {B * nw, kWgradWindow, Lz / nw, ilog2(nw)};
+}
+// Block tile: the largest of 64 x 64 / 64 x 32 / 32 x 32 that still gives the layer 32 tiles (the smaller tiles
+// split K inside the block instead of over the grid: fewer partial slabs to write and add); the batch is then split
+// over blockIdx.z until `target` blocks exist (one block = 8 waves = two per SIMD).
+inline WgradGeom wgrad_geom(int M, int Ctot, int B, int Lg, int Lz, int taps, int pad, int target, bool ragged) {
+    WgradGeom g{};
+    g.spc = std::max(1, dad::WG_ROWS / Lg);
+    while (g.spc > 1 && g.spc * dad::wgrad_segz(Lz, taps, pad) > dad::WG_MAX_ZROWS) g.spc /= 2;
+    static const int tms[3] = {2, 2, 1}, tns[3] = {2, 1, 1};
+    long tiles = 0;
+    for (g.tile = ragged ? 2 : 0; g.tile < 3; ++g.tile) {
+        g.tm = tms[g.tile]; g.tn = tns[g.tile];
+        g.gx = (unsigned)((M + 32 * g.tm - 1) / (32 * g.tm));
+        g.gy = (unsigned)((Ctot + 32 * g.tn - 1) / (32 * g.tn));
+        tiles = (long)g.gx * g.gy;
+        const int kgroups = 8 / (g.tm * g.tn);
+        if ((tiles >= 32 && (g.spc * Lg) % (4 * kgroups) == 0) || g.tile == 2) break;
+    }
+    const int chunks = (B + g.spc - 1) / g.spc;
+    int want = (int)std::max(1L, target / tiles);
+    want = std::min(want, chunks);
+    g.sps = (chunks + want - 1) / want * g.spc;                // samples per split: whole chunks
+    g.ksplit = (B + g.sps - 1) / g.sps;
+    g.lds = dad::wgrad_lds_floats(g.spc, Lg, Lz, taps, pad, g.tm, g.tn) * sizeof(float);
+    if (ragged) g.tile = 3;
+    return g;
+}
+
+// Scratch of dad_unet_backward, in floats: gradient mirror of the training plan | per-sample partial sums
+// | wgrad split slabs | padded d x | staging of a down-sampling conv's data gradient | split-K slabs;
+// and the geometry of every weight-gradient step of m.bsteps, in order.
+struct TrainScratch {
+    long mirror = 0, part = 0, wslab = 0, dxpad = 0, tmp = 0, bslab = 0, total = 0;
+    struct Wgrad { WgradShape sh; WgradGeom g; };
+    std::vector<Wgrad> wgrads;
+};
+inline const ConvOp& bwd_op(const HostModel& m, const BwdStep& s) { return s.conv < 0 ? m.bfinal : m.bconvs[s.conv].op[s.sub]; }
+// Everything of the backward pass that depends on the batch, with every check of its launches.  `t` is filled even
+// when a check fails: dad_train_workspace_bytes reports the sizes, dad_unet_backward refuses before its first launch.
+inline int train_scratch(const HostModel& m, int B, TrainScratch& t) {
+    const int H = m.cfg.horizon, td = m.cfg.transition_dim;
+    int rc = DAD_OK;
+    t = TrainScratch();
+    t.mirror = m.tplan.floats_per_sample * (long)B;
+    for (const ConvOp& f : m.tplan.convs) t.part += (f.norm.empty() ? 1L : 3L) * B * round_up(f.cout, 4);
+    t.part += (long)B * round_up(td, 4);
+    for (const BwdStep& s : m.bsteps) {
+        if (s.kind == BK_WGRAD) {
+            const WgradShape sh = wgrad_shape(B, s.Lg, s.Lz);             // windows of long layers run as samples
+            const bool ragged = ((s.M | s.C0 | s.C1) & 3) != 0;          // rows that are not whole aligned float4s
+            const WgradGeom g = wgrad_geom(s.M, s.C0 + s.C1, sh.B, sh.Lg, sh.Lz, s.taps, s.pad, m.wgrad_blocks, ragged);
+            const long numel = (long)s.M * (s.C0 + s.C1) * s.taps;
+            const int kgroups = 8 / (g.tm * g.tn);
+            if (rc == DAD_OK && (g.lds > dad::kLdsBytes || g.spc * sh.Lg > dad::WG_MAX_GROWS ||
+                                 g.spc * dad::wgrad_segz(sh.Lz, s.taps, s.pad) > dad::WG_MAX_ZROWS ||
+                                 (g.spc * sh.Lg) % (4 * kgroups) != 0))
+                rc = fail(DAD_E_INVALID, "wgrad: a chunk of %d samples x %d rows does not fit the kernel's staging", g.spc, sh.Lz);
+            if (rc == DAD_OK && std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) == std::end(kWgradTaps))
+                rc = fail(DAD_E_INVALID, "wgrad: %d taps", s.taps);
+            if (rc == DAD_OK && g.ksplit > 1 && numel % 4 != 0)
+                rc = fail(DAD_E_INVALID, "wgrad: %ld gradient elements (not a multiple of 4)", numel);
+            if (g.ksplit > 1) t.wslab = std::max(t.wslab, (long)g.ksplit * numel);
+            t.wgrads.push_back({sh, g});
+        } else if (s.kind == BK_DGRAD) {
+            const ConvOp& op = bwd_op(m, s);
+            const int cfg = choose_tile(m, op, B);
+            if (cfg >= 0) t.bslab = std::max(t.bslab, plan_split(m, op, cfg, B).slab_floats);
+            if (op.kind == CONV_UP) t.tmp = std::max(t.tmp, (long)B * s.n);
+        }
+    }
+    t.dxpad = (long)B * H * round_up(td, 32);
+    if (m.real_horizon > 0 && m.real_horizon != H) t.dxpad += 2L * B * H * round_up(td, 4);      // zero-padded copies of x and d out
+    auto al = [](long v) { return (v + 63) / 64 * 64; };
+    t.mirror = al(t.mirror); t.part = al(t.part); t.wslab = al(t.wslab); t.dxpad = al(t.dxpad);
+    t.tmp = al(t.tmp); t.bslab = al(t.bslab);
+    t.total = t.mirror + t.part + t.wslab + t.dxpad + t.tmp + t.bslab;
+    if (rc == DAD_OK && m.bpart * B > t.part)
+        rc = fail(DAD_E_WORKSPACE, "backward: partial sums overran their region (%ld > %ld floats)", m.bpart * B, t.part);
+    return rc;
 }
 
 inline size_t workspace_bytes(const HostModel& m, int batch);

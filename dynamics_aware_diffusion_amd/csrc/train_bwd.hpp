@@ -3,7 +3,7 @@
 // The reference trains with loss.backward() through TemporalUnet (m_diffuser/utils/training.py:144-156,
 // m_diffuser/models/diffusion.py:253-290): autograd walks Conv1d / ConvTranspose1d / GroupNorm / Mish /
 // Linear.  Here the data gradients of the convs run on the forward conv-GEMM kernel with transposed,
-// tap-flipped weight images (dad_lib.hip, "backward plan"); this file holds the rest:
+// tap-flipped weight images (host_plan.hpp, "backward plan"); this file holds the rest:
 //
 //   conv_wgrad<TAPS,TM,TN>   dW[m][c][k] = sum_{b,l} dH[b,l,m] * X[b, l*stride + k - pad, c]     (MFMA GEMM, K = B*L)
 //   gn_mish_bwd        dH = d(conv + bias) of  Mish(GroupNorm(h)) (+ time embedding), per (sample, group),
@@ -38,21 +38,6 @@ struct WgradParams {
     const float* zero;                       // >= 16 bytes of zeros (what the LDS-DMA fetches for halo rows)
     int32_t wshift;                          // WIN kernels: log2(windows per sample); B, Lg, Lz then count windows
 };
-
-constexpr int WG_THREADS = 512;              // 8 waves: TM x TN wave tiles of 32 x 32 (x TAPS), the rest split K
-constexpr int WG_ROWS = 64;                  // G rows per staged chunk: spc = max(1, 64 / Lg) whole samples
-constexpr int WG_MAX_GROWS = 128, WG_MAX_ZROWS = 160;      // rows one chunk may stage (registers of chunk_load)
-
-__host__ __device__ inline int wgrad_segz(int Lz, int taps, int pad) { return Lz + pad + (taps - 1 - pad); }
-__host__ __device__ inline int wgrad_round64(int v) { return (v + 63) / 64 * 64; }
-// LDS floats: two stages of a chunk (G rows [spc * Lg][32 TM], Z rows with halo [spc * SEGZ][32 TN], each part
-// rounded up to whole 64-float4 wave-instructions of the LDS-DMA), and afterwards the K-group reduction tree, whose
-// first round parks half of the block's accumulators: 4 waves x TAPS x 16 x 64.
-__host__ __device__ inline size_t wgrad_lds_floats(int spc, int Lg, int Lz, int taps, int pad, int tm, int tn) {
-    const size_t stage = 2 * ((size_t)wgrad_round64(spc * Lg * 8 * tm) * 4 + (size_t)wgrad_round64(spc * wgrad_segz(Lz, taps, pad) * 8 * tn) * 4);
-    const size_t red = (size_t)4 * taps * 16 * 64;
-    return stage > red ? stage : red;
-}
 
 // four consecutive columns of a row, zero beyond `ncols`; vector load when the row is 16-byte aligned
 __device__ __forceinline__ float4 wg_load4(const float* row, int col, int ncols, bool vec) {
@@ -768,6 +753,34 @@ __global__ __launch_bounds__(256) void gn_mish_bwd_wave_kernel(const GnBwdParams
             t[0] = pt[0]; t[1] = pt[1]; t[2] = pt[2]; t[3] = pt[3];
         }
     }
+}
+
+// ------------------------------------------------------------------------------------ zero-padded horizon
+// dst[b][l][c] (l < Hp) = l < Hr ? src[b][l][c] : 0      (the trajectory into the zero-padded layout)
+__global__ void pad_rows_kernel(float* dst, const float* src, long B, int Hp, int Hr, int cols) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * Hp * cols) return;
+    const int c = (int)(i % cols);
+    const long r = i / cols;
+    const int l = (int)(r % Hp);
+    const long b = r / Hp;
+    dst[i] = l < Hr ? src[(b * Hr + l) * cols + c] : 0.0f;
+}
+// dst[b][l][c] (l < Hr, c < cols) = src[(b * Hp + l) * ld + c]
+__global__ void slice_rows_cols_kernel(float* dst, const float* src, long B, int Hp, int Hr, int cols, int ld) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * Hr * cols) return;
+    const int c = (int)(i % cols);
+    const long r = i / cols;
+    const int l = (int)(r % Hr);
+    const long b = r / Hr;
+    dst[i] = src[(b * Hp + l) * ld + c];
+}
+__global__ void slice_cols_kernel(float* dst, const float* src, long rows, int cols, int ld) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * cols) return;
+    const long r = i / cols;
+    dst[i] = src[r * ld + (i - r * cols)];
 }
 
 }  // namespace dad

@@ -391,6 +391,76 @@ static void check_arch(const Arch& a, int precision) {
             std::vector<float> img;
             CHECK(pack_bwd_final(&m, img) == DAD_OK && img.size() == (size_t)m.bfinal.cin_pad * m.bfinal.M, "final data-gradient image");
         }
+        // the backward plan's steps (dad_unet_backward replays them): a gradient is read only after a step wrote it,
+        // its first write overwrites and later ones add; every gradient slot is written by exactly one weight-gradient
+        // step or one column sum; the partial sums tile their region; a gradient reaches the trajectory
+        CHECK(m.bwd_rc == DAD_OK, "backward plan: %s", m.bwd_err.c_str());
+        CHECK(m.bdx, "backward plan: no gradient reaches the trajectory");
+        std::vector<char> gwritten(T.bufs.size(), 0);
+        char dxwritten = 0;
+        std::vector<int> slot_writes(m.grad_slots.size(), 0);
+        std::vector<std::pair<long, long>> parts;      // [first, end) partial-sum rows of a step, units of B floats
+        for (const BwdStep& s : m.bsteps) {
+            for (const BwdRef* r : {&s.in, &s.z0, &s.z1}) {
+                CHECK(r->sp != BSP_DX, "a step reads d x");
+                if (r->sp == BSP_GRAD) CHECK(gwritten[r->buf], "a step reads the gradient of buffer %d before it is written", r->buf);
+            }
+            if (s.kind == BK_WGRAD) {
+                ++slot_writes[s.slot];
+                CHECK(s.out.sp == BSP_NONE && m.grad_slots[s.slot].numel == (long)s.M * (s.C0 + s.C1) * s.taps,
+                      "weight gradient of %s: shape", m.grad_slots[s.slot].key.c_str());
+            } else if (s.kind == BK_BIAS) {
+                CHECK(s.out.sp == BSP_NONE, "bias step writes a tensor");
+                parts.push_back({s.part, s.part + round_up(s.C, 4)});
+            } else {
+                CHECK(s.out.sp == BSP_GRAD || s.out.sp == BSP_DX, "step kind %d writes no gradient", (int)s.kind);
+                char& w = s.out.sp == BSP_DX ? dxwritten : gwritten[s.out.buf];
+                CHECK((s.write == BW_SET) == !w, "step kind %d: first write overwrites, later ones accumulate", (int)s.kind);
+                CHECK(s.write != BW_STAGE || (s.kind == BK_DGRAD && bwd_op(m, s).kind == CONV_UP), "staged write of a non-CONV_UP step");
+                w = 1;
+                if (s.kind == BK_GN) parts.push_back({s.part, s.part + 3L * round_up(T.convs[s.conv].cout, 4)});
+            }
+        }
+        for (const BwdSum& q : m.bsums) {
+            ++slot_writes[q.slot];
+            CHECK(m.grad_slots[q.slot].numel == q.C, "column sum into %s: %d columns", m.grad_slots[q.slot].key.c_str(), q.C);
+            bool inside = false;
+            for (const auto& r : parts) inside = inside || (q.part >= r.first && q.part + q.C <= r.second);
+            CHECK(inside, "column sum into %s reads outside the partial sums of a step", m.grad_slots[q.slot].key.c_str());
+        }
+        for (size_t k = 0; k < slot_writes.size(); ++k)
+            CHECK(slot_writes[k] == 1, "gradient slot %s written %d times", m.grad_slots[k].key.c_str(), slot_writes[k]);
+        std::sort(parts.begin(), parts.end());
+        long part_end = 0;
+        for (const auto& r : parts) { CHECK(r.first == part_end, "partial sums: gap or overlap at %ld", r.first); part_end = r.second; }
+        CHECK(part_end == m.bpart, "partial sums: %ld rows, the plan counts %ld", part_end, m.bpart);
+        for (int B : {1, 3, 9, 32, 256}) {
+            TrainScratch ts;
+            rc = train_scratch(m, B, ts);
+            CHECK(rc == DAD_OK, "backward geometry B=%d: %s", B, g_err);
+            CHECK(ts.part == (part_end * B + 63) / 64 * 64, "B=%d: partial sums fill %ld of a %ld-float region", B, part_end * B, ts.part);
+            size_t nw = 0;
+            for (const BwdStep& s : m.bsteps) {
+                if (s.kind != BK_WGRAD) continue;
+                CHECK(nw < ts.wgrads.size(), "B=%d: weight-gradient geometries missing", B);
+                if (nw >= ts.wgrads.size()) break;
+                const WgradShape& sh = ts.wgrads[nw].sh;
+                const WgradGeom& g = ts.wgrads[nw++].g;
+                const char* key = m.grad_slots[s.slot].key.c_str();
+                const long numel = (long)s.M * (s.C0 + s.C1) * s.taps;
+                CHECK(g.lds <= dad::kLdsBytes && g.lds == dad::wgrad_lds_floats(g.spc, sh.Lg, sh.Lz, s.taps, s.pad, g.tm, g.tn) * sizeof(float),
+                      "%s B=%d: %zu bytes of LDS", key, B, g.lds);
+                CHECK(g.spc * sh.Lg <= dad::WG_MAX_GROWS && g.spc * dad::wgrad_segz(sh.Lz, s.taps, s.pad) <= dad::WG_MAX_ZROWS,
+                      "%s B=%d: a chunk of %d samples overruns the staging", key, B, g.spc);
+                CHECK((g.spc * sh.Lg) % (4 * (8 / (g.tm * g.tn))) == 0, "%s B=%d: chunk rows do not split over the K-groups", key, B);
+                CHECK(sh.Lg << sh.wshift == s.Lg && sh.B == B << sh.wshift, "%s B=%d: windows", key, B);
+                CHECK(g.sps % g.spc == 0 && (long)g.ksplit * g.sps >= sh.B && (long)(g.ksplit - 1) * g.sps < sh.B,
+                      "%s B=%d: batch split %d x %d", key, B, g.ksplit, g.sps);
+                CHECK((long)g.gx * 32 * g.tm >= s.M && (long)g.gy * 32 * g.tn >= s.C0 + s.C1, "%s B=%d: grid", key, B);
+                CHECK(g.ksplit == 1 || ((long)g.ksplit * numel <= ts.wslab && numel % 4 == 0), "%s B=%d: split slabs", key, B);
+            }
+            CHECK(nw == ts.wgrads.size(), "B=%d: %zu weight-gradient geometries for %zu steps", B, ts.wgrads.size(), nw);
+        }
     }
     (void)bwd_launches;
     printf("  %-14s prec=%d: %zu launches in the plan, %zu buffers, %ld floats/sample, %ld launch geometries checked\n",
