@@ -71,7 +71,7 @@ template <int C> struct ChainShape {
     static constexpr int NP = (12 + SK - 1) / SK;           // (tap, 8-channel half) pairs of a chunk one wave owns: pu = ks + SK j
 };
 
-// chain image from the standard packed image [chunk][wtaps][C][16] (csrc/host_plan.hpp pack_op); one thread per float4
+// chain image from the standard packed image [chunk][wtaps][C][16] (csrc/weight_image.hpp); one thread per float4
 __global__ void chain_repack_kernel(float* dst, const float* src, int nch, int wtaps, int C) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // float4 index of dst
     const int TM = C / 32;

@@ -79,6 +79,7 @@ struct dad_model : HostModel {
     std::vector<int> chain_src;              // plan index of each chain conv (its standard image feeds chain_repack_kernel)
     int chain_C = 0, chain_last = -1;
     std::map<std::string, float*> d_time;    // time-MLP tensors as uploaded (dad_model_refresh_weights re-derives the tables)
+    std::vector<WeightEntry> weights;        // every device copy of a parameter (dad_model_refresh_weights rebuilds them)
     float* d_h1 = nullptr;            // [T][4 time_dim] scratch of the table builder
     std::vector<void*> owned;         // every hipMalloc to free
     void* d_repack = nullptr;         // dad_model_refresh_weights: descriptor table of the last refresh (device)
@@ -124,6 +125,23 @@ int upload(dad_model* m, const std::vector<float>& host, float** dev) {
     return DAD_OK;
 }
 
+// The pointer through which the launches read the device copy of a weight-table entry.
+float*& weight_ptr(dad_model* m, const WeightEntry& e) {
+    switch (e.to) {
+        case WT_W: return m->plan.convs[e.conv].d_w;
+        case WT_BIAS: return m->plan.convs[e.conv].d_bias;
+        case WT_RBIAS: return m->plan.convs[e.conv].d_rbias;
+        case WT_GAMMA: return m->plan.convs[e.conv].d_gamma;
+        case WT_BETA: return m->plan.convs[e.conv].d_beta;
+        case WT_BWD_W: return m->bconvs[e.conv].op[e.sub].d_w;
+        case WT_BFINAL_W: return m->bfinal.d_w;
+        case WT_FINAL_W: return m->d_final_w;
+        case WT_FINAL_B: return m->d_final_b;
+        case WT_TIME: break;
+    }
+    return m->d_time[e.key];
+}
+
 void free_device(dad_model* m) {
     for (auto& kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
     m->graphs.clear();
@@ -138,6 +156,7 @@ void free_device(dad_model* m) {
     m->d_counters = nullptr;
     m->d_zero = nullptr;
     m->chain.clear(); m->chain_src.clear(); m->chain_C = 0; m->chain_last = -1;
+    m->weights.clear(); m->d_time.clear();
     for (Plan* plan : {&m->plan, &m->tplan})
         for (auto& op : plan->convs) op.d_w = op.d_bias = op.d_gamma = op.d_beta = op.d_rbias = nullptr;
     for (auto& b : m->bconvs) for (int k = 0; k < b.n; ++k) b.op[k].d_w = b.op[k].d_bias = nullptr;
@@ -922,9 +941,11 @@ int dad_model_finalize(dad_model* m, dad_stream_t stream) {
     }
     free_device(m);
     const dad_cfg& c = m->cfg;
+    if (m->training) if (const char* why = training_refusal(*m)) return fail(DAD_E_INVALID, "training: %s", why);
+    m->weights = weight_table(*m);
     {
         void* a = nullptr;
-        m->arena_cap = arena_bytes_needed(*m);
+        m->arena_cap = arena_bytes_needed(*m, m->weights);
         HIP_TRY(hipMalloc(&a, m->arena_cap));
         m->owned.push_back(a);
         m->arena = (char*)a;
@@ -932,19 +953,13 @@ int dad_model_finalize(dad_model* m, dad_stream_t stream) {
     }
 
     HIP_TRY(hipGetDevice(&m->device));
-    for (ConvOp& op : m->plan.convs) {
-        PackedOp packed;
-        int rc = pack_op(m, op, packed);
-        if (rc != DAD_OK) return rc;
-        if ((rc = upload(m, packed.w, &op.d_w)) != DAD_OK) return rc;
-        if ((rc = upload(m, packed.bias, &op.d_bias)) != DAD_OK) return rc;
-        if (op.ride && (rc = upload(m, packed.rbias, &op.d_rbias)) != DAD_OK) return rc;
-        if (!op.norm.empty()) {
-            if ((rc = upload(m, m->raw[op.norm + ".weight"].data, &op.d_gamma)) != DAD_OK) return rc;
-            if ((rc = upload(m, m->raw[op.norm + ".bias"].data, &op.d_beta)) != DAD_OK) return rc;
-        }
-    }
     int rc;
+    std::vector<float> host;
+    for (WeightEntry& e : m->weights) {
+        if ((rc = pack_entry(m, e, host)) != DAD_OK) return rc;
+        if ((rc = upload(m, host, &e.dev)) != DAD_OK) return rc;
+        weight_ptr(m, e) = e.dev;
+    }
     for (size_t i = 0; i < m->plan.convs.size(); ++i) {        // the training plan launches the same images
         const ConvOp& a = m->plan.convs[i];
         ConvOp& b = m->tplan.convs[i];
@@ -979,22 +994,12 @@ int dad_model_finalize(dad_model* m, dad_stream_t stream) {
         }
     }
     if (m->training) {
-        if (const char* why = training_refusal(*m)) return fail(DAD_E_INVALID, "training: %s", why);
         std::vector<float> zeros((size_t)std::max(m->max_bwd_m, 2 * m->max_cout) + 64, 0.0f);
         if ((rc = upload(m, zeros, &m->d_zero)) != DAD_OK) return rc;
-        std::vector<float> img;
-        for (size_t i = 0; i < m->bconvs.size(); ++i)
-            for (int k = 0; k < m->bconvs[i].n; ++k) {
-                if ((rc = pack_bwd_op(m, m->tplan.convs[i], m->bconvs[i], k, img)) != DAD_OK) return rc;
-                if ((rc = upload(m, img, &m->bconvs[i].op[k].d_w)) != DAD_OK) return rc;
-                m->bconvs[i].op[k].d_bias = m->d_zero;
-            }
-        if ((rc = pack_bwd_final(m, img)) != DAD_OK) return rc;
-        if ((rc = upload(m, img, &m->bfinal.d_w)) != DAD_OK) return rc;
+        for (HostModel::BwdConv& b : m->bconvs)
+            for (int k = 0; k < b.n; ++k) b.op[k].d_bias = m->d_zero;
         m->bfinal.d_bias = m->d_zero;
     }
-    if ((rc = upload(m, m->raw["final_conv.1.weight"].data, &m->d_final_w)) != DAD_OK) return rc;
-    if ((rc = upload(m, m->raw["final_conv.1.bias"].data, &m->d_final_b)) != DAD_OK) return rc;
 
     // ---- time-embedding tables: every t in [0, T) at once --------------------------------
     const int T = c.n_timesteps, dim = c.dim, tdm = c.time_dim;
@@ -1013,13 +1018,6 @@ int dad_model_finalize(dad_model* m, dad_stream_t stream) {
     zeros.assign((size_t)T * std::max(1, m->plan.temb_width), 0.0f);
     if ((rc = upload(m, zeros, &m->d_temb_table)) != DAD_OK) return rc;
     m->d_emb = d_emb; m->d_temb = d_temb; m->d_h1 = d_h1;
-    m->d_time.clear();
-    for (const auto& kv : m->raw)                        // every time-MLP tensor keeps a device copy
-        if (kv.first.find("time_mlp.") != std::string::npos) {
-            float* dptr = nullptr;
-            if ((rc = upload(m, kv.second.data, &dptr)) != DAD_OK) return rc;
-            m->d_time[kv.first] = dptr;
-        }
     if ((rc = build_time_tables(m, st)) != DAD_OK) return rc;
     void* rng = nullptr;
     if ((rc = arena_alloc(m, 64, &rng)) != DAD_OK) return rc;
@@ -1205,24 +1203,8 @@ int dad_model_refresh_weights(dad_model* m, int32_t n, const char* const* keys, 
     // A training loop refreshes after every optimiser step: the ~70 images and ~110 small tensors of a PointMaze
     // net were ~200 launches of ~5 us; they are collected here and go out as one repack launch (descriptor table in
     // device memory, re-uploaded only when a source address changed) and one copy launch per COPY_MAX tensors.
-    std::vector<dad::RepackParams> reps;
+    std::vector<dad::ImageDesc> reps;
     std::vector<std::tuple<float*, const float*, size_t>> copies;
-    auto repack = [&](float* dst, const ConvOp& op, int mode, const float* w, const float* ride, int CO, int CI, int K,
-                      int c_lo, int c_n) -> int {
-        dad::RepackParams p{};
-        p.dst = dst; p.w = w; p.ride = ride;
-        p.kg = op.bdir ? 16 : std::min(op.kc, 16);
-        p.wtaps = op.wtaps(); p.M = op.M;
-        p.n = (long)op.cin_pad * p.wtaps * op.M;
-        p.mode = mode; p.CO = CO; p.CI = CI; p.K = K; p.c_lo = c_lo; p.c_n = c_n;
-        reps.push_back(p);
-        return DAD_OK;
-    };
-    auto copy = [&](float* dst, const float* src, size_t floats) -> int {
-        if (floats >= (1u << 31)) return fail(DAD_E_INVALID, "refresh: a tensor of %zu floats", floats);
-        copies.emplace_back(dst, src, floats);
-        return DAD_OK;
-    };
     std::map<std::string, const float*> given;
     for (int i = 0; i < n; ++i) {
         if (!keys[i] || !tensors[i]) return fail(DAD_E_INVALID, "null key or tensor at index %d", i);
@@ -1232,58 +1214,24 @@ int dad_model_refresh_weights(dad_model* m, int32_t n, const char* const* keys, 
     auto has = [&](const std::string& k) -> const float* { auto it = given.find(k); return it == given.end() ? nullptr : it->second; };
     bool tables_dirty = false;
     int rc;
-    for (auto& kv : given)
-        if (kv.first.find("time_mlp.") != std::string::npos) {
-            const auto& shape = m->expected[kv.first];
-            size_t fl = 1;
-            for (int64_t d : shape) fl *= (size_t)d;
-            if ((rc = copy(m->d_time.at(kv.first), kv.second, fl)) != DAD_OK) return rc;
-            tables_dirty = true;
+    for (const WeightEntry& e : m->weights) {
+        const float* w = has(e.key);
+        if (e.img.n == 0) {
+            if (!w) continue;
+            if ((size_t)e.floats >= (1u << 31)) return fail(DAD_E_INVALID, "refresh: a tensor of %zu floats", (size_t)e.floats);
+            for (int r = 0; r < e.reps; ++r) copies.emplace_back(e.dev + r * e.floats, w, (size_t)e.floats);
+            tables_dirty = tables_dirty || e.to == WT_TIME;
+            continue;
         }
-    std::vector<ConvOp>& convs = m->plan.convs;
-    for (size_t i = 0; i < convs.size(); ++i) {
-        ConvOp& op = convs[i];
-        const int cin = op.cin0 + op.cin1;
-        const float* w = has(op.name + ".weight");
-        const float* rw = op.ride ? has(op.rname + ".weight") : nullptr;
-        if (w || rw) {
-            // the image holds this conv's taps and, when a 1x1 residual conv rides along, that conv's weights
-            // as an extra tap: both are needed to rebuild it
-            if (op.ride && (!w || !rw))
-                return fail(DAD_E_KEY, "'%s.weight' and '%s.weight' share one packed image: refresh them together",
-                            op.name.c_str(), op.rname.c_str());
-            rc = op.kind == CONV_UP ? repack(op.d_w, op, dad::RP_FWD_UP, w, nullptr, op.cout, cin, 4, 0, 0)
-                                    : repack(op.d_w, op, dad::RP_FWD, w, rw, op.cout, cin, op.taps, 0, 0);
-            if (rc != DAD_OK) return rc;
-            if (m->training && w) {
-                const HostModel::BwdConv& b = m->bconvs[i];
-                for (int k = 0; k < b.n; ++k) {
-                    const ConvOp& bo = b.op[k];
-                    const int mode = op.kind == CONV_DOWN ? dad::RP_BWD_DOWN : op.kind == CONV_UP ? dad::RP_BWD_UP : dad::RP_BWD_CONV;
-                    if ((rc = repack(bo.d_w, bo, mode, w, nullptr, op.cout, cin, op.taps, b.c_lo[k], b.c_n[k])) != DAD_OK) return rc;
-                }
-            }
-        }
-        if (const float* bsrc = has(op.name + ".bias")) {
-            if ((rc = copy(op.d_bias, bsrc, op.cout)) != DAD_OK) return rc;
-            if (op.kind == CONV_UP && (rc = copy(op.d_bias + op.cout, bsrc, op.cout)) != DAD_OK) return rc;
-        }
-        if (op.ride)
-            if (const float* rb = has(op.rname + ".bias"))
-                if ((rc = copy(op.d_rbias, rb, op.cout)) != DAD_OK) return rc;
-        if (!op.norm.empty()) {
-            if (const float* g = has(op.norm + ".weight")) if ((rc = copy(op.d_gamma, g, op.cout)) != DAD_OK) return rc;
-            if (const float* be = has(op.norm + ".bias")) if ((rc = copy(op.d_beta, be, op.cout)) != DAD_OK) return rc;
-        }
+        // the image of a conv with a riding 1x1 residual conv holds both weights: both are needed to rebuild it
+        const float* ride = e.key2.empty() ? nullptr : has(e.key2);
+        if (!e.key2.empty() && (!w) != (!ride))
+            return fail(DAD_E_KEY, "'%s' and '%s' share one packed image: refresh them together", e.key.c_str(), e.key2.c_str());
+        if (!w) continue;
+        dad::ImageDesc p = e.img;
+        p.dst = e.dev; p.w = w; p.ride = ride;
+        reps.push_back(p);
     }
-    if (const float* fw = has("final_conv.1.weight")) {
-        if ((rc = copy(m->d_final_w, fw, (size_t)m->cfg.transition_dim * m->cfg.dim)) != DAD_OK) return rc;
-        if (m->training &&
-            (rc = repack(m->bfinal.d_w, m->bfinal, dad::RP_BWD_FINAL, fw, nullptr, m->cfg.transition_dim, m->cfg.dim, 1, 0, 0)) != DAD_OK)
-            return rc;
-    }
-    if (const float* fb = has("final_conv.1.bias"))
-        if ((rc = copy(m->d_final_b, fb, m->cfg.transition_dim)) != DAD_OK) return rc;
     for (size_t at = 0; at < copies.size(); at += dad::COPY_MAX) {
         dad::CopyMany cm{};
         const int k = (int)std::min<size_t>(dad::COPY_MAX, copies.size() - at);
@@ -1304,7 +1252,7 @@ int dad_model_refresh_weights(dad_model* m, int32_t n, const char* const* keys, 
             if (first[i] + blocks >= (1L << 31)) return fail(DAD_E_INVALID, "refresh: too many image elements for one launch");
             first[i + 1] = first[i] + (int)blocks;
         }
-        const size_t desc_bytes = reps.size() * sizeof(dad::RepackParams), first_bytes = first.size() * sizeof(int);
+        const size_t desc_bytes = reps.size() * sizeof(dad::ImageDesc), first_bytes = first.size() * sizeof(int);
         const bool same = m->repack_host.size() == desc_bytes && std::memcmp(m->repack_host.data(), reps.data(), desc_bytes) == 0;
         if (!same) {
             if (m->repack_cap < desc_bytes + first_bytes) {       // (grows once; freed with the model's other allocations)
@@ -1319,7 +1267,7 @@ int dad_model_refresh_weights(dad_model* m, int32_t n, const char* const* keys, 
             m->repack_host.assign((const char*)reps.data(), (const char*)reps.data() + desc_bytes);
         }
         hipLaunchKernelGGL(dad::repack_many_kernel, dim3((unsigned)first.back()), dim3(256), 0, st,
-                           (const dad::RepackParams*)m->d_repack, (const int*)((const char*)m->d_repack + desc_bytes), (int)reps.size());
+                           (const dad::ImageDesc*)m->d_repack, (const int*)((const char*)m->d_repack + desc_bytes), (int)reps.size());
         HIP_TRY(hipGetLastError());
     }
     // the per-timestep tables belong to the sampler: a training loop never reads them, so they are re-derived by the

@@ -21,6 +21,7 @@
 
 #include "../../include/dad.h"
 #include "conv_shapes.hpp"
+#include "weight_image.hpp"
 
 namespace dadhost {
 
@@ -723,46 +724,6 @@ inline int build_plan(HostModel* m) {
 }
 
 // ------------------------------------------------------------------------------ packing
-// Conv1d weight (co, ci, k)  ->  [ci_pad/KC][wtaps][M = co][KC]; tap index `tap_at + t`.
-inline void pack_conv_into(std::vector<float>& out, const HostTensor& w, int wtaps, int tap_at, int kc) {
-    const int co = (int)w.shape[0], ci = (int)w.shape[1], k = (int)w.shape[2];
-    for (int o = 0; o < co; ++o)
-        for (int i = 0; i < ci; ++i)
-            for (int t = 0; t < k; ++t) {
-                const size_t row = ((size_t)(i / kc) * wtaps + tap_at + t) * co + o;
-                out[row * kc + (i % kc)] = w.data[((size_t)o * ci + i) * k + t];
-            }
-}
-inline std::vector<float> pack_conv(const HostTensor& w, int cin_pad, int taps, int kc) {
-    std::vector<float> out((size_t)cin_pad * taps * (size_t)w.shape[0], 0.0f);
-    pack_conv_into(out, w, taps, 0, kc);
-    return out;
-}
-
-// ConvTranspose1d weight (ci, co, 4), stride 2, pad 1:
-//   y[co, 2j]   = sum_ci W[ci,co,3] x[ci,j-1] + W[ci,co,1] x[ci,j]
-//   y[co, 2j+1] = sum_ci W[ci,co,2] x[ci,j]   + W[ci,co,0] x[ci,j+1]
-// packed as a 2-tap conv with M = 2*co columns: columns [0,co) are the even phase (taps at
-// positions j-1, j), columns [co,2co) the odd phase (taps at j, j+1 — the kernel shifts the row
-// base by one for tiles of that half).
-inline std::vector<float> pack_convT(const HostTensor& w, int cin_pad, int kc) {
-    const int ci = (int)w.shape[0], co = (int)w.shape[1];
-    const int M = 2 * co;
-    std::vector<float> out((size_t)cin_pad * 2 * M, 0.0f);
-    auto at = [&](int i, int o, int kk) { return w.data[((size_t)i * co + o) * 4 + kk]; };
-    for (int i = 0; i < ci; ++i)
-        for (int o = 0; o < co; ++o) {
-            auto slot = [&](int tap, int mm) -> float& {
-                return out[(((size_t)(i / kc) * 2 + tap) * M + mm) * kc + (i % kc)];
-            };
-            slot(0, o) = at(i, o, 3);
-            slot(1, o) = at(i, o, 1);
-            slot(0, co + o) = at(i, o, 2);
-            slot(1, co + o) = at(i, o, 0);
-        }
-    return out;
-}
-
 // Split-f16 image of a packed weight tensor (granules of 16 input channels):
 //   [8 words: 16 hi halves | 8 words: 16 lo halves],  w * 2^s ~= hi + lo * 2^-11,
 // s chosen per layer so the largest weight lands in [2^9, 2^10) and small ones stay normal halves.
@@ -798,95 +759,105 @@ inline int split_f16_image(std::vector<float>& packed) {
     return s;
 }
 
-// What dad_model_finalize uploads for one conv launch.
-struct PackedOp {
-    std::vector<float> w, bias, rbias;
-};
-// Decides the layer's kernel family (direct-B, split-f16) and produces its packed image.
-inline int pack_op(HostModel* m, ConvOp& op, PackedOp& out) {
-    auto need = [&](const std::string& key) -> const HostTensor* {
-        auto it = m->raw.find(key);
-        return it == m->raw.end() ? nullptr : &it->second;
-    };
-    const HostTensor* w = need(op.name + ".weight");
-    const HostTensor* b = need(op.name + ".bias");
-    if (!w || !b) return fail(DAD_E_KEY, "missing key '%s.weight/.bias'", op.name.c_str());
-    const int pack_g = op.bdir ? 16 : op.kc;            // flags: decide_kernel_families
-    if (op.kind == CONV_UP) {
-        out.w = pack_convT(*w, op.cin_pad, pack_g);
-    } else {
-        const int wt = op.wtaps();
-        out.w.assign((size_t)op.cin_pad * wt * (size_t)op.M, 0.0f);
-        pack_conv_into(out.w, *w, wt, 0, pack_g);
-        if (op.ride) {
-            const HostTensor* rw = need(op.rname + ".weight");
-            const HostTensor* rb = need(op.rname + ".bias");
-            if (!rw || !rb) return fail(DAD_E_KEY, "missing key '%s.weight/.bias'", op.rname.c_str());
-            pack_conv_into(out.w, *rw, wt, op.taps, pack_g);
-            out.rbias = rb->data;
-        }
-    }
-    op.c1 = 1.0f; op.c2 = 0.0f;
-    if (op.x3) {
-        const int sh = split_f16_image(out.w);
-        op.c1 = std::ldexp(1.0f, -sh);
-        op.c2 = std::ldexp(1.0f, -sh - 11);
-    }
-    out.bias = b->data;
-    if (op.kind == CONV_UP) out.bias.insert(out.bias.end(), b->data.begin(), b->data.end());
-    return DAD_OK;
+// Descriptors of the packed images (layouts: weight_image.hpp); dad_model_finalize and dad_model_refresh_weights
+// both take them from here.
+inline dad::ImageDesc image_desc(const ConvOp& op, int mode, int CO, int CI, int K, int c_lo = 0, int c_n = 0) {
+    dad::ImageDesc p{};
+    p.mode = mode;
+    p.kg = op.bdir ? 16 : op.kc;                        // flags: decide_kernel_families
+    p.wtaps = op.wtaps(); p.M = op.M;
+    p.n = (long)op.cin_pad * p.wtaps * op.M;
+    p.CO = CO; p.CI = CI; p.K = K; p.c_lo = c_lo; p.c_n = c_n;
+    return p;
+}
+inline dad::ImageDesc fwd_image(const ConvOp& op) {        // the riding 1x1 conv, if any, is tap slot op.taps
+    const int cin = op.cin0 + op.cin1;
+    return op.kind == CONV_UP ? image_desc(op, dad::IMG_FWD_UP, op.cout, cin, 4) : image_desc(op, dad::IMG_FWD, op.cout, cin, op.taps);
+}
+// data-gradient launch k of forward conv f (see build_backward_plan)
+inline dad::ImageDesc bwd_image(const ConvOp& f, const HostModel::BwdConv& b, int k) {
+    const int mode = f.kind == CONV_DOWN ? dad::IMG_BWD_DOWN : f.kind == CONV_UP ? dad::IMG_BWD_UP : dad::IMG_BWD_CONV;
+    return image_desc(b.op[k], mode, f.cout, f.cin0 + f.cin1, f.taps, b.c_lo[k], b.c_n[k]);
+}
+inline dad::ImageDesc bfinal_image(const HostModel& m) {
+    return image_desc(m.bfinal, dad::IMG_BWD_FINAL, m.cfg.transition_dim, m.cfg.dim, 1);
 }
 
-// Weight image of data-gradient launch `s` of forward conv `f` (see build_backward_plan).
-inline int pack_bwd_op(HostModel* m, const ConvOp& f, const HostModel::BwdConv& b, int s, std::vector<float>& out) {
-    auto it = m->raw.find(f.name + ".weight");
-    if (it == m->raw.end()) return fail(DAD_E_KEY, "missing key '%s.weight'", f.name.c_str());
-    const HostTensor& w = it->second;
-    const ConvOp& op = b.op[s];
-    const int cin = f.cin0 + f.cin1;
-    HostTensor t;
-    if (f.kind == CONV_K5 || f.kind == CONV_1X1) {
-        const int K = f.taps;
-        t.shape = {op.cout, f.cout, K};
-        t.data.assign((size_t)op.cout * f.cout * K, 0.0f);
-        for (int mm = 0; mm < b.c_n[s]; ++mm)
-            for (int co = 0; co < f.cout; ++co)
-                for (int k = 0; k < K; ++k)
-                    t.data[((size_t)mm * f.cout + co) * K + k] = w.data[((size_t)co * cin + b.c_lo[s] + mm) * K + (K - 1 - k)];
-        out.assign((size_t)op.cin_pad * K * op.M, 0.0f);
-        pack_conv_into(out, t, K, 0, 16);
-    } else if (f.kind == CONV_DOWN) {            // -> transposed conv (in = co, out = ci, 4 taps; tap 3 zero)
-        t.shape = {f.cout, cin, 4};
-        t.data.assign((size_t)f.cout * cin * 4, 0.0f);
-        for (int co = 0; co < f.cout; ++co)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int k = 0; k < 3; ++k)
-                    t.data[((size_t)co * cin + ci) * 4 + k] = w.data[((size_t)co * cin + ci) * 3 + k];
-        out = pack_convT(t, op.cin_pad, 16);
-    } else {                                     // CONV_UP -> 5-tap stride-2 conv (out = ci, in = co; tap 0 zero)
-        t.shape = {cin, f.cout, 5};
-        t.data.assign((size_t)cin * f.cout * 5, 0.0f);
-        for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < f.cout; ++co)
-                for (int kk = 0; kk < 4; ++kk)
-                    t.data[((size_t)ci * f.cout + co) * 5 + kk + 1] = w.data[((size_t)ci * f.cout + co) * 4 + kk];
-        out.assign((size_t)op.cin_pad * 5 * op.M, 0.0f);
-        pack_conv_into(out, t, 5, 0, 16);
+// The device copies of the parameters, one entry each: a packed image or a plain copy.  dad_model_finalize packs
+// and uploads them, dad_model_refresh_weights rebuilds them on the device from the same entries, and
+// arena_bytes_needed counts them.
+enum WeightTarget { WT_W, WT_BIAS, WT_RBIAS, WT_GAMMA, WT_BETA, WT_BWD_W, WT_BFINAL_W, WT_FINAL_W, WT_FINAL_B, WT_TIME };
+struct WeightEntry {
+    WeightTarget to;            // where the device pointer goes: d_w / d_bias / ... of plan.convs[conv],
+    int conv, sub;              //   bconvs[conv].op[sub].d_w, bfinal.d_w, d_final_w / d_final_b or d_time[key]
+    std::string key, key2;      // source tensors; key2: the riding 1x1 conv's weight (slot op.taps of the image)
+    dad::ImageDesc img;         // img.n > 0: an image entry (its tensor pointers are filled where it is packed)
+    long floats = 0;            // else a copy of `floats` floats, `reps` times over (2: the bias of both CONV_UP phases)
+    int reps = 1;
+    float* dev = nullptr;       // the device copy (dad_model_finalize)
+    size_t size() const { return img.n > 0 ? (size_t)img.n : (size_t)floats * reps; }
+};
+inline std::vector<WeightEntry> weight_table(const HostModel& m) {
+    std::vector<WeightEntry> t;
+    auto copy = [&](WeightTarget to, int conv, const std::string& key, long floats, int reps = 1) {
+        t.push_back({to, conv, 0, key, "", dad::ImageDesc{}, floats, reps});
+    };
+    for (const auto& kv : m.expected)        // time-MLP tensors: the per-timestep tables are derived from them
+        if (kv.first.find("time_mlp.") != std::string::npos) {
+            long n = 1;
+            for (int64_t d : kv.second) n *= (long)d;
+            copy(WT_TIME, -1, kv.first, n);
+        }
+    for (int i = 0; i < (int)m.plan.convs.size(); ++i) {
+        const ConvOp& op = m.plan.convs[i];
+        t.push_back({WT_W, i, 0, op.name + ".weight", op.ride ? op.rname + ".weight" : "", fwd_image(op)});
+        for (int k = 0; m.training && k < m.bconvs[i].n; ++k)
+            t.push_back({WT_BWD_W, i, k, op.name + ".weight", "", bwd_image(m.tplan.convs[i], m.bconvs[i], k)});
+        copy(WT_BIAS, i, op.name + ".bias", op.cout, op.kind == CONV_UP ? 2 : 1);
+        if (op.ride) copy(WT_RBIAS, i, op.rname + ".bias", op.cout);
+        if (!op.norm.empty()) { copy(WT_GAMMA, i, op.norm + ".weight", op.cout); copy(WT_BETA, i, op.norm + ".bias", op.cout); }
     }
-    return DAD_OK;
+    copy(WT_FINAL_W, -1, "final_conv.1.weight", (long)m.cfg.transition_dim * m.cfg.dim);
+    if (m.training) t.push_back({WT_BFINAL_W, -1, 0, "final_conv.1.weight", "", bfinal_image(m)});
+    copy(WT_FINAL_B, -1, "final_conv.1.bias", m.cfg.transition_dim);
+    return t;
 }
-inline int pack_bwd_final(HostModel* m, std::vector<float>& out) {
-    auto it = m->raw.find("final_conv.1.weight");
-    if (it == m->raw.end()) return fail(DAD_E_KEY, "missing key 'final_conv.1.weight'");
-    const HostTensor& w = it->second;            // (td, dim, 1)
-    const int td = m->cfg.transition_dim, dim = m->cfg.dim;
-    HostTensor t;
-    t.shape = {dim, td, 1};
-    t.data.assign((size_t)dim * td, 0.0f);
-    for (int j = 0; j < td; ++j)
-        for (int c = 0; c < dim; ++c) t.data[(size_t)c * td + j] = w.data[(size_t)j * dim + c];
-    out.assign((size_t)m->bfinal.cin_pad * m->bfinal.M, 0.0f);
-    pack_conv_into(out, t, 1, 0, 16);
+
+// The host image of a descriptor: the elements in image order, so that none pays a division.
+inline void pack_image(const dad::ImageDesc& p, float* out) {
+    const long chunks = p.n / ((long)p.wtaps * p.M * p.kg);
+    for (long c = 0; c < chunks; ++c)
+        for (int slot = 0; slot < p.wtaps; ++slot)
+            for (int o = 0; o < p.M; ++o)
+                for (int j = 0; j < p.kg; ++j) *out++ = dad::image_value(p, (int)c * p.kg + j, slot, o);
+}
+// What dad_model_finalize uploads for an entry, from the host tensors.  A split-f16 conv's forward image is
+// converted, and the conv receives its output scales.
+inline int pack_entry(HostModel* m, const WeightEntry& e, std::vector<float>& out) {
+    auto src = [&](const std::string& key) -> const float* {
+        auto it = m->raw.find(key);
+        return it == m->raw.end() ? nullptr : it->second.data.data();
+    };
+    const float* w = src(e.key);
+    const float* ride = e.key2.empty() ? nullptr : src(e.key2);
+    if (!w || (!e.key2.empty() && !ride)) return fail(DAD_E_KEY, "missing key '%s'", (w ? e.key2 : e.key).c_str());
+    out.resize(e.size());
+    if (e.img.n == 0) {
+        for (int r = 0; r < e.reps; ++r) std::copy(w, w + e.floats, out.begin() + r * e.floats);
+        return DAD_OK;
+    }
+    dad::ImageDesc p = e.img;
+    p.w = w; p.ride = ride;
+    pack_image(p, out.data());
+    if (e.to == WT_W) {
+        ConvOp& op = m->plan.convs[e.conv];
+        op.c1 = 1.0f; op.c2 = 0.0f;
+        if (op.x3) {
+            const int sh = split_f16_image(out);
+            op.c1 = std::ldexp(1.0f, -sh);
+            op.c2 = std::ldexp(1.0f, -sh - 11);
+        }
+    }
     return DAD_OK;
 }
 
@@ -1490,32 +1461,19 @@ inline size_t workspace_bytes(const HostModel& m, int batch) {
     return ((size_t)m.plan.floats_per_sample * (size_t)batch + scratch) * sizeof(float);
 }
 
-// Bytes the parameter arena must hold: packed weights, norms, tables, time-MLP weights, flags.
-inline size_t arena_bytes_needed(const HostModel& m) {
+// Bytes the parameter arena must hold: the parameter copies, the per-timestep tables, the level-0 chain images,
+// the zero row of the data-gradient launches, rng and split-K tickets.
+inline size_t arena_bytes_needed(const HostModel& m, const std::vector<WeightEntry>& weights) {
     const dad_cfg& c = m.cfg;
     size_t floats = 0, allocs = 0;
     auto add = [&](size_t n) { floats += n + 64; ++allocs; };
-    for (const ConvOp& op : m.plan.convs) {
-        add((size_t)op.cin_pad * (op.taps + (op.rname.empty() ? 0 : 1)) * op.M);
-        add(op.M);
-        if (!op.rname.empty()) add(op.M);
-        if (!op.norm.empty()) { add(op.cout); add(op.cout); }
-        if (op.temb_off >= 0) { add((size_t)op.cout * c.time_dim); add(op.cout); }
-    }
-    add((size_t)c.transition_dim * c.dim); add(c.transition_dim);
+    for (const WeightEntry& e : weights) add(e.size());
     const size_t T = c.n_timesteps;
     add(T * c.dim); add(T * 4 * c.time_dim); add(T * c.time_dim);
     add(T * std::max(1, m.plan.temb_width));
-    add((size_t)4 * c.time_dim * c.dim); add(4 * c.time_dim);
-    add((size_t)c.time_dim * 4 * c.time_dim); add(c.time_dim);
     if (c.n_levels >= 2 && c.channels[0] <= 128)               // level-0 chain images (conv_chain.hpp)
         for (int i = 0; i < 6 && i < (int)m.plan.convs.size(); ++i) add((size_t)m.plan.convs[i].cin_pad * 6 * m.plan.convs[i].M);
-    if (m.training) {
-        for (const HostModel::BwdConv& b : m.bconvs)
-            for (int s = 0; s < b.n; ++s) add((size_t)b.op[s].cin_pad * b.op[s].wtaps() * b.op[s].M);
-        add((size_t)m.bfinal.cin_pad * m.bfinal.M);
-        add((size_t)std::max(m.max_bwd_m, 2 * m.max_cout) + 64);
-    }
+    if (m.training) add((size_t)std::max(m.max_bwd_m, 2 * m.max_cout) + 64);
     return floats * sizeof(float) + allocs * 256 + kMaxSplitTiles * sizeof(unsigned) + (1 << 16);
 }
 

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "conv_gemm.hpp"
+#include "weight_image.hpp"
 
 namespace dad {
 
@@ -302,71 +303,18 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad(const WgradParams p) {
 }
 
 // ------------------------------------------------------------------ device-side weight re-packing
-// dad_model_refresh_weights: a training loop changes the parameters every step; the packed images
-// (csrc/host_plan.hpp pack_op / pack_bwd_op) are rebuilt ON THE DEVICE from the parameter tensors in the
-// reference's layouts, one thread per element of the image (padding included, so no memset):
-//   image index = (((ci / kg) * wtaps + slot) * M + o) * kg + ci % kg
-enum RepackMode {
-    RP_FWD = 0,        // Conv1d (co, ci, K) [+ riding 1x1 conv as slot K]
-    RP_FWD_UP = 1,     // ConvTranspose1d (ci, co, 4) as two 2-tap phases, M = 2 co
-    RP_BWD_CONV = 2,   // data gradient of Conv1d: (m, c, K-1-slot) <- W[c][c_lo + m][.]
-    RP_BWD_DOWN = 3,   // data gradient of Downsample1d as a transposed conv whose 4th tap is zero
-    RP_BWD_UP = 4,     // data gradient of Upsample1d as a 5-tap stride-2 conv whose first tap is zero
-    RP_BWD_FINAL = 5,  // data gradient of final_conv[1]
-};
-struct RepackParams {
-    float* dst; const float* w; const float* ride;     // ride: the 1x1 residual conv's weight, or nullptr
-    long n;                                            // elements of the image
-    int32_t mode, kg, wtaps, M;
-    int32_t CO, CI, K;                                 // the SOURCE tensor's dims as the mode reads them
-    int32_t c_lo, c_n;                                 // RP_BWD_CONV: input-channel range of the forward conv
-};
-__global__ void repack_kernel(const RepackParams p) {
-    const long d = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= p.n) return;
-    const int j = (int)(d % p.kg);
-    long r = d / p.kg;
-    const int o = (int)(r % p.M);
-    r /= p.M;
-    const int slot = (int)(r % p.wtaps);
-    const int ci = (int)(r / p.wtaps) * p.kg + j;
-    float v = 0.0f;
-    switch (p.mode) {
-        case RP_FWD:
-            if (ci < p.CI) {
-                if (slot < p.K) v = p.w[((long)o * p.CI + ci) * p.K + slot];
-                else if (p.ride != nullptr) v = p.ride[(long)o * p.CI + ci];
-            }
-            break;
-        case RP_FWD_UP: case RP_BWD_DOWN: {
-            const int co = p.M >> 1, half = o >= co, oo = o - half * co;
-            const int kk = half == 0 ? (slot == 0 ? 3 : 1) : (slot == 0 ? 2 : 0);
-            if (p.mode == RP_FWD_UP) { if (ci < p.CI) v = p.w[((long)ci * co + oo) * 4 + kk]; }
-            else if (ci < p.CO && kk < 3) v = p.w[((long)ci * p.CI + oo) * 3 + kk];       // W (co_f = ci, ci_f = oo, k)
-            break;
-        }
-        case RP_BWD_CONV:
-            if (o < p.c_n && ci < p.CO) v = p.w[((long)ci * p.CI + p.c_lo + o) * p.K + (p.K - 1 - slot)];
-            break;
-        case RP_BWD_UP:
-            if (slot >= 1 && o < p.CI && ci < p.CO) v = p.w[((long)o * p.CO + ci) * 4 + (slot - 1)];   // Wt (ci_f = o, co_f = ci, kk)
-            break;
-        case RP_BWD_FINAL:
-            if (ci < p.CO) v = p.w[(long)ci * p.CI + o];                                      // Wf (td = ci, dim = o)
-            break;
-    }
-    p.dst[d] = v;
-}
-
-// Every image of a refresh in ONE launch: descriptor table + block ranges in device memory (cached by the caller
-// while the parameter tensors keep their addresses), block b finds its descriptor by bisection over first[].
-__global__ __launch_bounds__(256) void repack_many_kernel(const RepackParams* descs, const int* first, int ndesc) {
+// dad_model_refresh_weights: a training loop changes the parameters every step; the packed images are rebuilt ON
+// THE DEVICE from the parameter tensors in the reference's layouts (weight_image.hpp), one thread per element of
+// the image (padding included, so no memset).  Every image of a refresh in ONE launch: descriptor table + block
+// ranges in device memory (cached by the caller while the parameter tensors keep their addresses), block b finds
+// its descriptor by bisection over first[].
+__global__ __launch_bounds__(256) void repack_many_kernel(const ImageDesc* descs, const int* first, int ndesc) {
     int lo = 0, hi = ndesc - 1;                  // first[lo] <= blockIdx.x < first[lo + 1]
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
     }
-    const RepackParams p = descs[lo];
+    const ImageDesc p = descs[lo];
     const long d = (long)((int)blockIdx.x - first[lo]) * 256 + threadIdx.x;
     if (d >= p.n) return;
     const int j = (int)(d % p.kg);
@@ -374,33 +322,7 @@ __global__ __launch_bounds__(256) void repack_many_kernel(const RepackParams* de
     const int o = (int)(r % p.M);
     r /= p.M;
     const int slot = (int)(r % p.wtaps);
-    const int ci = (int)(r / p.wtaps) * p.kg + j;
-    float v = 0.0f;
-    switch (p.mode) {
-        case RP_FWD:
-            if (ci < p.CI) {
-                if (slot < p.K) v = p.w[((long)o * p.CI + ci) * p.K + slot];
-                else if (p.ride != nullptr) v = p.ride[(long)o * p.CI + ci];
-            }
-            break;
-        case RP_FWD_UP: case RP_BWD_DOWN: {
-            const int co = p.M >> 1, half = o >= co, oo = o - half * co;
-            const int kk = half == 0 ? (slot == 0 ? 3 : 1) : (slot == 0 ? 2 : 0);
-            if (p.mode == RP_FWD_UP) { if (ci < p.CI) v = p.w[((long)ci * co + oo) * 4 + kk]; }
-            else if (ci < p.CO && kk < 3) v = p.w[((long)ci * p.CI + oo) * 3 + kk];
-            break;
-        }
-        case RP_BWD_CONV:
-            if (o < p.c_n && ci < p.CO) v = p.w[((long)ci * p.CI + p.c_lo + o) * p.K + (p.K - 1 - slot)];
-            break;
-        case RP_BWD_UP:
-            if (slot >= 1 && o < p.CI && ci < p.CO) v = p.w[((long)o * p.CO + ci) * 4 + (slot - 1)];
-            break;
-        case RP_BWD_FINAL:
-            if (ci < p.CO) v = p.w[(long)ci * p.CI + o];
-            break;
-    }
-    p.dst[d] = v;
+    p.dst[d] = image_value(p, (int)(r / p.wtaps) * p.kg + j, slot, o);
 }
 
 // The small tensors of a refresh (biases, GroupNorm parameters, time-MLP tensors) in one launch: blockIdx.y picks

@@ -58,6 +58,98 @@ static bool xswz_conflict_free(uint64_t packed, int L, int stride, int pad, int 
     return true;
 }
 
+// The packed layouts stated a second time, independently of weight_image.hpp: explicit loops over the source
+// tensors.  Every image of the weight table must equal them bit for bit.
+// Conv1d weight (co, ci, k)  ->  [ci_pad/KC][wtaps][M = co][KC]; tap index `tap_at + t`.
+static void ref_pack_conv_into(std::vector<float>& out, const HostTensor& w, int wtaps, int tap_at, int kc) {
+    const int co = (int)w.shape[0], ci = (int)w.shape[1], k = (int)w.shape[2];
+    for (int o = 0; o < co; ++o)
+        for (int i = 0; i < ci; ++i)
+            for (int t = 0; t < k; ++t) {
+                const size_t row = ((size_t)(i / kc) * wtaps + tap_at + t) * co + o;
+                out[row * kc + (i % kc)] = w.data[((size_t)o * ci + i) * k + t];
+            }
+}
+// ConvTranspose1d weight (ci, co, 4), stride 2, pad 1, as a 2-tap conv with M = 2*co columns:
+//   y[co, 2j]   = sum_ci W[ci,co,3] x[ci,j-1] + W[ci,co,1] x[ci,j]       columns [0, co)
+//   y[co, 2j+1] = sum_ci W[ci,co,2] x[ci,j]   + W[ci,co,0] x[ci,j+1]     columns [co, 2co)
+static std::vector<float> ref_pack_convT(const HostTensor& w, int cin_pad, int kc) {
+    const int ci = (int)w.shape[0], co = (int)w.shape[1];
+    const int M = 2 * co;
+    std::vector<float> out((size_t)cin_pad * 2 * M, 0.0f);
+    auto at = [&](int i, int o, int kk) { return w.data[((size_t)i * co + o) * 4 + kk]; };
+    for (int i = 0; i < ci; ++i)
+        for (int o = 0; o < co; ++o) {
+            auto slot = [&](int tap, int mm) -> float& {
+                return out[(((size_t)(i / kc) * 2 + tap) * M + mm) * kc + (i % kc)];
+            };
+            slot(0, o) = at(i, o, 3);
+            slot(1, o) = at(i, o, 1);
+            slot(0, co + o) = at(i, o, 2);
+            slot(1, co + o) = at(i, o, 0);
+        }
+    return out;
+}
+// forward image of a conv (fp32)
+static std::vector<float> ref_fwd_image(const HostModel& m, const ConvOp& op) {
+    const int pack_g = op.bdir ? 16 : op.kc;
+    const HostTensor& w = m.raw.at(op.name + ".weight");
+    if (op.kind == CONV_UP) return ref_pack_convT(w, op.cin_pad, pack_g);
+    std::vector<float> out((size_t)op.cin_pad * op.wtaps() * op.M, 0.0f);
+    ref_pack_conv_into(out, w, op.wtaps(), 0, pack_g);
+    if (op.ride) ref_pack_conv_into(out, m.raw.at(op.rname + ".weight"), op.wtaps(), op.taps, pack_g);
+    return out;
+}
+// image of data-gradient launch s of forward conv f: the equivalent conv's weight tensor, then packed
+static std::vector<float> ref_bwd_image(const HostModel& m, const ConvOp& f, const HostModel::BwdConv& b, int s) {
+    const HostTensor& w = m.raw.at(f.name + ".weight");
+    const ConvOp& op = b.op[s];
+    const int cin = f.cin0 + f.cin1;
+    HostTensor t;
+    std::vector<float> out;
+    if (f.kind == CONV_K5 || f.kind == CONV_1X1) {
+        const int K = f.taps;
+        t.shape = {op.cout, f.cout, K};
+        t.data.assign((size_t)op.cout * f.cout * K, 0.0f);
+        for (int mm = 0; mm < b.c_n[s]; ++mm)
+            for (int co = 0; co < f.cout; ++co)
+                for (int k = 0; k < K; ++k)
+                    t.data[((size_t)mm * f.cout + co) * K + k] = w.data[((size_t)co * cin + b.c_lo[s] + mm) * K + (K - 1 - k)];
+        out.assign((size_t)op.cin_pad * K * op.M, 0.0f);
+        ref_pack_conv_into(out, t, K, 0, 16);
+    } else if (f.kind == CONV_DOWN) {            // -> transposed conv (in = co, out = ci, 4 taps; tap 3 zero)
+        t.shape = {f.cout, cin, 4};
+        t.data.assign((size_t)f.cout * cin * 4, 0.0f);
+        for (int co = 0; co < f.cout; ++co)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int k = 0; k < 3; ++k)
+                    t.data[((size_t)co * cin + ci) * 4 + k] = w.data[((size_t)co * cin + ci) * 3 + k];
+        out = ref_pack_convT(t, op.cin_pad, 16);
+    } else {                                     // CONV_UP -> 5-tap stride-2 conv (out = ci, in = co; tap 0 zero)
+        t.shape = {cin, f.cout, 5};
+        t.data.assign((size_t)cin * f.cout * 5, 0.0f);
+        for (int ci = 0; ci < cin; ++ci)
+            for (int co = 0; co < f.cout; ++co)
+                for (int kk = 0; kk < 4; ++kk)
+                    t.data[((size_t)ci * f.cout + co) * 5 + kk + 1] = w.data[((size_t)ci * f.cout + co) * 4 + kk];
+        out.assign((size_t)op.cin_pad * 5 * op.M, 0.0f);
+        ref_pack_conv_into(out, t, 5, 0, 16);
+    }
+    return out;
+}
+static std::vector<float> ref_bfinal_image(const HostModel& m) {
+    const HostTensor& w = m.raw.at("final_conv.1.weight");            // (td, dim, 1)
+    const int td = m.cfg.transition_dim, dim = m.cfg.dim;
+    HostTensor t;
+    t.shape = {dim, td, 1};
+    t.data.assign((size_t)dim * td, 0.0f);
+    for (int j = 0; j < td; ++j)
+        for (int c = 0; c < dim; ++c) t.data[(size_t)c * td + j] = w.data[(size_t)j * dim + c];
+    std::vector<float> out((size_t)m.bfinal.cin_pad * m.bfinal.M, 0.0f);
+    ref_pack_conv_into(out, t, 1, 0, 16);
+    return out;
+}
+
 static void check_arch(const Arch& a, int precision) {
     HostModel m;
     dad_cfg& c = m.cfg;
@@ -147,25 +239,47 @@ static void check_arch(const Arch& a, int precision) {
             t.data.resize(n);
             for (float& v : t.data) v = synth(st) * 0.05f;
         }
+        // the weight table as dad_model_finalize walks it (data-gradient images where the net trains)
+        m.training = precision == DAD_PREC_FP32 && training_refusal(m) == nullptr;
+        const std::vector<WeightEntry> table = weight_table(m);
         size_t arena = 0;
-        for (ConvOp& op : m.plan.convs) {
-            PackedOp po;
-            rc = pack_op(&m, op, po);
-            CHECK(rc == DAD_OK, "%s: pack_op: %s", op.name.c_str(), g_err);
-            CHECK(po.w.size() == (size_t)op.cin_pad * op.wtaps() * op.M, "%s: packed size", op.name.c_str());
-            CHECK(po.bias.size() == (size_t)op.M, "%s: bias size", op.name.c_str());
-            CHECK(!op.ride || po.rbias.size() == (size_t)op.M, "%s: ride bias size", op.name.c_str());
-            if (op.x3) CHECK(op.c1 > 0 && op.c2 > 0 && std::isfinite(op.c1), "%s: split scales", op.name.c_str());
-            if (!op.x3) {     // the packed image is a permutation of the weights plus zero padding
-                double s_in = 0, s_out = 0;
-                for (float v : m.raw[op.name + ".weight"].data) s_in += v;
-                if (op.ride) for (float v : m.raw[op.rname + ".weight"].data) s_in += v;
-                for (float v : po.w) s_out += v;
-                CHECK(std::fabs(s_in - s_out) <= 1e-6 * (1 + std::fabs(s_in)), "%s: packed checksum", op.name.c_str());
+        std::vector<float> img, want;
+        for (const WeightEntry& e : table) {
+            rc = pack_entry(&m, e, img);
+            CHECK(rc == DAD_OK, "%s: pack_entry: %s", e.key.c_str(), g_err);
+            if (rc != DAD_OK) continue;
+            CHECK(img.size() == e.size(), "%s: %zu floats packed, the table says %zu", e.key.c_str(), img.size(), e.size());
+            arena += (img.size() * sizeof(float) + 255) / 256 * 256;
+            const std::vector<float>& src = m.raw[e.key].data;
+            if (e.img.n == 0) {          // a copy: the tensor, `reps` times
+                CHECK((size_t)e.floats == src.size(), "%s: copy of %ld floats", e.key.c_str(), e.floats);
+                for (int r = 0; r < e.reps; ++r)
+                    CHECK(std::equal(src.begin(), src.end(), img.begin() + r * src.size()), "%s: copy %d", e.key.c_str(), r);
+                if (e.to == WT_BIAS || e.to == WT_RBIAS)
+                    CHECK(img.size() == (size_t)m.plan.convs[e.conv].M, "%s: bias size", e.key.c_str());
+                continue;
             }
-            arena += (po.w.size() + po.bias.size() + po.rbias.size()) * sizeof(float) + 3 * 256;
+            const ConvOp& op = e.to == WT_W ? m.plan.convs[e.conv] : e.to == WT_BWD_W ? m.bconvs[e.conv].op[e.sub] : m.bfinal;
+            CHECK(img.size() == (size_t)op.cin_pad * op.wtaps() * op.M, "%s: packed size", op.name.c_str());
+            if (op.x3) CHECK(op.c1 > 0 && op.c2 > 0 && std::isfinite(op.c1), "%s: split scales", op.name.c_str());
+            // the explicit loops; a split-f16 image is compared after the same split of theirs
+            want = e.to == WT_W ? ref_fwd_image(m, op) : e.to == WT_BWD_W ? ref_bwd_image(m, m.tplan.convs[e.conv], m.bconvs[e.conv], e.sub)
+                                                     : ref_bfinal_image(m);
+            if (op.x3) split_f16_image(want);
+            CHECK(want.size() == img.size() && std::memcmp(want.data(), img.data(), img.size() * sizeof(float)) == 0,
+                  "%s: image differs from the explicit packing loops", op.name.c_str());
+            // the image of one source tensor is a permutation of it plus zero padding
+            const bool one_source = e.to == WT_W ? !op.x3 : e.to == WT_BWD_W && m.bconvs[e.conv].n == 1;
+            if (one_source) {
+                double s_in = 0, s_out = 0;
+                for (float v : src) s_in += v;
+                if (!e.key2.empty()) for (float v : m.raw[e.key2].data) s_in += v;
+                for (float v : img) s_out += v;
+                const double tol = e.to == WT_W ? 1e-6 : 1e-5;
+                CHECK(std::fabs(s_in - s_out) <= tol * (1 + std::fabs(s_in)), "%s: packed checksum", op.name.c_str());
+            }
         }
-        CHECK(arena <= arena_bytes_needed(m), "arena estimate %zu < %zu", arena_bytes_needed(m), arena);
+        CHECK(arena <= arena_bytes_needed(m, table), "arena estimate %zu < %zu", arena_bytes_needed(m, table), arena);
     }
 
     // launches: every batch size, every forced tile, with and without split-K / fusion
@@ -368,17 +482,6 @@ static void check_arch(const Arch& a, int precision) {
                     CHECK(rc == DAD_OK, "%s B=%d: %s", b.op[k].name.c_str(), B, g_err);
                     if (rc == DAD_OK) { ++bwd_launches; CHECK(g.lds_bytes <= dad::kLdsBytes && !g.fused, "%s: geometry", b.op[k].name.c_str()); }
                 }
-                if (a.pack) {
-                    std::vector<float> img;
-                    rc = pack_bwd_op(&m, f, b, k, img);
-                    CHECK(rc == DAD_OK && img.size() == (size_t)b.op[k].cin_pad * b.op[k].wtaps() * b.op[k].M, "%s: data-gradient image", f.name.c_str());
-                    if (b.n == 1) {        // one source: the image is a permutation of the weight tensor plus zeros
-                        double s_in = 0, s_out = 0;
-                        for (float v : m.raw[f.name + ".weight"].data) s_in += v;
-                        for (float v : img) s_out += v;
-                        CHECK(std::fabs(s_in - s_out) <= 1e-5 * (1 + std::fabs(s_in)), "%s: data-gradient image checksum", f.name.c_str());
-                    }
-                }
             }
             CHECK(covered == f.cin0 + f.cin1, "%s: data gradients cover %d of %d input channels", f.name.c_str(), covered, f.cin0 + f.cin1);
         }
@@ -386,10 +489,6 @@ static void check_arch(const Arch& a, int precision) {
             LaunchGeom g;
             rc = plan_launch(m, m.bfinal, B, g);
             CHECK(rc == DAD_OK, "final data gradient B=%d: %s", B, g_err);
-        }
-        if (a.pack) {
-            std::vector<float> img;
-            CHECK(pack_bwd_final(&m, img) == DAD_OK && img.size() == (size_t)m.bfinal.cin_pad * m.bfinal.M, "final data-gradient image");
         }
         // the backward plan's steps (dad_unet_backward replays them): a gradient is read only after a step wrote it,
         // its first write overwrites and later ones add; every gradient slot is written by exactly one weight-gradient

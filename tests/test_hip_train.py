@@ -252,3 +252,55 @@ def test_gradients_on_other_architectures_vs_oracle(arch, dev):
         worst = max(worst, e)
         assert e <= REL, f"{k}: {e:.2e} x max|g|"
     print(f"{arch}: worst parameter-gradient error {worst:.2e} x max|g|")
+
+
+@pytest.mark.parametrize("net", [
+    "tiny4",                           # channel concat, CONV_UP, the riding 1x1 residual conv
+    "tiny_d48",                        # zero-padded widths: the padded tensors are rebuilt on the device (pad_flat)
+    (5, 256, (1, 8), 8, 5),            # 2048 channels: direct-B images, K chunks of 8
+    (6, 64, (1, 2, 4), 32, 3),         # kernel_size 3
+], ids=lambda n: n if isinstance(n, str) else f"td{n[0]}_d{n[1]}_m{'x'.join(map(str, n[2]))}_H{n[3]}_k{n[4]}")
+def test_refresh_with_unchanged_weights_changes_nothing(net, dev):
+    """dad_model_finalize packs the weight images on the host, dad_model_refresh_weights rebuilds them on the
+    device: refreshing with the parameters the engine was loaded with must leave every forward output (batches
+    1 and 3: the small-batch kernels and split-K without the ride; 256: the ride), every parameter gradient and
+    d loss / d x bit for bit as they were."""
+    from dynamics_aware_diffusion_amd import GaussianDiffusion, TemporalUnet
+    from dynamics_aware_diffusion_amd.utils import synth
+    T = 20
+    if isinstance(net, str):
+        od, ad, td, dim, mults = cases.net_dims(net)
+        H, ks, state = cases.H, 5, cases.net_weights(net)
+    else:
+        td, dim, mults, H, ks = net
+        od, ad = td - 1, 1
+        state = synth.synth_unet_state(td, dim, mults, seed=23, affine_jitter=0.3, kernel_size=ks)
+    unet = TemporalUnet(td, dim=dim, dim_mults=mults, kernel_size=ks)
+    unet.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+    diff = GaussianDiffusion(unet, H, od, ad, n_timesteps=T).to(dev)
+    xs = [torch.from_numpy(synth.normal_like(24, f"refresh.x{B}", (B, H, td))).to(dev) for B in (1, 3, 256)]
+    x5 = torch.from_numpy(synth.normal_like(24, "refresh.x5", (5, H, td))).to(dev)
+    t5 = torch.tensor([3, 0, 19, 7, 11], device=dev)
+    target = torch.from_numpy(synth.normal_like(24, "refresh.n5", (5, H, td))).to(dev)
+
+    def run():
+        params = diff.model._params()
+        for p in params.values():
+            p.grad = None
+        with torch.enable_grad():              # (first: the engine is built with training on)
+            x = x5.clone().requires_grad_(True)
+            ((diff.model(x, t5) - target) ** 2).mean().backward()
+        with torch.no_grad():
+            outs = [diff.model(x, 7).clone() for x in xs]
+        torch.cuda.synchronize()
+        return outs + [x.grad.clone()] + [p.grad.clone() for p in params.values()]
+
+    before = run()
+    eng = diff.model._engine
+    assert eng.training
+    eng.refresh(diff.model._params())
+    after = run()
+    assert diff.model._engine is eng, "the engine was rebuilt"
+    names = ["out B=1", "out B=3", "out B=256", "d x"] + list(diff.model._params())
+    for name, a, b in zip(names, before, after):
+        assert torch.equal(a, b), f"{name}: max|diff| = {float((a - b).abs().max()):.3e}"

@@ -230,8 +230,9 @@ def test_debug_hooks_are_per_model():
     lib.dad_model_destroy(b)
 
 
-def test_host_logic_under_address_and_ub_sanitizers(tmp_path):
-    """the launch planner, packers, split-f16 imaging, tile / split-K choice and
+def test_host_logic_and_weight_table_under_address_and_ub_sanitizers(tmp_path):
+    """the launch planner, the weight table and its packed images (bit for bit
+    against explicit packing loops kept in the harness), split-f16 imaging, tile / split-K choice and
     LDS slot-shift search compiled host-only with -fsanitize=address,undefined and run over the
     five architectures plus the fuzz generator's space (tests/sanitize/host_check.cpp).  CPU
     build only — GPU sanitizers are not available on this pool."""
