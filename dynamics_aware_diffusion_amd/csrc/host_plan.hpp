@@ -203,11 +203,6 @@ struct HostModel {
     int cc_max_rows = 512;                                     //   up to this many batch * horizon rows
     int ccw_max_rows = 128;                                    //   the same for nets whose plan needs conv_ccw.hpp (wide layers)
     int ccw_min_blocks = 256;                                  //   blocks a wide layer keeps when its K slices are fattened
-    bool chain_enabled = false;                                // level-0 encoder chain (conv_chain.hpp) for dim <= 128: opt-in
-                                                               //   ("chain" option / DAD_CHAIN=1) — measured 73-75 us against 68 us
-                                                               //   for the five launches it replaces
-    int chain_min_batch = 64;                                  //   from this batch on (one block per sample: below, the
-                                                               //   chip is mostly idle and the batch kernels' split-K wins)
     int real_channels[DAD_MAX_LEVELS] = {0};                   // dad_model_set_group_channels: widths before padding (0: as cfg)
     int real_horizon = 0;                                      // dad_model_set_horizon: horizon before padding (0: as cfg)
     int wgrad_blocks = 256;                                    // blocks a weight-gradient launch aims for (tiles x batch splits)
@@ -1429,30 +1424,6 @@ inline CcPlan cc_plan(const HostModel& m, int batch) {
     return P;
 }
 
-// ------------------------------------------------------------------ level-0 chain (conv_chain.hpp)
-// downs.0.0 (first conv with the riding 1x1 residual conv, second conv), downs.0.1 (two convs) and the
-// down-sampling conv as ONE launch, one block per sample.  Architecture conditions (the batch threshold and
-// the per-call conditions — shared timestep, inference plan — are checked where it is launched):
-struct ChainPlan { bool ok = false; int last = -1; int C = 0; };
-inline ChainPlan chain_plan(const HostModel& m) {
-    ChainPlan P;
-    const dad_cfg& c = m.cfg;
-    const std::vector<ConvOp>& v = m.plan.convs;
-    if (m.precision != DAD_PREC_FP32 || c.kernel_size != 5 || c.horizon != 32 || c.n_levels < 2 ||
-        (m.real_horizon > 0 && m.real_horizon != c.horizon)) return P;
-    const int C = c.channels[0];
-    if ((C != 32 && C != 64 && C != 128) || c.transition_dim > 16 || c.transition_dim == C || v.size() < 6) return P;
-    // the plan order of build_plan: conv0 (+ride), its stand-alone 1x1 form, conv1, conv0', conv1', down
-    if (!(v[0].ride && v[0].kind == CONV_K5 && v[0].src0 == -2 && v[0].cin1 == 0 && v[1].rider_of == 0 &&
-          v[2].kind == CONV_K5 && v[2].res == v[1].dst && v[3].kind == CONV_K5 && v[4].kind == CONV_K5 &&
-          v[4].res == v[3].src0 && v[5].kind == CONV_DOWN && v[5].src0 == v[4].dst))
-        return P;
-    for (int i : {0, 2, 3, 4, 5})
-        if (v[i].cout != C || v[i].kc != 16 || v[i].x3 || v[i].bdir || v[i].gn_real > 0) return P;
-    P.ok = true; P.last = 5; P.C = C;
-    return P;
-}
-
 // activations, then whichever scratch the batch uses: split-K slabs or the CC partial-sum slabs
 inline size_t workspace_bytes(const HostModel& m, int batch) {
     const CcPlan cc = cc_plan(m, batch);
@@ -1461,8 +1432,8 @@ inline size_t workspace_bytes(const HostModel& m, int batch) {
     return ((size_t)m.plan.floats_per_sample * (size_t)batch + scratch) * sizeof(float);
 }
 
-// Bytes the parameter arena must hold: the parameter copies, the per-timestep tables, the level-0 chain images,
-// the zero row of the data-gradient launches, rng and split-K tickets.
+// Bytes the parameter arena must hold: the parameter copies, the per-timestep tables, the zero row of the
+// data-gradient launches, rng and split-K tickets.
 inline size_t arena_bytes_needed(const HostModel& m, const std::vector<WeightEntry>& weights) {
     const dad_cfg& c = m.cfg;
     size_t floats = 0, allocs = 0;
@@ -1471,8 +1442,6 @@ inline size_t arena_bytes_needed(const HostModel& m, const std::vector<WeightEnt
     const size_t T = c.n_timesteps;
     add(T * c.dim); add(T * 4 * c.time_dim); add(T * c.time_dim);
     add(T * std::max(1, m.plan.temb_width));
-    if (c.n_levels >= 2 && c.channels[0] <= 128)               // level-0 chain images (conv_chain.hpp)
-        for (int i = 0; i < 6 && i < (int)m.plan.convs.size(); ++i) add((size_t)m.plan.convs[i].cin_pad * 6 * m.plan.convs[i].M);
     if (m.training) add((size_t)std::max(m.max_bwd_m, 2 * m.max_cout) + 64);
     return floats * sizeof(float) + allocs * 256 + kMaxSplitTiles * sizeof(unsigned) + (1 << 16);
 }

@@ -214,6 +214,8 @@ def test_debug_hooks_are_per_model():
     assert lib.dad_debug_set_option(a, b"split_target", 64) == 0
     assert lib.dad_debug_set_option(a, b"no_such_option", 1) == -1
     assert b"no_such_option" in lib.dad_last_error()
+    assert lib.dad_debug_set_option(a, b"chain", 1) == -1                 # the level-0 chain kernel was removed
+    assert b"unknown option" in lib.dad_last_error()
     assert lib.dad_debug_set_tile(a, -1) == 0
     assert ws(a, 32) < base and ws(b, 32) == base          # split target 64 < 256: smaller slabs
     # the small-batch (consumer-combine) kernels are a per-model switch as well
