@@ -13,15 +13,18 @@ dim_mults (1,2,4), T = 100 denoise steps, batch 256 plans PER GPU (weak scaling)
 weights/conditions from the portable generator, in-kernel Philox noise.
 One "step" = one full sampling loop (T U-Net evaluations + posterior updates) over the batch.
 
-Extra objects on the JSON line:
-  roofline     — the dominant kernel (conv_gemm_f32, all tile variants): algorithmic FLOPs of
-                 its launches / their HIP-event duration, measured in a second, instrumented
-                 pass of the same loop (events between launches perturb the clean timing).
-  cpu_baseline — the CPU oracle (torch-CPU restatement of the reference path, kind "port")
-                 timed on this host's cores on a bounded sample of the same workload.
-  configs      — the other BASELINE.json configurations (the T=1000 half of the metric, the
-                 projected T=500 loop, the batch-1 planning call), one timed loop each in the same
-                 invocation, each with its own ms_per_step / roofline / cpu_baseline.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  The
+extra objects on the JSON line are measured only with --full (a plain run prints them as null):
+  roofline      — the dominant kernel (conv_gemm_f32, all tile variants): algorithmic FLOPs of
+                  its launches / their HIP-event duration, measured in a second, instrumented
+                  pass of the same loop (events between launches perturb the clean timing).
+  alt_precision — the same loop timed in the other conv arithmetic (fp32 / f16x3), one GPU only.
+  cpu_baseline  — the CPU oracle (torch-CPU restatement of the reference path, kind "port")
+                  timed on this host's cores on a bounded sample of the same workload.
+  configs       — the other BASELINE.json configurations (the T=1000 half of the metric, the
+                  projected T=500 loop, the batch-1 planning call), one timed loop each in the same
+                  invocation, each with its own ms_per_step / roofline / cpu_baseline.
+  training_step — one training step (loss + backward) of the headline architecture, one GPU only.
 
 --dump-outputs DIR writes the headline loop's plans of its last timed step (seed 1000 + warmup + steps - 1;
 weights, conditions and Philox noise all come from fixed seeds) to DIR/plans.npy, for comparing two builds.
@@ -85,17 +88,23 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="pointmaze_b256", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline pass, the other "
+                         "conv arithmetic, the CPU baselines, the other BASELINE configurations and the "
+                         "training step (the --no-* options below leave parts of it out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="with --full: host time budget of the headline's CPU baseline")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "f16x3"],
                     help="conv arithmetic: exact fp32 MFMA, or split-f16 operands (3 f16 MFMAs per "
                          "product block, fp32 accumulation; same parity gates)")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the sampling loop as one hipGraph (auto: batches <= 32, which are launch-bound)")
     ap.add_argument("--no-alt", action="store_true",
-                    help="skip the second pass with the other conv arithmetic")
+                    help="with --full: skip the second pass with the other conv arithmetic")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the other BASELINE configurations (T=1000 nets, projected loop, batch 1)")
+                    help="with --full: skip the other BASELINE configurations (T=1000 nets, projected loop, "
+                         "batch 1) and the training step")
     ap.add_argument("--inflight", type=int, default=1,
                     help="independent sampling loops kept in flight on separate HIP streams "
                          "(diagnostic: shows how much of a step is dependency bubbles; the "
@@ -433,7 +442,7 @@ def main() -> None:
             dump_outputs(args.dump_outputs, {"plans": plans})
 
         roof = None
-        if rank == 0:
+        if rank == 0 and args.full:
             roof = roofline_of(workload, policy, diff, cond, args.precision, loop_s)
 
         # ---- the other conv arithmetic, same workload, same run (one GPU only; reported beside
@@ -469,14 +478,14 @@ def main() -> None:
             }
 
         alt = None
-        if headline and rank == 0 and world == 1 and args.inflight == 1 and not args.no_alt:
+        if headline and rank == 0 and world == 1 and args.inflight == 1 and args.full and not args.no_alt:
             try:                                  # a failure here must not cost the headline line
                 alt = run_alt()
             except Exception as exc:              # noqa: BLE001
                 alt = {"error": repr(exc)}
 
         base = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 base = cpu_baseline(workload, state, args.cpu_seconds if headline else 3.0)
             except Exception as exc:              # noqa: BLE001
@@ -590,7 +599,7 @@ def main() -> None:
 
     head = run_workload(args.workload, args.steps, args.warmup, headline=True)
     configs = None
-    if not args.no_configs and args.inflight == 1:
+    if args.full and not args.no_configs and args.inflight == 1:
         configs = {}
         for name in EXTRA_CONFIGS:
             if name == args.workload:

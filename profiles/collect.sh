@@ -31,7 +31,7 @@ run_pass() {   # name, limit seconds, command...
   fi
 }
 
-bench=(python3 "$root/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-alt --no-configs)
+bench=(python3 "$root/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --no-alt --no-configs)
 target=(python3 "$root/profiles/pmc_target.py")
 run_pass trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_$stamp" -- "${bench[@]}"
 run_pass pmc_fetch 180 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch_$stamp" -- "${target[@]}"
@@ -64,6 +64,6 @@ for cfg in "pointmaze 256" "halfcheetah 128" "door 128"; do
   [ -n "$t" ] && python3 "$root/profiles/layer_table.py" "$t" "$1" "$2" > "$root/gpurun_out/${tag}_layers_$1_b$2.md" 2> "$out/layers_$1_b$2.err" || true
 done
 echo "[collect] bench"
-timeout -k 10 600 python3 "$root/bench.py" --steps 5 --warmup 2 > "$out/bench_$stamp.json" 2> "$out/bench_$stamp.err"
+timeout -k 10 600 python3 "$root/bench.py" --steps 5 --warmup 2 --full > "$out/bench_$stamp.json" 2> "$out/bench_$stamp.err"
 cp "$out/bench_$stamp.json" "$out/bench.json"
 python3 "$root/profiles/summarize.py" "$out" "$tag"

@@ -37,7 +37,7 @@ if stats:
     shutil.copy(stats, os.path.join(here, f"{tag}_kernel_stats.csv"))
 
 summary = {"tag": tag,
-           "command": "python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt --no-configs",
+           "command": "python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-alt --no-configs",
            "pmc_command": "python3 profiles/pmc_target.py  (one eager sampling loop)",
            "failed_passes": sorted(os.path.basename(p) for p in glob.glob(os.path.join(src, "*.TIMEOUT")))}
 trace = one("trace_*/**/*_kernel_trace.csv")
@@ -114,7 +114,8 @@ if x3trace:
             a[0] += 1
             a[1] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
     conv = [(n, t) for k, (n, t) in agg.items() if "conv_gemm_f32" in k]
-    x3 = {"command": "python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt --precision f16x3",
+    x3 = {"command": "python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-alt --no-configs "
+                     "--precision f16x3",
           "kernels_us": {k: {"calls": n, "total_us": t, "avg_us": t / n} for k, (n, t) in agg.items()},
           "conv_gemm_all_variants": {"calls": sum(n for n, _ in conv), "total_us": sum(t for _, t in conv),
                                      "avg_us": sum(t for _, t in conv) / max(1, sum(n for n, _ in conv))}}

@@ -772,7 +772,7 @@ def test_bench_launches_its_own_ranks(dev):
     """`python bench.py --gpus 2` with no launcher around it: the parent starts two ranks before
     touching the GPU; they share this box's one GPU (rehearsal mode) and exchange plans and the
     max-over-ranks time over gloo.  Exercises init_process_group, the gather and the MAX reduce of
-    bench.py itself."""
+    bench.py itself, and rank 0's roofline pass (--full)."""
     import json
     import os
     import subprocess
@@ -782,7 +782,7 @@ def test_bench_launches_its_own_ranks(dev):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1",
-                          "--warmup", "0", "--no-alt", "--no-cpu-baseline", "--no-configs"],
+                          "--warmup", "0", "--full", "--no-alt", "--no-cpu-baseline", "--no-configs"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -796,7 +796,8 @@ def test_bench_rehearses_config5_shape_on_four_ranks(dev):
     """BASELINE config 5's workload (Door, T = 1000, 128 plans per rank) through bench.py's own rank
     start-up, gather and max-over-ranks timing on FOUR ranks sharing this box's GPU (a GPU box admits at
     most six GPU processes: the eight-rank run is the driver's; its sharding arithmetic is covered by the
-    eight-rank gloo test of tests/test_host_logic.py and by the row-for-row test below)."""
+    eight-rank gloo test of tests/test_host_logic.py and by the row-for-row test below).  A plain run: the
+    line carries the headline alone (rank 0's roofline pass is --full's)."""
     import json
     import os
     import subprocess
@@ -814,6 +815,7 @@ def test_bench_rehearses_config5_shape_on_four_ranks(dev):
     out = json.loads(lines[0])
     assert out["n_gpus"] == 4 and out["config"]["global_batch"] == 512 and out["config"]["batch_per_gpu"] == 128
     assert out["config"]["denoise_steps"] == 1000 and out["value"] > 0
+    assert out["roofline"] is None
 
 
 def test_config5_shards_equal_one_1024_row_run(dev):
