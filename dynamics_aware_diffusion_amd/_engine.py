@@ -87,6 +87,8 @@ ABI = {
     "dad_debug_kernel_table_consistent": (C.c_int, []),
     "dad_debug_small_batch_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32)]),
+    "dad_debug_backward_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                          C.POINTER(C.c_int32)]),
     "dad_model_set_training": (C.c_int, [C.c_void_p, C.c_int32]),
     "dad_model_refresh_weights": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                             C.c_void_p]),
@@ -575,6 +577,29 @@ class HipEngine:
         n, w = C.c_int32(), C.c_int32()
         _check(self.lib, self.lib.dad_debug_small_batch_plan(self._h, int(batch), C.byref(n), C.byref(w)))
         return n.value, w.value
+
+    def backward_plan(self, batch: int) -> dict:
+        """Which kernels one training step takes at `batch` under the current debug options (host logic only: needs
+        ``training=True`` but neither weights nor a device).  Keys as DAD_BP_* of include/dad.h: ``wgrads``, ``multi``
+        (launches whose fullest block stages more than one chunk), ``max_chunks``, ``max_ksplit``, ``part``,
+        ``part_multi``, ``windowed``, ``tile`` [4], ``taps_tile`` {(taps, tile): launches}, ``fwd`` / ``dgrad``
+        {(conv tile cfg, grid split-K?): launches}, and ``launches``: one dict per weight-gradient launch."""
+        need = C.c_int32()
+        _check(self.lib, self.lib.dad_debug_backward_plan(self._h, int(batch), None, 0, C.byref(need)))
+        buf = (C.c_int32 * need.value)()
+        _check(self.lib, self.lib.dad_debug_backward_plan(self._h, int(batch), buf, need.value, C.byref(need)))
+        r = list(buf)
+        fields = ("taps", "tile", "windowed", "samples", "spc", "sps", "ksplit", "chunks", "last_chunks")
+        assert r[71] == len(fields) and (len(r) - 72) == r[0] * r[71]
+        hist = lambda at: {(cfg, bool(s)): r[at + 2 * cfg + s] for cfg in range(10) for s in (0, 1) if r[at + 2 * cfg + s]}
+        return {
+            "wgrads": r[0], "multi": r[1], "max_chunks": r[2], "max_ksplit": r[3], "part": r[4], "part_multi": r[5],
+            "windowed": r[6], "tile": r[7:11],
+            "taps_tile": {(taps, tile): r[11 + 4 * i + tile] for i, taps in enumerate((1, 3, 4, 5, 7)) for tile in range(4)
+                          if r[11 + 4 * i + tile]},
+            "fwd": hist(31), "dgrad": hist(51),
+            "launches": [dict(zip(fields, r[at:at + len(fields)])) for at in range(72, len(r), len(fields))],
+        }
 
     def mish(self, x: torch.Tensor) -> torch.Tensor:
         """The conv epilogue's Mish applied to a device tensor (test hook)."""

@@ -1549,6 +1549,18 @@ int dad_debug_small_batch_plan(dad_model* m, int32_t batch, int32_t* launches_ou
     return DAD_OK;
 }
 
+int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
+    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
+    std::vector<int32_t> r;
+    const int rc = backward_plan_report(*m, batch, r);      // (a batch the backward pass refuses is refused here too)
+    if (rc != DAD_OK) return rc;
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
+}
+
 int dad_profile_enable(dad_model* m, int32_t on) {
     if (!m) return fail(DAD_E_INVALID, "null model");
     m->profile = on != 0;

@@ -1216,6 +1216,44 @@ inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g)
     return DAD_OK;
 }
 
+// dad_debug_backward_plan: which kernels one training step takes at batch B (layout: include/dad.h, DAD_BP_*).
+// Restates what dad_unet_forward_train and dad_unet_backward launch from the same planner calls they make.
+inline int backward_plan_report(const HostModel& m, int B, std::vector<int32_t>& r) {
+    TrainScratch ts;
+    const int rc = train_scratch(m, B, ts);
+    r.assign(DAD_BP_HEADER, 0);
+    r[DAD_BP_RECORD_INTS] = DAD_BP_REC_INTS;
+    size_t nw = 0;
+    auto conv = [&](const ConvOp& op, int at) {
+        const int cfg = choose_tile(m, op, B);
+        if (cfg >= 0) ++r[at + 2 * cfg + (plan_split(m, op, cfg, B).kslices > 1 ? 1 : 0)];
+    };
+    for (const ConvOp& op : m.tplan.convs)             // run_unet: a riding 1x1 residual conv is not launched
+        if (!(op.rider_of >= 0 && fused_at(m, m.tplan.convs[op.rider_of], B))) conv(op, DAD_BP_FWD);
+    for (const BwdStep& s : m.bsteps) {
+        if (s.kind == BK_DGRAD) conv(bwd_op(m, s), DAD_BP_DGRAD);
+        if (s.kind != BK_WGRAD) continue;
+        const WgradShape& sh = ts.wgrads[nw].sh;
+        const WgradGeom& g = ts.wgrads[nw++].g;
+        const int fullest = (std::min(g.sps, sh.B) + g.spc - 1) / g.spc;
+        const int last = (sh.B - (g.ksplit - 1) * g.sps + g.spc - 1) / g.spc;
+        const bool part = sh.B % g.spc != 0;
+        const int ti = (int)(std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) - std::begin(kWgradTaps));
+        ++r[DAD_BP_WGRADS];
+        r[DAD_BP_MULTI] += fullest > 1;
+        r[DAD_BP_MAX_CHUNKS] = std::max(r[DAD_BP_MAX_CHUNKS], fullest);
+        r[DAD_BP_MAX_KSPLIT] = std::max(r[DAD_BP_MAX_KSPLIT], g.ksplit);
+        r[DAD_BP_PART] += part;
+        r[DAD_BP_PART_MULTI] += part && last > 1;
+        r[DAD_BP_WINDOWED] += sh.wshift > 0;
+        ++r[DAD_BP_TILE + g.tile];
+        if (ti < (int)std::size(kWgradTaps)) ++r[DAD_BP_TAPS_TILE + 4 * ti + g.tile];
+        const int32_t rec[DAD_BP_REC_INTS] = {s.taps, g.tile, sh.wshift > 0, sh.B, g.spc, g.sps, g.ksplit, fullest, last};
+        r.insert(r.end(), rec, rec + DAD_BP_REC_INTS);
+    }
+    return rc;
+}
+
 // ------------------------------------------------------------------ small-batch (CC) plan
 // conv_cc.hpp: convs only produce partial sums, consumers finish them.  Decided per batch on the
 // host: which launches exist, their K slices, where their partial slabs live, and for every input

@@ -316,6 +316,52 @@ int dad_debug_kernel_table_consistent(void);
  * batch runs the batch-256 kernels; wide_out = how many of them are the streamed-weight form for
  * wide layers (csrc/conv_ccw.hpp). */
 int dad_debug_small_batch_plan(dad_model* m, int32_t batch, int32_t* launches_out, int32_t* wide_out);
+/* Which kernels one training step (dad_unet_forward_train + dad_unet_backward) takes at a batch, under the current
+ * debug options (host-side query, no device work; needs dad_model_set_training(m, 1) but neither weights nor
+ * dad_model_finalize).  Writes min(capacity, *needed_out) int32 values to `out`:
+ *   [DAD_BP_WGRADS]         weight-gradient launches (conv_wgrad)
+ *   [DAD_BP_MULTI]          ... whose fullest block stages more than one chunk (the double-buffered steady state)
+ *   [DAD_BP_MAX_CHUNKS]     most chunks a block stages
+ *   [DAD_BP_MAX_KSPLIT]     deepest batch split (slabs sum_slabs_kernel adds)
+ *   [DAD_BP_PART]           launches whose last chunk is part filled (samples % chunk samples != 0; the windows of a
+ *                           long layer count as samples)
+ *   [DAD_BP_PART_MULTI]     ... in a block that stages more than one chunk
+ *   [DAD_BP_WINDOWED]       launches of the windowed kernel (layers longer than 128 positions)
+ *   [DAD_BP_TILE + tile]    launches per wgrad tile: 0 = 64x64, 1 = 64x32, 2 = 32x32, 3 = 32x32 on rows that are not
+ *                           whole aligned float4s (the trajectory's columns)
+ *   [DAD_BP_TAPS_TILE + 4 * i + tile]   the same per tap count, i indexing 1, 3, 4, 5, 7 taps
+ *   [DAD_BP_FWD + 2 * cfg + s]          conv launches of the training forward on conv tile cfg (0..9) without (s = 0)
+ *                                       and with (s = 1) grid-level split-K
+ *   [DAD_BP_DGRAD + 2 * cfg + s]        the same for the data-gradient convs
+ *   [DAD_BP_RECORD_INTS]    ints per record (DAD_BP_REC_*); one record per weight-gradient launch follows from
+ *                           DAD_BP_HEADER on, in launch order:
+ *     taps, tile, windowed (0 / 1), samples (windows of a windowed launch), samples per chunk, samples per block
+ *     (a whole number of chunks), blocks over the batch (ksplit), chunks the fullest block stages, chunks the last
+ *     block stages. */
+#define DAD_BP_WGRADS 0
+#define DAD_BP_MULTI 1
+#define DAD_BP_MAX_CHUNKS 2
+#define DAD_BP_MAX_KSPLIT 3
+#define DAD_BP_PART 4
+#define DAD_BP_PART_MULTI 5
+#define DAD_BP_WINDOWED 6
+#define DAD_BP_TILE 7
+#define DAD_BP_TAPS_TILE 11
+#define DAD_BP_FWD 31
+#define DAD_BP_DGRAD 51
+#define DAD_BP_RECORD_INTS 71
+#define DAD_BP_HEADER 72
+#define DAD_BP_REC_TAPS 0
+#define DAD_BP_REC_TILE 1
+#define DAD_BP_REC_WINDOWED 2
+#define DAD_BP_REC_SAMPLES 3
+#define DAD_BP_REC_SPC 4
+#define DAD_BP_REC_SPS 5
+#define DAD_BP_REC_KSPLIT 6
+#define DAD_BP_REC_CHUNKS 7
+#define DAD_BP_REC_LAST_CHUNKS 8
+#define DAD_BP_REC_INTS 9
+int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
 
 #ifdef __cplusplus
 }

@@ -104,7 +104,7 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 24):
         gerr = 0.0
         shrinking = any(b < a for a, b in zip(mults, mults[1:]))
         if knobs and (grads or it % 3 == 0) and prec == "fp32" and td != dim:
-            Bg = min(B, 6)
+            Bg = B                           # (the case's batch, up to 100: training batches take other kernels than 6 rows do)
             x0 = torch.from_numpy(np.clip(synth.normal_like(400 + it, "fuzz.x0", (Bg, H, td)) * 0.5, -1, 1).astype(np.float32))
             tt = torch.from_numpy(np.array([(3 * i + 1) % 20 for i in range(Bg)], dtype=np.int64))
             nz = torch.from_numpy(synth.normal_like(400 + it, "fuzz.nz", (Bg, H, td)))

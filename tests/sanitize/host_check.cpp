@@ -533,10 +533,16 @@ static void check_arch(const Arch& a, int precision) {
         long part_end = 0;
         for (const auto& r : parts) { CHECK(r.first == part_end, "partial sums: gap or overlap at %ld", r.first); part_end = r.second; }
         CHECK(part_end == m.bpart, "partial sums: %ld rows, the plan counts %ld", part_end, m.bpart);
-        for (int B : {1, 3, 9, 32, 256}) {
+        for (int B : {1, 3, 9, 32, 128, 250, 256, 512}) {
             TrainScratch ts;
             rc = train_scratch(m, B, ts);
             CHECK(rc == DAD_OK, "backward geometry B=%d: %s", B, g_err);
+            std::vector<int32_t> report;                  // dad_debug_backward_plan: what the tests prove their path with
+            CHECK(backward_plan_report(m, B, report) == rc, "B=%d: the plan report disagrees about the batch", B);
+            CHECK(report.size() == DAD_BP_HEADER + ts.wgrads.size() * DAD_BP_REC_INTS && report[DAD_BP_WGRADS] == (int)ts.wgrads.size(),
+                  "B=%d: plan report of %zu ints for %zu weight-gradient launches", B, report.size(), ts.wgrads.size());
+            if (report.size() != DAD_BP_HEADER + ts.wgrads.size() * DAD_BP_REC_INTS) continue;
+            int multi = 0, most = 0, part_multi = 0;
             CHECK(ts.part == (part_end * B + 63) / 64 * 64, "B=%d: partial sums fill %ld of a %ld-float region", B, part_end * B, ts.part);
             size_t nw = 0;
             for (const BwdStep& s : m.bsteps) {
@@ -557,8 +563,32 @@ static void check_arch(const Arch& a, int precision) {
                       "%s B=%d: batch split %d x %d", key, B, g.ksplit, g.sps);
                 CHECK((long)g.gx * 32 * g.tm >= s.M && (long)g.gy * 32 * g.tn >= s.C0 + s.C1, "%s B=%d: grid", key, B);
                 CHECK(g.ksplit == 1 || ((long)g.ksplit * numel <= ts.wslab && numel % 4 == 0), "%s B=%d: split slabs", key, B);
+                // the kernel's block ks walks samples [ks * sps, min(B, (ks + 1) * sps)) in chunks of spc: the ranges
+                // tile [0, B) and none is empty; the chunk counts are what the plan report states
+                const int32_t* rec = &report[DAD_BP_HEADER + (nw - 1) * DAD_BP_REC_INTS];
+                int at = 0, fullest = 0, last = 0;
+                for (int ks = 0; ks < g.ksplit; ++ks) {
+                    const int lo = ks * g.sps, hi = std::min(sh.B, (ks + 1) * g.sps);
+                    CHECK(lo == at && hi > lo, "%s B=%d: block %d of %d walks samples [%d, %d) after %d", key, B, ks, g.ksplit, lo, hi, at);
+                    at = hi;
+                    last = (hi - lo + g.spc - 1) / g.spc;
+                    fullest = std::max(fullest, last);
+                }
+                CHECK(at == sh.B, "%s B=%d: the blocks walk %d of %d samples", key, B, at, sh.B);
+                CHECK(rec[DAD_BP_REC_CHUNKS] == fullest && rec[DAD_BP_REC_LAST_CHUNKS] == last,
+                      "%s B=%d: blocks stage up to %d chunks (the last one %d), the report says %d / %d", key, B, fullest, last,
+                      rec[DAD_BP_REC_CHUNKS], rec[DAD_BP_REC_LAST_CHUNKS]);
+                CHECK(rec[DAD_BP_REC_TAPS] == s.taps && rec[DAD_BP_REC_TILE] == g.tile && rec[DAD_BP_REC_WINDOWED] == (sh.wshift > 0) &&
+                      rec[DAD_BP_REC_SAMPLES] == sh.B && rec[DAD_BP_REC_SPC] == g.spc && rec[DAD_BP_REC_SPS] == g.sps &&
+                      rec[DAD_BP_REC_KSPLIT] == g.ksplit, "%s B=%d: plan report record", key, B);
+                multi += fullest > 1;
+                most = std::max(most, fullest);
+                part_multi += sh.B % g.spc != 0 && last > 1;
             }
             CHECK(nw == ts.wgrads.size(), "B=%d: %zu weight-gradient geometries for %zu steps", B, ts.wgrads.size(), nw);
+            CHECK(report[DAD_BP_MULTI] == multi && report[DAD_BP_MAX_CHUNKS] == most && report[DAD_BP_PART_MULTI] == part_multi,
+                  "B=%d: plan report counts %d multi-chunk launches (most %d chunks, %d part filled), the geometries give %d (%d, %d)", B,
+                  report[DAD_BP_MULTI], report[DAD_BP_MAX_CHUNKS], report[DAD_BP_PART_MULTI], multi, most, part_multi);
         }
     }
     (void)bwd_launches;
