@@ -17,6 +17,7 @@
 #include <mutex>
 #include <set>
 #include <tuple>
+#include <utility>
 
 #include "../../include/dad.h"
 #include "host_plan.hpp"
@@ -159,160 +160,127 @@ void free_device(dad_model* m) {
 }
 
 // ---------------------------------------------------------------------- kernel registry
-// Every conv-GEMM instantiation the planner can ask for, keyed by what plan_launch decides.
+// Every conv-GEMM instantiation the planner can ask for, keyed by what plan_launch decides.  Which ones exist is
+// decided by kernel_registered (host_plan.hpp) and nowhere else: the table is filled by a compile-time walk over
+// that predicate's whole domain.
 using KernFn = void (*)(const ConvParams);
 using KernKey = std::tuple<int, int, int, bool, bool, bool, bool, bool, bool>;   // cfg, taps, stride, x3, bdir, ragged, res, padded, windowed
 using KernTable = std::map<KernKey, KernFn>;
 
-template <int CFG> struct Tile {
-    static constexpr int BM = kTiles[CFG].BM, BN = kTiles[CFG].BN, SK = kTiles[CFG].SK, KC = kTiles[CFG].KC;
-};
-
-template <int CFG, int TAPS, int STRIDE, bool X3, bool BDIR, bool RES, bool PADDED = false, bool WIN = false>
+template <int CFG, int TAPS, int STRIDE, int F>
 void reg_kernel(KernTable& t) {
-    using T = Tile<CFG>;
-    constexpr int KC = eff_kc(T::KC, T::BM, TAPS, T::SK, X3, BDIR, T::BN);
-    t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, false, RES, PADDED, WIN)] =
-        dad::conv_gemm_f32<T::BM, T::BN, T::SK, KC, TAPS, STRIDE, false, X3, BDIR, RES, PADDED, WIN>;
-    if constexpr (!BDIR && STRIDE == 1 && (TAPS & 1) == 1)             // general staging path
-        t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, true, RES, PADDED, WIN)] =
-            dad::conv_gemm_f32<T::BM, T::BN, T::SK, KC, TAPS, STRIDE, true, X3, BDIR, RES, PADDED, WIN>;
-}
-// Zero-padded nets (dad_model_set_horizon / dad_model_set_group_channels): fp32, no ride, on the tiles the heuristic
-// picks (kPaddedTiles of host_plan.hpp)
-template <int CFG>
-void reg_tile_padded(KernTable& t) {
-    reg_kernel<CFG, 5, 1, false, false, false, true>(t);
-    reg_kernel<CFG, 3, 1, false, false, false, true>(t);
-    reg_kernel<CFG, 7, 1, false, false, false, true>(t);
-    reg_kernel<CFG, 3, 2, false, false, false, true>(t);
-    if constexpr (Tile<CFG>::KC >= 16)                      // backward of Upsample1d
-        reg_kernel<CFG, 5, 2, false, false, false, true>(t);
-    reg_kernel<CFG, 2, 1, false, false, false, true>(t);
-    reg_kernel<CFG, 1, 1, false, false, false, true>(t);
-    if constexpr (Tile<CFG>::KC < 16) {
-        reg_kernel<CFG, 5, 1, false, true, false, true>(t);
-        reg_kernel<CFG, 3, 1, false, true, false, true>(t);
-        reg_kernel<CFG, 7, 1, false, true, false, true>(t);
+    if constexpr (kernel_registered_f(CFG, TAPS, STRIDE, F)) {
+        constexpr TileCfg T = kTiles[CFG];
+        constexpr bool X3 = F & 1, BDIR = F & 2, RAGGED = F & 4, RES = F & 8, PADDED = F & 16, WIN = F & 32;
+        t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, RAGGED, RES, PADDED, WIN)] =
+            dad::conv_gemm_f32<T.BM, T.BN, T.SK, tile_kc(CFG, TAPS, X3, BDIR), TAPS, STRIDE, RAGGED, X3, BDIR, RES, PADDED, WIN>;
     }
 }
-// Windowed tiles (layers longer than any tile: kWinTiles of host_plan.hpp): fp32, PADDED, every conv form of the
-// forward and backward passes
-template <int CFG>
-void reg_tile_windowed(KernTable& t) {
-    reg_kernel<CFG, 5, 1, false, false, false, true, true>(t);
-    reg_kernel<CFG, 3, 1, false, false, false, true, true>(t);
-    reg_kernel<CFG, 7, 1, false, false, false, true, true>(t);
-    reg_kernel<CFG, 3, 2, false, false, false, true, true>(t);
-    reg_kernel<CFG, 5, 2, false, false, false, true, true>(t);   // backward of Upsample1d
-    reg_kernel<CFG, 2, 1, false, false, false, true, true>(t);
-    reg_kernel<CFG, 1, 1, false, false, false, true, true>(t);
+// One fold per dimension (a single fold over all combinations would exceed the compiler's nesting limit).
+template <int CFG, int TAPS, size_t... F>
+void reg_flags(KernTable& t, std::index_sequence<F...>) {
+    (reg_kernel<CFG, TAPS, 1, (int)F>(t), ...);
+    (reg_kernel<CFG, TAPS, 2, (int)F>(t), ...);
 }
-template <int CFG>
-void reg_tile(KernTable& t) {
-    reg_kernel<CFG, 5, 1, false, false, false>(t);
-    reg_kernel<CFG, 3, 1, false, false, false>(t);      // TemporalUnet(kernel_size=3 / 7) (temporal_unet.py:139): fp32 only
-    reg_kernel<CFG, 7, 1, false, false, false>(t);
-    reg_kernel<CFG, 3, 2, false, false, false>(t);
-    if constexpr (Tile<CFG>::KC >= 16)                      // backward of Upsample1d: 5-tap stride-2 conv
-        reg_kernel<CFG, 5, 2, false, false, false>(t);
-    reg_kernel<CFG, 2, 1, false, false, false>(t);
-    reg_kernel<CFG, 1, 1, false, false, false>(t);
-    if constexpr (Tile<CFG>::KC >= 16) {
-        reg_kernel<CFG, 5, 1, false, false, true>(t);      // + the riding 1x1 residual conv
-        reg_kernel<CFG, 3, 1, false, false, true>(t);
-        reg_kernel<CFG, 7, 1, false, false, true>(t);
-        reg_kernel<CFG, 5, 1, true, false, false>(t);      // split-f16 variants (16-channel granules)
-        reg_kernel<CFG, 3, 2, true, false, false>(t);
-        reg_kernel<CFG, 2, 1, true, false, false>(t);
-        reg_kernel<CFG, 1, 1, true, false, false>(t);
-    } else {                                               // wide tile: direct-B kernels of the GroupNorm'd 5-tap convs
-        reg_kernel<CFG, 5, 1, true, true, false>(t);
-        reg_kernel<CFG, 5, 1, false, true, false>(t);
-        reg_kernel<CFG, 3, 1, true, true, false>(t);       // kernel_size 3 / 7 (an LDS weight stage of 7 taps x 256 rows
-        reg_kernel<CFG, 3, 1, false, true, false>(t);      //   would not fit twice)
-        reg_kernel<CFG, 7, 1, true, true, false>(t);
-        reg_kernel<CFG, 7, 1, false, true, false>(t);
-    }
+template <int CFG, size_t... TAPS>
+void reg_taps(KernTable& t, std::index_sequence<TAPS...>) {
+    (reg_flags<CFG, (int)TAPS + 1>(t, std::make_index_sequence<(1 << kRegFlags)>()), ...);
+}
+template <size_t... CFG>
+void reg_tiles(KernTable& t, std::index_sequence<CFG...>) {
+    (reg_taps<(int)CFG>(t, std::make_index_sequence<kRegMaxTaps>()), ...);
 }
 const KernTable& kernel_table() {
     static const KernTable table = [] {
         KernTable t;
-        reg_tile<0>(t); reg_tile<1>(t); reg_tile<2>(t); reg_tile<3>(t);
-        reg_tile<4>(t); reg_tile<5>(t); reg_tile<6>(t); reg_tile<7>(t);
-        reg_tile<8>(t); reg_tile<9>(t);
-        reg_tile_padded<0>(t); reg_tile_padded<1>(t); reg_tile_padded<2>(t); reg_tile_padded<3>(t);
-        reg_tile_padded<4>(t); reg_tile_padded<8>(t); reg_tile_padded<9>(t);
-        reg_tile_windowed<0>(t); reg_tile_windowed<1>(t); reg_tile_windowed<2>(t);
+        reg_tiles(t, std::make_index_sequence<kNumTiles>());
         return t;
     }();
     return table;
 }
 
-// Small-batch conv kernels (conv_cc.hpp) by (taps, riding 1x1 conv, an input with 9..16 partial
-// slabs, rows per tile).
-template <bool BIG, int NR>
-const void* cc_kernel_t(int taps, bool ride) {
-    if (taps == 5) return ride ? (const void*)dad::conv_cc<5, 1, true, BIG, NR> : (const void*)dad::conv_cc<5, 1, false, BIG, NR>;
-    if (ride) return nullptr;
-    if (taps == 3) return (const void*)dad::conv_cc<3, 2, false, BIG, NR>;
-    if (taps == 2) return (const void*)dad::conv_cc<2, 1, false, BIG, NR>;
+// The other kernel families that stage through dynamic LDS: one list of instantiations each, searched by the
+// family's lookup and walked by configure_kernels.
+struct FamilyKernel { int key[5]; const void* fn; };
+using FamilyList = std::vector<FamilyKernel>;
+const void* find_kernel(const FamilyList& list, int k0, int k1, int k2, int k3 = 0, int k4 = 0) {
+    for (const FamilyKernel& k : list)
+        if (k.key[0] == k0 && k.key[1] == k1 && k.key[2] == k2 && k.key[3] == k3 && k.key[4] == k4) return k.fn;
     return nullptr;
-}
-const void* cc_kernel(int taps, bool ride, bool big, int rows, bool windowed = false) {
-    if (windowed) {
-        if (taps != 5 || big || rows != 32) return nullptr;
-        return ride ? (const void*)dad::conv_cc<5, 1, true, false, 32, 6, true> : (const void*)dad::conv_cc<5, 1, false, false, 32, 6, true>;
-    }
-    if (rows == 16) return big ? cc_kernel_t<true, 16>(taps, ride) : cc_kernel_t<false, 16>(taps, ride);
-    return big ? cc_kernel_t<true, 32>(taps, ride) : cc_kernel_t<false, 32>(taps, ride);
 }
 
-// conv_ccw.hpp instantiations: (taps, this launch carries a riding 1x1 conv, an input has ride slabs,
-// rows per tile)
+// Small-batch conv kernels (conv_cc.hpp) by (taps, riding 1x1 conv, an input with 9..16 partial slabs, rows per
+// tile, windowed: layers longer than a tile).  The stride follows from the taps: 5 / 1, 3 / 2, 2 / 1.
+template <bool BIG, int NR>
+void add_cc(FamilyList& v) {
+    v.push_back({{5, 0, BIG, NR, 0}, (const void*)dad::conv_cc<5, 1, false, BIG, NR>});
+    v.push_back({{5, 1, BIG, NR, 0}, (const void*)dad::conv_cc<5, 1, true, BIG, NR>});
+    v.push_back({{3, 0, BIG, NR, 0}, (const void*)dad::conv_cc<3, 2, false, BIG, NR>});
+    v.push_back({{2, 0, BIG, NR, 0}, (const void*)dad::conv_cc<2, 1, false, BIG, NR>});
+}
+const FamilyList& cc_kernels() {
+    static const FamilyList list = [] {
+        FamilyList v;
+        add_cc<false, 16>(v); add_cc<false, 32>(v); add_cc<true, 16>(v); add_cc<true, 32>(v);
+        v.push_back({{5, 0, 0, 32, 1}, (const void*)dad::conv_cc<5, 1, false, false, 32, 6, true>});
+        v.push_back({{5, 1, 0, 32, 1}, (const void*)dad::conv_cc<5, 1, true, false, 32, 6, true>});
+        return v;
+    }();
+    return list;
+}
+const void* cc_kernel(int taps, bool ride, bool big, int rows, bool windowed) {
+    return find_kernel(cc_kernels(), taps, ride, big, rows, windowed);
+}
+
+// conv_ccw.hpp instantiations by (taps, this launch carries a riding 1x1 conv, an input has ride slabs, rows per
+// tile)
 template <bool RIDE, int NR>
-const void* ccw_kernel_t(int taps, bool res) {
-    if (taps == 5) return res ? (const void*)dad::conv_ccw<5, 1, true, RIDE, NR> : (const void*)dad::conv_ccw<5, 1, false, RIDE, NR>;
-    if (res) return nullptr;
-    if (taps == 3) return (const void*)dad::conv_ccw<3, 2, false, RIDE, NR>;
-    if (taps == 2) return (const void*)dad::conv_ccw<2, 1, false, RIDE, NR>;
-    if (taps == 1) return (const void*)dad::conv_ccw<1, 1, false, RIDE, NR>;
-    return nullptr;
+void add_ccw(FamilyList& v) {
+    v.push_back({{5, 0, RIDE, NR}, (const void*)dad::conv_ccw<5, 1, false, RIDE, NR>});
+    v.push_back({{5, 1, RIDE, NR}, (const void*)dad::conv_ccw<5, 1, true, RIDE, NR>});
+    v.push_back({{3, 0, RIDE, NR}, (const void*)dad::conv_ccw<3, 2, false, RIDE, NR>});
+    v.push_back({{2, 0, RIDE, NR}, (const void*)dad::conv_ccw<2, 1, false, RIDE, NR>});
+    v.push_back({{1, 0, RIDE, NR}, (const void*)dad::conv_ccw<1, 1, false, RIDE, NR>});
+}
+const FamilyList& ccw_kernels() {
+    static const FamilyList list = [] {
+        FamilyList v;
+        add_ccw<false, 16>(v); add_ccw<false, 32>(v); add_ccw<true, 16>(v); add_ccw<true, 32>(v);
+        return v;
+    }();
+    return list;
 }
 const void* ccw_kernel(int taps, bool res, bool ride_in, int rows) {
-    if (rows == 16) return ride_in ? ccw_kernel_t<true, 16>(taps, res) : ccw_kernel_t<false, 16>(taps, res);
-    return ride_in ? ccw_kernel_t<true, 32>(taps, res) : ccw_kernel_t<false, 32>(taps, res);
+    return find_kernel(ccw_kernels(), taps, res, ride_in, rows);
 }
+
+// conv_wgrad instantiations by (taps of kWgradTaps, block tile, windowed: layers longer than a chunk stages):
+// tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32 (eight); tile 3 = 32 x 32 with the general
+// staging path (operands that are not whole aligned float4 rows)
+template <int TAPS, bool WIN>
+void add_wgrad(FamilyList& v) {
+    v.push_back({{TAPS, 0, WIN}, (const void*)dad::conv_wgrad<TAPS, 2, 2, true, WIN>});
+    v.push_back({{TAPS, 1, WIN}, (const void*)dad::conv_wgrad<TAPS, 2, 1, true, WIN>});
+    v.push_back({{TAPS, 2, WIN}, (const void*)dad::conv_wgrad<TAPS, 1, 1, true, WIN>});
+    v.push_back({{TAPS, 3, WIN}, (const void*)dad::conv_wgrad<TAPS, 1, 1, false, WIN>});
+}
+template <size_t... I>
+void add_wgrad_taps(FamilyList& v, std::index_sequence<I...>) {
+    ((add_wgrad<kWgradTaps[I], false>(v), add_wgrad<kWgradTaps[I], true>(v)), ...);
+}
+const FamilyList& wgrad_kernels() {
+    static const FamilyList list = [] {
+        FamilyList v;
+        add_wgrad_taps(v, std::make_index_sequence<std::size(kWgradTaps)>());
+        return v;
+    }();
+    return list;
+}
+const void* wgrad_kernel(int taps, int tile, bool win) { return find_kernel(wgrad_kernels(), taps, tile, win); }
 
 // Every kernel may use up to the full 160 KiB of LDS; the dynamic-LDS limit is a per-device
 // function attribute, raised once per device (not lazily per launch, so that nothing but launches
 // happens under hipGraph capture).
-// conv_wgrad instantiations by (taps, block tile): tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32
-// (eight); tile 3 = 32 x 32 with the general staging path (operands that are not whole aligned float4 rows)
-constexpr int kWgradTiles = 4;
-// (win: the windowed form for layers longer than a chunk stages, conv_wgrad WIN)
-template <int TAPS, bool WIN>
-const void* wgrad_kernel_t(int tile) {
-    return tile == 0 ? (const void*)dad::conv_wgrad<TAPS, 2, 2, true, WIN>
-         : tile == 1 ? (const void*)dad::conv_wgrad<TAPS, 2, 1, true, WIN>
-         : tile == 2 ? (const void*)dad::conv_wgrad<TAPS, 1, 1, true, WIN>
-                     : (const void*)dad::conv_wgrad<TAPS, 1, 1, false, WIN>;
-}
-template <bool WIN>
-const void* wgrad_kernel_w(int taps, int tile) {
-    switch (taps) {
-        case 1: return wgrad_kernel_t<1, WIN>(tile);
-        case 3: return wgrad_kernel_t<3, WIN>(tile);
-        case 4: return wgrad_kernel_t<4, WIN>(tile);
-        case 5: return wgrad_kernel_t<5, WIN>(tile);
-        case 7: return wgrad_kernel_t<7, WIN>(tile);
-    }
-    return nullptr;
-}
-const void* wgrad_kernel(int taps, int tile, bool win = false) {
-    return win ? wgrad_kernel_w<true>(taps, tile) : wgrad_kernel_w<false>(taps, tile);
-}
-
 int configure_kernels() {
     static std::mutex lock;
     static std::set<int> done;
@@ -320,36 +288,13 @@ int configure_kernels() {
     HIP_TRY(hipGetDevice(&dev));
     std::lock_guard<std::mutex> hold(lock);
     if (done.count(dev)) return DAD_OK;
-    for (const auto& kv : kernel_table())
-        HIP_TRY(hipFuncSetAttribute((const void*)kv.second, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)dad::kLdsBytes));
-    HIP_TRY(hipFuncSetAttribute((const void*)dad::final_posterior_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
-    for (int taps : {5, 3, 2})
-        for (int ride = 0; ride < 2; ++ride)
-            for (int big = 0; big < 2; ++big)
-                for (int rows : {16, 32})
-                    if (const void* k = cc_kernel(taps, ride != 0, big != 0, rows))
-                        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
-    for (int ride = 0; ride < 2; ++ride)
-        HIP_TRY(hipFuncSetAttribute(cc_kernel(5, ride != 0, false, 32, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
-    for (int taps : {5, 3, 2, 1})
-        for (int res = 0; res < 2; ++res)
-            for (int ride = 0; ride < 2; ++ride)
-                for (int rows : {16, 32})
-                    if (const void* k = ccw_kernel(taps, res != 0, ride != 0, rows))
-                        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
-    HIP_TRY(hipFuncSetAttribute((const void*)dad::final_cc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)dad::kLdsBytes));
-    for (int taps : kWgradTaps)
-        for (int tile = 0; tile < kWgradTiles; ++tile)
-            for (int win = 0; win < 2; ++win)
-                HIP_TRY(hipFuncSetAttribute(wgrad_kernel(taps, tile, win != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)dad::kLdsBytes));
-    HIP_TRY(hipFuncSetAttribute((const void*)dad::project_kernel<4, 16>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
-    HIP_TRY(hipFuncSetAttribute((const void*)dad::project_kernel<1, 16>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
+    std::vector<const void*> fns = {(const void*)dad::final_posterior_kernel, (const void*)dad::final_cc_kernel,
+                                    (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>};
+    for (const auto& kv : kernel_table()) fns.push_back((const void*)kv.second);
+    for (const FamilyList* list : {&cc_kernels(), &ccw_kernels(), &wgrad_kernels()})
+        for (const FamilyKernel& k : *list) fns.push_back(k.fn);
+    for (const void* fn : fns)
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
     done.insert(dev);
     return DAD_OK;
 }
@@ -1442,17 +1387,18 @@ int dad_fill_normal(float* x, int32_t batch, int32_t row_elems, uint64_t seed, u
 #ifdef DAD_STAMPS
 int dad_debug_stamps(void* buf) { g_stamps = (unsigned long long*)buf; return DAD_OK; }
 #endif
-// 1 when the host's statement of which conv-GEMM kernels exist (kernel_registered) equals the registry
+// 1 when the generated registry covers the domain of kernel_registered (an entry wherever the predicate is true)
+// and holds nothing else
 int dad_debug_kernel_table_consistent(void) {
     const KernTable& t = kernel_table();
     size_t hits = 0;
     for (int cfg = 0; cfg < kNumTiles; ++cfg)
-        for (int taps = 1; taps <= 7; ++taps)
+        for (int taps = 1; taps <= kRegMaxTaps; ++taps)
             for (int stride = 1; stride <= 2; ++stride)
-                for (int f = 0; f < 64; ++f) {
+                for (int f = 0; f < (1 << kRegFlags); ++f) {
                     const bool x3 = f & 1, bdir = f & 2, ragged = f & 4, res = f & 8, padded = f & 16, win = f & 32;
                     const bool have = t.count(KernKey(cfg, taps, stride, x3, bdir, ragged, res, padded, win)) != 0;
-                    if (have != kernel_registered(cfg, taps, stride, x3, bdir, ragged, res, padded, win)) {
+                    if (have != kernel_registered_f(cfg, taps, stride, f)) {
                         fail(DAD_E_INVALID, "kernel table mismatch at tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d padded=%d windowed=%d (registry %d)",
                              cfg, taps, stride, (int)x3, (int)bdir, (int)ragged, (int)res, (int)padded, (int)win, (int)have);
                         return 0;

@@ -128,6 +128,8 @@ constexpr int kMaxTileBN = 128;   // the longest layer a whole-sample tile holds
 // BN consecutive positions of one sample per tile (conv_gemm.hpp, WIN), the GroupNorm tail as a second launch
 // over whole (sample, group) pairs (conv_gn_pass.hpp).  Tiles with windowed instantiations:
 constexpr bool kWinTiles[kNumTiles] = {true, true, true, false, false, false, false, false, false, false};
+// Tiles with PADDED instantiations (zero-padded nets: the tiles choose_tile's heuristic picks):
+constexpr bool kPaddedTiles[kNumTiles] = {true, true, true, true, true, false, false, false, true, true};
 constexpr int kGnPassMaxPair = 256 * 4 * 32;   // elements of a (sample, group) pair the GroupNorm pass holds
 inline bool windowed_layer(const ConvOp& op) { return op.Lout > kMaxTileBN; }
 // N tiles of a launch: whole samples per tile, or Lout / BN windows per sample
@@ -146,6 +148,11 @@ constexpr int eff_kc(int cfg_kc, int bm, int taps, int sk = 1, bool x3 = false, 
            : (taps == 1 && cfg_kc >= 16) ? (bn >= 128 ? 32 : bm >= 128 ? 64 : 128)
            : (x3 && cfg_kc < 16 * sk)  ? 16 * sk
                                        : cfg_kc;
+}
+// K chunk of tile `cfg` for a conv form: what the kernel is compiled with, and what the planner sizes LDS and the
+// weight image with.
+constexpr int tile_kc(int cfg, int taps, bool x3, bool bdir) {
+    return eff_kc(kTiles[cfg].KC, kTiles[cfg].BM, taps, kTiles[cfg].SK, x3, bdir, kTiles[cfg].BN);
 }
 
 // ---- the backward pass as a list of steps (build_backward_plan), replayed by dad_unet_backward
@@ -861,7 +868,6 @@ inline int pack_entry(HostModel* m, const WeightEntry& e, std::vector<float>& ou
 // (BN % L == 0), BM divides the columns (each phase half for the transposed conv), the K chunk
 // matches the packed weights.  Preference: enough blocks to cover the 256 CUs; when tiles are
 // scarce, trade tile size for split-K depth.
-constexpr bool kPaddedTiles[kNumTiles] = {true, true, true, true, true, false, false, false, true, true};
 inline bool tile_valid(const ConvOp& op, int cfg) {
     const TileCfg& t = kTiles[cfg];
     if (windowed_layer(op)) {
@@ -870,7 +876,7 @@ inline bool tile_valid(const ConvOp& op, int cfg) {
         if (!kWinTiles[cfg] || op.x3 || op.bdir || op.kc != 16 || op.Lout % t.BN != 0) return false;
         if ((op.kind == CONV_UP ? op.M / 2 : op.M) % t.BM != 0) return false;
         if (!op.norm.empty() && (long)(op.cout / 8) * op.Lout > kGnPassMaxPair) return false;
-        const int kc = eff_kc(t.KC, t.BM, op.taps, t.SK, false, false, t.BN);
+        const int kc = tile_kc(cfg, op.taps, false, false);
         return dad::conv_lds_floats(t.BM, t.BN, kc, op.taps, op.Lin, op.Lout, t.SK, false, op.taps) * sizeof(float) <=
                dad::kLdsBytes;
     }
@@ -885,7 +891,7 @@ inline bool tile_valid(const ConvOp& op, int cfg) {
     const int f4pl = t.BM * t.BN / 4 / nthreads;
     if (!op.norm.empty() && op.Lout * cpg / 4 < f4pl) return false;   // >= 1 lane per (group, sample)
     // the stage must fit LDS (the 128-position tiles with the 128-channel chunk of a 1x1 conv do not)
-    const int kc = eff_kc(t.KC, t.BM, op.taps, t.SK, op.x3, op.bdir, t.BN);
+    const int kc = tile_kc(cfg, op.taps, op.x3, op.bdir);
     if (dad::conv_lds_floats(t.BM, t.BN, kc, op.taps, op.Lin, op.Lout, t.SK, op.bdir, op.taps) * sizeof(float) > dad::kLdsBytes)
         return false;
     return true;
@@ -963,7 +969,7 @@ struct SplitPlan { int kslices, chunks_per_slice; long slab_floats; };
 inline SplitPlan plan_split(const HostModel& m, const ConvOp& op, int cfg, int batch) {
     const TileCfg& t = kTiles[cfg];
     const long tiles = tiles_n(op, t.BN, batch) * (op.M / t.BM);
-    const int kc = eff_kc(t.KC, t.BM, op.taps, t.SK, op.x3, op.bdir, t.BN);
+    const int kc = tile_kc(cfg, op.taps, op.x3, op.bdir);
     const int nchunks = (op.cin0 + op.cin1 + kc - 1) / kc;      // chunks holding real channels
     SplitPlan sp{1, nchunks, 0};
     if (!m.split_enabled) return sp;
@@ -992,7 +998,7 @@ inline long slab_floats_for(const HostModel& m, int batch) {
 }
 
 // ------------------------------------------------------------------ backward pass: per-batch geometry
-// conv_wgrad instantiations exist for these tap counts (dad_lib.hip, wgrad_kernel)
+// conv_wgrad instantiations exist for these tap counts (the list of dad_lib.hip, wgrad_kernels, is built from them)
 constexpr int kWgradTaps[] = {1, 3, 4, 5, 7};
 struct WgradGeom { int spc, ksplit, sps, tile, tm, tn; unsigned gx, gy; size_t lds; };
 // Layers longer than a chunk stages (more than 128 rows of G or Z per sample: horizons 256 / 512) run the windowed
@@ -1113,16 +1119,20 @@ inline bool fused_at(const HostModel& m, const ConvOp& op, int batch) {
     if (cfg < 0) return false;
     const TileCfg& t = kTiles[cfg];
     if (t.KC < 16 || plan_split(m, op, cfg, batch).kslices != 1) return false;
-    const int kc = eff_kc(t.KC, t.BM, op.taps, t.SK, op.x3, op.bdir, t.BN);
+    const int kc = tile_kc(cfg, op.taps, op.x3, op.bdir);
     return dad::conv_lds_floats(t.BM, t.BN, kc, op.taps, op.Lin, op.Lout, t.SK, false, op.taps + 1) *
                sizeof(float) <= dad::kLdsBytes;
 }
 
-// Which conv-GEMM instantiations exist (the registry of dad_lib.hip, reg_tile, restated on the host so that the
-// planner — and the sanitizer harness, which has no device code — refuses a launch no kernel was compiled for;
-// dad_debug_kernel_table_consistent() compares the two).
-inline bool kernel_registered(int cfg, int taps, int stride, bool x3, bool bdir, bool ragged, bool res, bool padded = false,
-                              bool windowed = false) {
+// Which conv-GEMM instantiations exist.  This is the one statement of it: the registry of dad_lib.hip
+// (kernel_table) is generated by walking this predicate's domain at compile time and instantiates a kernel where it
+// is true and nowhere else, and the planner — and the sanitizer harness, which has no device code — refuses a launch
+// it is false for.  dad_debug_kernel_table_consistent() checks that the generated table covers the domain and
+// holds nothing else.  The domain: tile 0..kNumTiles-1, taps 1..kRegMaxTaps, stride 1..2, kRegFlags flags.
+constexpr int kRegMaxTaps = 7;
+constexpr int kRegFlags = 6;      // x3, bdir, ragged, res, padded, windowed: bits 0..5 of a flag word
+constexpr bool kernel_registered(int cfg, int taps, int stride, bool x3, bool bdir, bool ragged, bool res, bool padded = false,
+                                 bool windowed = false) {
     if (cfg < 0 || cfg >= kNumTiles) return false;
     if (windowed) {
         if (!kWinTiles[cfg] || !padded || x3 || bdir || res) return false;
@@ -1141,6 +1151,20 @@ inline bool kernel_registered(int cfg, int taps, int stride, bool x3, bool bdir,
     if (stride == 2) return taps == 3 || (taps == 5 && kc16);
     return stride == 1 && (taps == 1 || taps == 2 || k357);
 }
+// the same with the six flags as one word (how the registry and its check walk the domain)
+constexpr bool kernel_registered_f(int cfg, int taps, int stride, int f) {
+    return kernel_registered(cfg, taps, stride, f & 1, f & 2, f & 4, f & 8, f & 16, f & 32);
+}
+constexpr int count_registered() {
+    int n = 0;
+    for (int cfg = 0; cfg < kNumTiles; ++cfg)
+        for (int taps = 1; taps <= kRegMaxTaps; ++taps)
+            for (int stride = 1; stride <= 2; ++stride)
+                for (int f = 0; f < (1 << kRegFlags); ++f) n += kernel_registered_f(cfg, taps, stride, f);
+    return n;
+}
+// 223 plain + 79 PADDED + 33 windowed (125 of them RAGGED).  Adding or dropping a kernel form changes this line.
+static_assert(count_registered() == 335, "the set of conv-GEMM kernels changed: kernel_registered");
 
 inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g) {
     if ((long)batch * op.Lout * op.M >= (1L << 31) ||
@@ -1151,7 +1175,7 @@ inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g)
         return fail(DAD_E_INVALID, "no tile configuration for %s (M=%d, C/8=%d, L=%d)",
                     op.name.c_str(), op.M, op.cout / 8, op.Lout);
     const TileCfg& t = kTiles[g.cfg];
-    g.kc = eff_kc(t.KC, t.BM, op.taps, t.SK, op.x3, op.bdir, t.BN);
+    g.kc = tile_kc(g.cfg, op.taps, op.x3, op.bdir);
     const int cin = op.cin0 + op.cin1;
     g.ragged = (op.cin0 & 3) != 0 || (op.cin1 & 3) != 0 || op.cin0 % g.kc != 0 || cin % g.kc != 0;
     if (g.ragged && !(op.stride == 1 && (op.taps & 1) == 1))

@@ -168,9 +168,10 @@ def test_horizon_padding_entry_point():
 
 
 def test_planner_and_kernel_registry_agree():
-    """The planner refuses launches no kernel was compiled for from its own statement of the registry
-    (csrc/host_plan.hpp kernel_registered — what the sanitizer harness checks launch plans against); the two
-    must be the same set (round 3: a 3-tap conv under the split-f16 arithmetic was planned onto a kernel that
+    """The planner refuses launches no kernel was compiled for by one predicate (csrc/host_plan.hpp
+    kernel_registered — what the sanitizer harness checks launch plans against), and the library's kernel
+    registry is generated from that predicate: the table must hold an entry wherever it is true over its whole
+    domain and nothing else (round 3: a 3-tap conv under the split-f16 arithmetic was planned onto a kernel that
     does not exist)."""
     from dynamics_aware_diffusion_amd import _engine
     lib = _engine.load_library()
