@@ -77,8 +77,7 @@ __device__ unsigned long long* g_cc_gn_stamps = nullptr;     // set per launch b
 #else
 #define CC_GN_STAMP(i) do {} while (0)
 #endif
-constexpr int CC_MAX_SLABS = 8;
-constexpr int CC_THREADS = 512;
+// (CC_MAX_SLABS, CC_THREADS, cc_lds_floats, final_cc_lds_floats: conv_shapes.hpp)
 
 // Kernel arguments are fetched from the kernarg segment by scalar loads that hipcc places in the
 // basic block of their FIRST USE, each batch followed by its own s_waitcnt: a kernel that first
@@ -393,15 +392,6 @@ __device__ __forceinline__ void cc_build_input(const CcSrc& s, float* dst, int l
     __syncthreads();
 }
 
-// LDS floats of one conv_cc block: [X rows][slice + 4] + [weight taps][32][slice + 4], or the
-// exchange tile [8 waves][32][36] (+ the ride's) after the K loop.
-__host__ __device__ inline size_t cc_lds_floats(int slice_ch, int taps, int wtaps, int Lin, int Lout, int nr) {
-    const size_t xs = slice_ch + 4;
-    const size_t k = (size_t)cc_xrows(taps, Lin, Lout, nr) * xs + (size_t)wtaps * 32 * xs;
-    const size_t e = (size_t)2 * 8 * nr * 36;
-    return k > e ? k : e;
-}
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // grid = (K slices, M / 32, N tiles of NR GEMM rows); 8 waves: every wave owns the whole NR x 32 tile
@@ -640,10 +630,6 @@ struct FinalCcParams {
     CcSrc src;               // final_conv[0]'s output, still in pieces
     FinalParams f;           // everything else (f.act unused)
 };
-
-__host__ __device__ inline size_t final_cc_lds_floats(int td, int dim, int H) {
-    return (size_t)td * dim + ((td + 3) & ~3) + (size_t)H * (dim + 4);
-}
 
 __global__ __launch_bounds__(CC_THREADS) void final_cc_kernel(const FinalCcParams pp) {
     extern __shared__ __attribute__((aligned(16))) float ws[];

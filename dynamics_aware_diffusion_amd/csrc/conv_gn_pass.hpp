@@ -34,9 +34,7 @@ struct GnPassParams {
     int32_t cpg_real;    // > 0: channels of a group that exist (zero-padded widths); 0: all
 };
 
-constexpr int GNP_THREADS = 256;
-// pairs of up to GNP_THREADS * 4 * kGnPassMaxNpt elements (cpg x L)
-constexpr int kGnPassMaxNpt = 32;
+// (GNP_THREADS, kGnPassMaxNpt: conv_shapes.hpp)
 
 __device__ __forceinline__ float gnp_block_sum(float v, float* red) {
 #pragma unroll

@@ -55,6 +55,40 @@ DAD_HD inline int cc_xrows(int taps, int Lin, int Lout, int nr) {
     return Lout > nr ? nr + 2 * (taps / 2) : (nr / Lout) * (Lin + 2 * (taps / 2));
 }
 
+// conv_cc.hpp: 512 threads; a consumer adds up to CC_MAX_SLABS partial slabs per round trip (the BIG forms take two).
+constexpr int CC_THREADS = 512;
+constexpr int CC_MAX_SLABS = 8;
+// LDS floats of one conv_cc block: [X rows][slice + 4] + [weight taps][32][slice + 4], or the
+// exchange tile [8 waves][32][36] (+ the ride's) after the K loop.
+DAD_HD inline size_t cc_lds_floats(int slice_ch, int taps, int wtaps, int Lin, int Lout, int nr) {
+    const size_t xs = slice_ch + 4;
+    const size_t k = (size_t)cc_xrows(taps, Lin, Lout, nr) * xs + (size_t)wtaps * 32 * xs;
+    const size_t e = (size_t)2 * 8 * nr * 36;
+    return k > e ? k : e;
+}
+// final_cc_kernel: the 1x1 output conv's weights and bias + one sample of final_conv[0]'s output
+DAD_HD inline size_t final_cc_lds_floats(int td, int dim, int H) {
+    return (size_t)td * dim + ((td + 3) & ~3) + (size_t)H * (dim + 4);
+}
+
+// final_posterior_kernel (pointwise.hpp)
+constexpr int FINAL_COLS = 32;   // trajectory positions per block (256 blocks at B*H = 8192)
+// a block keeps the weight rows of ITS output columns (gy = gridDim.y column groups), the biases and
+// the activation tile
+DAD_HD inline int final_rows_local(int td, int gy) {
+    constexpr int JG = 256 / FINAL_COLS;
+    const int col_groups = (td + JG - 1) / JG;
+    return (col_groups + gy - 1) / gy * JG;
+}
+DAD_HD inline size_t final_lds_floats(int td, int dim, int gy) {
+    return (size_t)final_rows_local(td, gy) * dim + ((td + 3) & ~3) + (size_t)FINAL_COLS * (dim + 4);
+}
+
+// conv_gn_pass.hpp: one block of GNP_THREADS threads holds a (sample, group) pair in NPT float4 per thread,
+// NPT a power of two up to kGnPassMaxNpt: pairs of up to GNP_THREADS * 4 * kGnPassMaxNpt elements (cpg x L)
+constexpr int GNP_THREADS = 256;
+constexpr int kGnPassMaxNpt = 32;
+
 // conv_ccw.hpp (wide small-batch convs).  K phase: X rows with halo [XROWS][slice + 4], the additive
 // terms [rows][slice + 4], gamma / beta [2][slice], pair statistics; afterwards the exchange tile.
 constexpr int kCcwMaxPairs = 64;         // (sample, group) pairs of one block's input slice

@@ -308,13 +308,17 @@ struct ConvIO {
     float* pre = nullptr; float* stats = nullptr;      // training forward: pre-normalisation output, pair statistics
     float* slab = nullptr;                             // split-K scratch
 };
-int launch_conv(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hipStream_t st);
+int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, const ConvIO& io, hipStream_t st);
 
-// `plan`: m->plan (sampling: buffers shared by lifetime) or m->tplan (training: every tensor kept, plus
-// the pre-activation / statistics buffers of the GroupNorm'd convs).  `temb_rows`: (B, temb_width) time
-// projections of the training forward (indexed through trow), instead of the per-timestep table.
-int run_conv(dad_model* m, const Plan& plan, const ConvOp& op, const float* xext, float* ws, int batch, int t,
-             hipStream_t st, const int32_t* trow = nullptr, const float* temb_rows = nullptr) {
+// Launch `l` of the forward description `f`, on m->plan (sampling: buffers shared by lifetime) or m->tplan
+// (training: every tensor kept, plus the pre-activation / statistics buffers of the GroupNorm'd convs).
+// `temb_rows`: (B, temb_width) time projections of the training forward (indexed through trow), instead of the
+// per-timestep table.
+int run_conv(dad_model* m, const FwdPlan& f, const FwdLaunch& l, const float* xext, float* ws, int t, hipStream_t st,
+             const int32_t* trow, const float* temb_rows) {
+    const Plan& plan = f.train ? m->tplan : m->plan;
+    const ConvOp& op = plan.convs[l.conv];
+    const int batch = f.batch;
     auto buf = [&](int id) -> float* {
         return id >= 0 ? ws + plan.bufs[id].offset * (long)batch : nullptr;
     };
@@ -340,11 +344,12 @@ int run_conv(dad_model* m, const Plan& plan, const ConvOp& op, const float* xext
     io.rdst = buf(op.rdst);
     io.pre = buf(op.pre); io.stats = buf(op.stats);
     io.slab = ws + plan.floats_per_sample * (long)batch;     // scratch behind the activations
-    return launch_conv(m, op, batch, io, st);
+    return launch_conv(m, op, l.g, batch, io, st);
 }
 
-// GroupNorm -> Mish -> + time embedding -> + residual of a windowed layer (conv_gn_pass.hpp), after its conv
-int launch_gn_pass(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hipStream_t st) {
+// GroupNorm -> Mish -> + time embedding -> + residual of a windowed layer (conv_gn_pass.hpp), after its conv:
+// gn_pass_kernel<npt>, npt planned with the launch (LaunchGeom::gn_npt)
+int launch_gn_pass(dad_model* m, const ConvOp& op, int npt, int batch, const ConvIO& io, hipStream_t st) {
     dad::GnPassParams q{};
     q.src = io.pre != nullptr ? io.pre : io.dst;
     q.dst = io.dst;
@@ -352,28 +357,25 @@ int launch_gn_pass(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, 
     q.temb = io.temb; q.trow = io.trow; q.temb_stride = m->plan.temb_width;
     q.res = io.res; q.stats = io.stats;
     q.C = op.cout; q.L = op.Lout; q.cpg = op.cout / 8; q.lreal = op.lreal; q.cpg_real = op.gn_real;
-    const long elems = (long)q.cpg * q.L;
     const dim3 grid(8, (unsigned)batch), block(dad::GNP_THREADS);
-    const long per = dad::GNP_THREADS * 4L;              // elements per float4 of every thread
-    if (op.kind != CONV_K5 || q.cpg % 4 != 0 || elems > per * dad::kGnPassMaxNpt)
-        return fail(DAD_E_INVALID, "%s: no GroupNorm pass for %ld-element pairs", op.name.c_str(), elems);
-    if (elems <= per) hipLaunchKernelGGL(dad::gn_pass_kernel<1>, grid, block, 0, st, q);
-    else if (elems <= 2 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<2>, grid, block, 0, st, q);
-    else if (elems <= 4 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<4>, grid, block, 0, st, q);
-    else if (elems <= 8 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<8>, grid, block, 0, st, q);
-    else if (elems <= 16 * per) hipLaunchKernelGGL(dad::gn_pass_kernel<16>, grid, block, 0, st, q);
-    else hipLaunchKernelGGL(dad::gn_pass_kernel<32>, grid, block, 0, st, q);
+    static_assert(dad::kGnPassMaxNpt == 32, "one case per power of two up to kGnPassMaxNpt");
+    switch (npt) {
+        case 1: hipLaunchKernelGGL(dad::gn_pass_kernel<1>, grid, block, 0, st, q); break;
+        case 2: hipLaunchKernelGGL(dad::gn_pass_kernel<2>, grid, block, 0, st, q); break;
+        case 4: hipLaunchKernelGGL(dad::gn_pass_kernel<4>, grid, block, 0, st, q); break;
+        case 8: hipLaunchKernelGGL(dad::gn_pass_kernel<8>, grid, block, 0, st, q); break;
+        case 16: hipLaunchKernelGGL(dad::gn_pass_kernel<16>, grid, block, 0, st, q); break;
+        default: hipLaunchKernelGGL(dad::gn_pass_kernel<32>, grid, block, 0, st, q);
+    }
     HIP_TRY(hipGetLastError());
     return DAD_OK;
 }
 
-int launch_conv(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hipStream_t st) {
-    LaunchGeom g;
-    int rc = plan_launch(*m, op, batch, g);
-    if (rc != DAD_OK) return rc;
+// `g`: the launch as plan_launch accepted it (plan_forward, train_scratch); nothing is decided here
+int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, const ConvIO& io, hipStream_t st) {
     // windowed tiles of a GroupNorm'd layer: the conv stores conv + bias (into the pre-activation buffer when
     // the training forward keeps one), the pass over whole (sample, group) pairs finishes the block
-    const bool gn_pass = g.windowed && !op.norm.empty();
+    const bool gn_pass = g.gn_npt > 0;
     ConvParams p{};
     p.src0 = io.src0;
     p.src1 = io.src1;
@@ -425,7 +427,7 @@ int launch_conv(dad_model* m, const ConvOp& op, int batch, const ConvIO& io, hip
     void* args[] = {&p};
     HIP_TRY(hipLaunchKernel((const void*)it->second, dim3(g.gx, g.gy, g.gz), dim3(g.threads), args,
                             g.lds_bytes, st));
-    if (gn_pass) return launch_gn_pass(m, op, batch, io, st);
+    if (gn_pass) return launch_gn_pass(m, op, g.gn_npt, batch, io, st);
     return DAD_OK;
 }
 
@@ -439,21 +441,19 @@ int ensure_tables(dad_model* m, hipStream_t st) {
     return rc;
 }
 
-// rows per sample of the external tensors (x, noise, guide, means): the horizon before zero-padding
-inline int traj_horizon(const dad_model* m) { return m->real_horizon > 0 ? m->real_horizon : m->cfg.horizon; }
-
-int check_ready(const dad_model* m, int batch, int t, size_t ws_bytes) {
+// Every refusal of a forward entry point, before its first launch; `f`: what the call then replays (plan_forward).
+int check_ready(const dad_model* m, int batch, int t, size_t ws_bytes, bool small_ok, FwdPlan& f) {
     if (!m) return fail(DAD_E_INVALID, "null model");
     if (!m->finalized) return fail(DAD_E_STATE, "dad_model_finalize has not been called");
     if (batch <= 0) return fail(DAD_E_INVALID, "batch must be positive (got %d)", batch);
     if (t < 0 || t >= m->cfg.n_timesteps)
         return fail(DAD_E_RANGE, "index %d is out of bounds for the schedule of size %d", t,
                     m->cfg.n_timesteps);
-    const size_t need = workspace_bytes(*m, batch);
-    if (ws_bytes < need)
+    const int rc = plan_forward(*m, false, batch, small_ok, f);
+    if (ws_bytes < f.bytes)
         return fail(DAD_E_WORKSPACE, "workspace has %zu bytes, batch %d needs %zu", ws_bytes, batch,
-                    need);
-    return DAD_OK;
+                    f.bytes);
+    return rc;
 }
 
 // ------------------------------------------------------------------ small-batch (CC) launches
@@ -505,14 +505,8 @@ int run_conv_cc(dad_model* m, const CcPlan& cc, int i, const float* xext, float*
     p.oslab = slabs + o.oslab;
     p.orslab = o.orslab >= 0 ? slabs + o.orslab : nullptr;
     p.out_rows = o.out_rows;
-    const bool shape_ok = (op.taps == 5 && op.stride == 1) || (op.taps == 3 && op.stride == 2) || (op.taps == 2 && op.stride == 1);
-    const bool big = p.src0.nsl > dad::CC_MAX_SLABS || p.src0.nrs > dad::CC_MAX_SLABS ||
-                     p.src1.nsl > dad::CC_MAX_SLABS || p.src1.nrs > dad::CC_MAX_SLABS;
-    const void* kern = shape_ok ? cc_kernel(op.taps, op.ride, big, o.tile_rows, op.Lout > 32) : nullptr;
-    if (o.wide) {
-        if (big) return fail(DAD_E_INVALID, "wide small-batch conv %s: more than %d partial slabs", op.name.c_str(), dad::CC_MAX_SLABS);
-        kern = ccw_kernel(op.taps, op.ride, p.src0.rslab != nullptr || p.src1.rslab != nullptr, o.tile_rows);
-    }
+    const void* kern = o.wide ? ccw_kernel(op.taps, op.ride, o.ride_in, o.tile_rows)
+                              : cc_kernel(op.taps, op.ride, o.big, o.tile_rows, op.Lout > 32);
     if (!kern) return fail(DAD_E_INVALID, "no small-batch kernel for %s (taps=%d stride=%d)", op.name.c_str(), op.taps, op.stride);
     static const bool trace = getenv("DAD_TRACE_TILES") != nullptr;
     if (trace)
@@ -527,9 +521,9 @@ int run_conv_cc(dad_model* m, const CcPlan& cc, int i, const float* xext, float*
     return DAD_OK;
 }
 
-int run_unet(dad_model* m, const float* x, int t, int batch, float* ws, hipStream_t st,
-             const int32_t* trow = nullptr, const CcPlan* cc = nullptr, bool train = false,
-             const float* temb_rows = nullptr) {
+// One denoiser evaluation up to final_conv[0]: the launches of `f`, nothing else
+int run_unet(dad_model* m, const FwdPlan& f, const float* x, int t, float* ws, hipStream_t st,
+             const int32_t* trow = nullptr, const float* temb_rows = nullptr) {
     // Profiling brackets the whole run of conv-GEMM launches of one denoiser evaluation with
     // ONE pair of HIP events on the launch stream (events between individual launches would
     // break the back-to-back dispatch they are meant to time).
@@ -546,41 +540,34 @@ int run_unet(dad_model* m, const float* x, int t, int batch, float* ws, hipStrea
         ++m->ev_used;
         HIP_TRY(hipEventRecord(e0, st));
     }
-    const Plan& plan = train ? m->tplan : m->plan;
-    const std::vector<ConvOp>& convs = plan.convs;
-    if (cc != nullptr) {                                  // small batch: consumer-combine kernels
-        for (size_t i = 0; i < convs.size(); ++i) {
-            if (m->profile) m->prof_flops += convs[i].flops_per_sample * batch;
-            if (!cc->ops[i].launched) continue;
-            const int rc = run_conv_cc(m, *cc, (int)i, x, ws, batch, t, st);
-            if (rc != DAD_OK) return rc;
-            if (m->profile) ++m->prof_launches;
-        }
-        if (m->profile) HIP_TRY(hipEventRecord(e1, st));
-        return DAD_OK;
-    }
-    for (const ConvOp& op : convs) {
-        // a residual 1x1 conv whose block's first conv carries it at this batch is not launched
-        const bool rides = op.rider_of >= 0 && fused_at(*m, convs[op.rider_of], batch);
-        if (m->profile) m->prof_flops += op.flops_per_sample * batch;
-        if (rides) continue;
-        const int rc = run_conv(m, plan, op, x, ws, batch, t, st, trow, temb_rows);
+    for (size_t i = 0; f.cc.ok && i < f.cc.ops.size(); ++i) {        // small batch: consumer-combine kernels
+        if (!f.cc.ops[i].launched) continue;
+        const int rc = run_conv_cc(m, f.cc, (int)i, x, ws, f.batch, t, st);
         if (rc != DAD_OK) return rc;
-        if (m->profile) ++m->prof_launches;
     }
-    if (m->profile) HIP_TRY(hipEventRecord(e1, st));
+    for (const FwdLaunch& l : f.launches) {
+        const int rc = run_conv(m, f, l, x, ws, t, st, trow, temb_rows);
+        if (rc != DAD_OK) return rc;
+    }
+    if (m->profile) {                 // (a riding 1x1 residual conv counts its flops, not a launch)
+        for (const ConvOp& op : m->plan.convs) m->prof_flops += op.flops_per_sample * f.batch;
+        for (const CcOp& o : f.cc.ops) m->prof_launches += o.launched;
+        m->prof_launches += (int64_t)f.launches.size();
+        HIP_TRY(hipEventRecord(e1, st));
+    }
     return DAD_OK;
 }
 
-int run_final(dad_model* m, float* x, const float* x_ro, int t, int batch, const dad_step_args* a,
-              int x_out_disabled, float* eps_only, float* ws, hipStream_t st,
-              bool seed_from_device = false, const CcPlan* cc = nullptr, bool train = false) {
+// final_conv[1] and the posterior update (or, `eps_only`, the network output alone), on the grid `f` planned
+int run_final(dad_model* m, const FwdPlan& f, float* x, const float* x_ro, int t, const dad_step_args* a,
+              int x_out_disabled, float* eps_only, float* ws, hipStream_t st, bool seed_from_device = false) {
     const dad_cfg& c = m->cfg;
+    const int batch = f.batch;
     dad::FinalParams p{};
-    const Plan& plan = train ? m->tplan : m->plan;
+    const Plan& plan = f.train ? m->tplan : m->plan;
     p.act = ws + plan.bufs[plan.final_act].offset * (long)batch;
     p.w = m->d_final_w; p.bias = m->d_final_b;
-    p.dim = c.dim; p.td = c.transition_dim; p.B = batch; p.H = traj_horizon(m); p.Hact = c.horizon;
+    p.dim = c.dim; p.td = c.transition_dim; p.B = batch; p.H = traj_horizon(*m); p.Hact = c.horizon;
     p.predict_epsilon = c.predict_epsilon; p.clip_denoised = c.clip_denoised;
     if (eps_only) {
         p.x = const_cast<float*>(x_ro);
@@ -598,39 +585,21 @@ int run_final(dad_model* m, float* x, const float* x_ro, int t, int batch, const
         p.sigma = t == 0 ? 0.0f : expf(0.5f * lv);
         p.guide_scale = a->guide_weight * expf(lv);
         p.seed = a->seed;
-        p.elem_offset = a->row_offset * (uint64_t)traj_horizon(m) * (uint64_t)c.transition_dim;
+        p.elem_offset = a->row_offset * (uint64_t)traj_horizon(*m) * (uint64_t)c.transition_dim;
         p.draw = a->draw;
         p.seed_dev = seed_from_device ? (const unsigned long long*)m->d_rng : nullptr;
     }
-    if (cc != nullptr) {
+    const dim3 grid(f.final_gx, f.final_gy);
+    if (f.cc.ok) {
         dad::FinalCcParams fp{};
-        CcInput in; in.kind = 3; in.producer = cc->final_producer; in.buf = m->plan.final_act;
-        fp.src = cc_source(m, *cc, in, c.dim, x_ro ? x_ro : x, ws, batch, t);
+        CcInput in; in.kind = 3; in.producer = f.cc.final_producer; in.buf = m->plan.final_act;
+        fp.src = cc_source(m, f.cc, in, c.dim, x_ro ? x_ro : x, ws, batch, t);
         fp.src.mat = nullptr;
         fp.f = p;
-        const size_t lds_cc = dad::final_cc_lds_floats(c.transition_dim, c.dim, c.horizon) * sizeof(float);
-        if (lds_cc > dad::kLdsBytes)
-            return fail(DAD_E_INVALID, "final 1x1 conv does not fit LDS (td=%d, dim=%d)", c.transition_dim, c.dim);
-        // one block per (sample, group of output columns): enough columns per block to occupy its
-        // 512 threads once, as long as the grid stays within one wave of blocks
-        const int want = (c.horizon * c.transition_dim + dad::CC_THREADS - 1) / dad::CC_THREADS;
-        const int gy = std::max(1, std::min({want, c.transition_dim, 256 / std::max(batch, 1)}));
-        hipLaunchKernelGGL(dad::final_cc_kernel, dim3(batch, gy), dim3(dad::CC_THREADS), lds_cc, st, fp);
-        HIP_TRY(hipGetLastError());
-        return DAD_OK;
+        hipLaunchKernelGGL(dad::final_cc_kernel, grid, dim3(dad::CC_THREADS), f.final_lds, st, fp);
+    } else {
+        hipLaunchKernelGGL(dad::final_posterior_kernel, grid, dim3(256), f.final_lds, st, p);
     }
-    const long N = (long)batch * traj_horizon(m);
-    // columns of the transition are spread over gridDim.y when the row tiles alone leave CUs idle
-    // (a block stages only the weight rows of its own columns), and further until a block fits LDS
-    const long row_tiles = (N + dad::FINAL_COLS - 1) / dad::FINAL_COLS;
-    const int jg = 256 / dad::FINAL_COLS;
-    const long col_groups = (c.transition_dim + jg - 1) / jg;
-    long gy = std::max(1L, std::min(col_groups, 512 / row_tiles));
-    while (gy < col_groups && dad::final_lds_floats(c.transition_dim, c.dim, (int)gy) * sizeof(float) > dad::kLdsBytes) ++gy;
-    const size_t lds = dad::final_lds_floats(c.transition_dim, c.dim, (int)gy) * sizeof(float);
-    if (lds > dad::kLdsBytes)
-        return fail(DAD_E_INVALID, "final 1x1 conv does not fit LDS (td=%d, dim=%d)", c.transition_dim, c.dim);
-    hipLaunchKernelGGL(dad::final_posterior_kernel, dim3((unsigned)row_tiles, (unsigned)gy), dim3(256), lds, st, p);
     HIP_TRY(hipGetLastError());
     return DAD_OK;
 }
@@ -910,40 +879,39 @@ int dad_workspace_bytes(const dad_model* m, int32_t batch, size_t* bytes) {
 
 int dad_unet_forward(dad_model* m, const float* x, int32_t t, float* out, int32_t batch,
                      void* workspace, size_t workspace_bytes, dad_stream_t stream) {
-    int rc = check_ready(m, batch, t, workspace_bytes);
+    FwdPlan f;
+    int rc = check_ready(m, batch, t, workspace_bytes, true, f);
     if (rc != DAD_OK) return rc;
     if (!x || !out || !workspace) return fail(DAD_E_INVALID, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;
-    const CcPlan cc = cc_plan(*m, batch);
-    const CcPlan* ccp = cc.ok ? &cc : nullptr;
-    if ((rc = run_unet(m, x, t, batch, (float*)workspace, st, nullptr, ccp)) != DAD_OK) return rc;
-    return run_final(m, nullptr, x, t, batch, nullptr, 1, out, (float*)workspace, st, false, ccp);
+    if ((rc = run_unet(m, f, x, t, (float*)workspace, st)) != DAD_OK) return rc;
+    return run_final(m, f, nullptr, x, t, nullptr, 1, out, (float*)workspace, st);
 }
 
 int dad_unet_forward_rows(dad_model* m, const float* x, const int32_t* t_rows, float* out, int32_t batch,
                           void* workspace, size_t workspace_bytes, dad_stream_t stream) {
-    int rc = check_ready(m, batch, 0, workspace_bytes);
+    FwdPlan f;
+    int rc = check_ready(m, batch, 0, workspace_bytes, false, f);      // per-row timesteps: the batch kernels
     if (rc != DAD_OK) return rc;
     if (!x || !out || !workspace || !t_rows) return fail(DAD_E_INVALID, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;
-    if ((rc = run_unet(m, x, 0, batch, (float*)workspace, st, t_rows)) != DAD_OK) return rc;
-    return run_final(m, nullptr, x, 0, batch, nullptr, 1, out, (float*)workspace, st);
+    if ((rc = run_unet(m, f, x, 0, (float*)workspace, st, t_rows)) != DAD_OK) return rc;
+    return run_final(m, f, nullptr, x, 0, nullptr, 1, out, (float*)workspace, st);
 }
 
 int dad_denoise_step(dad_model* m, float* x, int32_t t, int32_t batch, const dad_step_args* args,
                      int32_t x_out_disabled, void* workspace, size_t workspace_bytes,
                      dad_stream_t stream) {
-    int rc = check_ready(m, batch, t, workspace_bytes);
+    FwdPlan f;
+    int rc = check_ready(m, batch, t, workspace_bytes, true, f);
     if (rc != DAD_OK) return rc;
     if (!x || !args || !workspace) return fail(DAD_E_INVALID, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;
-    const CcPlan cc = cc_plan(*m, batch);
-    const CcPlan* ccp = cc.ok ? &cc : nullptr;
-    if ((rc = run_unet(m, x, t, batch, (float*)workspace, st, nullptr, ccp)) != DAD_OK) return rc;
-    return run_final(m, x, nullptr, t, batch, args, x_out_disabled, nullptr, (float*)workspace, st, false, ccp);
+    if ((rc = run_unet(m, f, x, t, (float*)workspace, st)) != DAD_OK) return rc;
+    return run_final(m, f, x, nullptr, t, args, x_out_disabled, nullptr, (float*)workspace, st);
 }
 
 int dad_project(const dad_project_args* p, float alpha, float* x, int32_t batch, int32_t horizon,
@@ -964,17 +932,16 @@ int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
                     const float* proj_alphas_host, int32_t use_graph, void* workspace,
                     size_t workspace_bytes, dad_stream_t stream) {
     if (n_steps < 1) return fail(DAD_E_INVALID, "n_steps must be positive");
-    int rc = check_ready(m, batch, n_steps - 1, workspace_bytes);
+    FwdPlan f;                  // one description for all n_steps evaluations (and for a capture of them)
+    int rc = check_ready(m, batch, n_steps - 1, workspace_bytes, true, f);
     if (rc != DAD_OK) return rc;
     if (!x || !workspace) return fail(DAD_E_INVALID, "null pointer");
     if (proj && !proj_alphas_host) return fail(DAD_E_INVALID, "projection needs per-step alphas");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;      // (before any capture: the replayed loop reads the tables)
-    const long step_elems = (long)batch * traj_horizon(m) * m->cfg.transition_dim;
+    const long step_elems = (long)batch * traj_horizon(*m) * m->cfg.transition_dim;
 
     const bool seed_dev = use_graph && !m->profile && noise_stack == nullptr;
-    const CcPlan cc = cc_plan(*m, batch);
-    const CcPlan* ccp = cc.ok ? &cc : nullptr;
     auto enqueue_all = [&](hipStream_t st) -> int {
         for (int j = 0; j < n_steps; ++j) {
             const int t = n_steps - 1 - j;
@@ -982,12 +949,10 @@ int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
             a.noise = noise_stack ? noise_stack + (long)j * step_elems : nullptr;
             a.seed = seed; a.row_offset = row_offset; a.draw = (uint64_t)(j + 1);
             a.cond0 = cond0; a.cond_per_row = cond_per_row;
-            int r = run_unet(m, x, t, batch, (float*)workspace, st, nullptr, ccp);
+            int r = run_unet(m, f, x, t, (float*)workspace, st);
             if (r != DAD_OK) return r;
-            if ((r = run_final(m, x, nullptr, t, batch, &a, 0, nullptr, (float*)workspace, st,
-                               seed_dev, ccp)) != DAD_OK)
-                return r;
-            if (proj && (r = run_project(proj, proj_alphas_host[t], x, batch, traj_horizon(m), st)) != DAD_OK)
+            if ((r = run_final(m, f, x, nullptr, t, &a, 0, nullptr, (float*)workspace, st, seed_dev)) != DAD_OK) return r;
+            if (proj && (r = run_project(proj, proj_alphas_host[t], x, batch, traj_horizon(*m), st)) != DAD_OK)
                 return r;
         }
         return DAD_OK;
@@ -1015,7 +980,7 @@ int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
     key.n_steps = n_steps; key.batch = batch; key.cond_per_row = cond_per_row;
     key.force_tile = m->force_tile;
     key.flags = (m->split_enabled ? 1 : 0) | (m->fuse_residual ? 2 : 0) | (m->xswz_enabled ? 4 : 0) |
-                (m->xcd_order ? 8 : 0) | (ccp ? 16 : 0) | (m->split_target << 8);
+                (m->xcd_order ? 8 : 0) | (f.cc.ok ? 16 : 0) | (m->split_target << 8);
     key.row_offset = row_offset;
     if (proj) {
         uint64_t hsh = 1469598103934665603ull;            // FNV-1a over the per-step alphas
@@ -1164,10 +1129,6 @@ int dad_train_grad_info(const dad_model* m, int32_t i, const char** key, int64_t
 
 namespace {
 
-size_t train_saved_bytes(const dad_model& m, int B) {
-    return ((size_t)m.tplan.floats_per_sample * (size_t)B + (size_t)slab_floats_for(m, B)) * sizeof(float);
-}
-
 // weight-gradient step `s` of the backward plan, geometry `w` (train_scratch); split batches go through `wslab`
 int launch_wgrad(const dad_model* m, const BwdStep& s, const TrainScratch::Wgrad& w, const float* G, const float* Z0,
                  const float* Z1, float* out, float* wslab, hipStream_t st) {
@@ -1215,7 +1176,11 @@ extern "C" {
 
 int dad_train_workspace_bytes(const dad_model* m, int32_t batch, size_t* saved_bytes, size_t* scratch_bytes) {
     if (!m || batch <= 0) return fail(DAD_E_INVALID, "bad argument");
-    if (saved_bytes) *saved_bytes = train_saved_bytes(*m, batch);
+    if (saved_bytes) {
+        FwdPlan f;
+        plan_forward(*m, true, batch, false, f);       // (as below: a refused batch still has a size)
+        *saved_bytes = f.bytes;
+    }
     if (scratch_bytes) {
         TrainScratch ts;
         train_scratch(*m, batch, ts);          // a batch the backward pass refuses is refused there, not here
@@ -1229,12 +1194,14 @@ int dad_unet_forward_train(dad_model* m, const float* x, const int32_t* row_inde
     int rc = check_train(m, batch);
     if (rc != DAD_OK) return rc;
     if (!x || !row_index || !temb_rows || !out || !saved) return fail(DAD_E_INVALID, "null pointer");
-    if (saved_bytes < train_saved_bytes(*m, batch))
-        return fail(DAD_E_WORKSPACE, "saved-activation buffer has %zu bytes, batch %d needs %zu", saved_bytes, batch,
-                    train_saved_bytes(*m, batch));
+    FwdPlan f;
+    rc = plan_forward(*m, true, batch, false, f);
+    if (saved_bytes < f.bytes)
+        return fail(DAD_E_WORKSPACE, "saved-activation buffer has %zu bytes, batch %d needs %zu", saved_bytes, batch, f.bytes);
+    if (rc != DAD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = run_unet(m, x, 0, batch, (float*)saved, st, row_index, nullptr, true, temb_rows)) != DAD_OK) return rc;
-    return run_final(m, nullptr, x, 0, batch, nullptr, 1, out, (float*)saved, st, false, nullptr, true);
+    if ((rc = run_unet(m, f, x, 0, (float*)saved, st, row_index, temb_rows)) != DAD_OK) return rc;
+    return run_final(m, f, nullptr, x, 0, nullptr, 1, out, (float*)saved, st);
 }
 
 int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d_x, float* d_temb_rows,
@@ -1250,11 +1217,13 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
     for (int32_t i = 0; i < n_grad_tensors; ++i)
         if (!grad_tensors[i]) return fail(DAD_E_INVALID, "gradient tensor %d ('%s') is null", i, m->grad_slots[i].key.c_str());
     const int B = batch;
+    FwdPlan fwd;                                   // (read for the size of `saved` alone)
+    plan_forward(*m, true, B, false, fwd);
     TrainScratch ts;
     const int geom_rc = train_scratch(*m, B, ts);
-    if (saved_bytes < train_saved_bytes(*m, B) || scratch_bytes < (size_t)ts.total * sizeof(float))
+    if (saved_bytes < fwd.bytes || scratch_bytes < (size_t)ts.total * sizeof(float))
         return fail(DAD_E_WORKSPACE, "backward workspaces too small (saved %zu / %zu, scratch %zu / %zu bytes)", saved_bytes,
-                    train_saved_bytes(*m, B), scratch_bytes, (size_t)ts.total * sizeof(float));
+                    fwd.bytes, scratch_bytes, (size_t)ts.total * sizeof(float));
     if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
     if (geom_rc != DAD_OK) return geom_rc;
     if (d_x != nullptr && !m->bdx) return fail(DAD_E_STATE, "backward: no gradient reached the trajectory");
@@ -1271,7 +1240,7 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
     float* const bslab = tmp + ts.tmp;
     // zero-padded horizon: the trajectory and d loss / d out arrive in their real shape (B, H_real, td); the pass runs on
     // copies in the padded layout (zero rows behind the real ones), d x goes back through the same row map
-    const int Hr = traj_horizon(m);
+    const int Hr = traj_horizon(*m);
     if (Hr != H) {
         float* const xpad = dxpad + (long)B * H * tdp;
         float* const dopad = xpad + (long)B * H * round_up(td, 4);
@@ -1293,7 +1262,7 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
     };
 
     // the steps of the backward plan (build_backward_plan), in order
-    size_t nw = 0;
+    size_t nw = 0, nd = 0;
     for (const BwdStep& s : m->bsteps) {
         switch (s.kind) {
             case BK_BIAS:
@@ -1310,7 +1279,7 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
                 io.src0 = ptr(s.in); io.slab = bslab;
                 io.dst = s.write == BW_STAGE ? tmp : ptr(s.out);
                 io.res = s.write == BW_ADD ? io.dst : nullptr;
-                if ((rc = launch_conv(m, bwd_op(*m, s), B, io, st)) != DAD_OK) return rc;
+                if ((rc = launch_conv(m, bwd_op(*m, s), ts.dgrads[nd++].g, B, io, st)) != DAD_OK) return rc;
                 if (s.write == BW_STAGE && (rc = accumulate(ptr(s.out), tmp, s.n * B, BW_ADD, st)) != DAD_OK) return rc;
                 break;
             }

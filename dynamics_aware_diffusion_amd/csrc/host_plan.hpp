@@ -1,12 +1,15 @@
 // host_plan.hpp — everything libdad_hip.so decides on the HOST before a kernel is launched:
 // validation of the architecture, the launch plan of TemporalUnet.forward, workspace layout,
 // weight packing (fp32 and split-f16 images), tile choice, grid-level split-K, the LDS slot
-// shifts, the launch geometry of every conv-GEMM, and the backward pass as a list of steps with its
-// per-batch geometry.  Plain C++17, no HIP: dad_lib.hip includes
-// it for the product, tests/sanitize/host_check.cpp compiles it host-only under
-// -fsanitize=address,undefined.
+// shifts, the launch geometry of every conv-GEMM, the small-batch plan, and — per call — one description of
+// everything a forward evaluation launches at a batch (FwdPlan, plan_forward) and of the backward pass (the list
+// of steps of build_backward_plan with its per-batch geometry, train_scratch).  The entry points of dad_lib.hip
+// build those two once per call, refuse before their first launch, and only replay them; the size queries and
+// the plan report read the same descriptions.  Plain C++17, no HIP: dad_lib.hip includes it for the product,
+// tests/sanitize/host_check.cpp compiles it host-only under -fsanitize=address,undefined.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -65,7 +68,7 @@ struct ConvOp {
     // 5-tap conv stages (temporal_unet.py:117-121).  It exists in the plan as its own launch
     // (rider_of = index of that conv) and, where the kernel variant exists, ALSO as a sixth
     // "tap" inside that conv's weight image (rname/rdst; own accumulator, plain bias epilogue).
-    // Which of the two runs is decided per batch (fused_at): the ride needs the whole K in one
+    // Which of the two runs is decided per batch (LaunchGeom::fused of the carrier): the ride needs the whole K in one
     // block, so batches small enough for grid-level split-K keep the separate launch.
     std::string rname;       // weight key prefix of the riding residual conv, or ""
     int rdst = -1;           // buffer the ride writes
@@ -130,7 +133,7 @@ constexpr int kMaxTileBN = 128;   // the longest layer a whole-sample tile holds
 constexpr bool kWinTiles[kNumTiles] = {true, true, true, false, false, false, false, false, false, false};
 // Tiles with PADDED instantiations (zero-padded nets: the tiles choose_tile's heuristic picks):
 constexpr bool kPaddedTiles[kNumTiles] = {true, true, true, true, true, false, false, false, true, true};
-constexpr int kGnPassMaxPair = 256 * 4 * 32;   // elements of a (sample, group) pair the GroupNorm pass holds
+constexpr int kGnPassMaxPair = dad::GNP_THREADS * 4 * dad::kGnPassMaxNpt;   // elements of a (sample, group) pair the GroupNorm pass holds
 inline bool windowed_layer(const ConvOp& op) { return op.Lout > kMaxTileBN; }
 // N tiles of a launch: whole samples per tile, or Lout / BN windows per sample
 inline long tiles_n(const ConvOp& op, int BN, int batch) {
@@ -215,7 +218,7 @@ struct HostModel {
     int wgrad_blocks = 256;                                    // blocks a weight-gradient launch aims for (tiles x batch splits)
     bool ccw_prefer16 = true;                                  //   two 16-row tiles instead of an LDS-short 32-row one
                                                                //   (measured crossover: batch 16 at H = 32)
-    std::map<std::vector<int>, uint64_t> xswz_cache;           // find_xswz memo
+    mutable std::map<std::array<int, 5>, uint64_t> xswz_cache; // find_xswz memo: the cache of a pure function, filled by const planning
     // ---- backward pass (dad_model_set_training): data-gradient launches + the layout of the gradients
     bool training = false;
     struct BwdConv {
@@ -920,9 +923,9 @@ inline int choose_tile(const HostModel& m, const ConvOp& op, int batch) {
 // 32-row wave tile both 16-lane groups of ds_read_b128 see 16 distinct slots, and no sample is
 // pushed onto its neighbour's real rows (d(s) - d(s+1) <= pad * slots-per-row).  Returns 0 (plain
 // layout — correct, just slower) when L >= 32, when there is no halo, or when nothing is found.
-inline uint64_t find_xswz(HostModel& m, int L, int stride, int pad, int kp4, int BN) {
+inline uint64_t find_xswz(const HostModel& m, int L, int stride, int pad, int kp4, int BN) {
     if (L >= 32 || pad == 0 || BN / L > 16) return 0;
-    const std::vector<int> key{L, stride, pad, kp4, BN};
+    const std::array<int, 5> key{L, stride, pad, kp4, BN};
     auto it = m.xswz_cache.find(key);
     if (it != m.xswz_cache.end()) return it->second;
     static const int groups[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
@@ -986,112 +989,6 @@ inline SplitPlan plan_split(const HostModel& m, const ConvOp& op, int cfg, int b
     return sp;
 }
 
-// floats of split-K scratch a batch needs (max over layers)
-inline long slab_floats_for(const HostModel& m, int batch) {
-    long best = 0;
-    for (const ConvOp& op : m.plan.convs) {
-        const int cfg = choose_tile(m, op, batch);
-        if (cfg < 0) continue;
-        best = std::max(best, plan_split(m, op, cfg, batch).slab_floats);
-    }
-    return best;
-}
-
-// ------------------------------------------------------------------ backward pass: per-batch geometry
-// conv_wgrad instantiations exist for these tap counts (the list of dad_lib.hip, wgrad_kernels, is built from them)
-constexpr int kWgradTaps[] = {1, 3, 4, 5, 7};
-struct WgradGeom { int spc, ksplit, sps, tile, tm, tn; unsigned gx, gy; size_t lds; };
-// Layers longer than a chunk stages (more than 128 rows of G or Z per sample: horizons 256 / 512) run the windowed
-// kernel over windows of kWgradWindow rows of G (and the matching rows of Z) as if they were samples.
-constexpr int kWgradWindow = 64;
-struct WgradShape { int B, Lg, Lz, wshift; };
-inline WgradShape wgrad_shape(int B, int Lg, int Lz) {
-    if (Lg <= 128 && Lz <= 128) return {B, Lg, Lz, 0};
-    const int nw = Lg / kWgradWindow;
-    return {B * nw, kWgradWindow, Lz / nw, ilog2(nw)};
-}
-// Block tile: the largest of 64 x 64 / 64 x 32 / 32 x 32 that still gives the layer 32 tiles (the smaller tiles
-// split K inside the block instead of over the grid: fewer partial slabs to write and add); the batch is then split
-// over blockIdx.z until `target` blocks exist (one block = 8 waves = two per SIMD).
-inline WgradGeom wgrad_geom(int M, int Ctot, int B, int Lg, int Lz, int taps, int pad, int target, bool ragged) {
-    WgradGeom g{};
-    g.spc = std::max(1, dad::WG_ROWS / Lg);
-    while (g.spc > 1 && g.spc * dad::wgrad_segz(Lz, taps, pad) > dad::WG_MAX_ZROWS) g.spc /= 2;
-    static const int tms[3] = {2, 2, 1}, tns[3] = {2, 1, 1};
-    long tiles = 0;
-    for (g.tile = ragged ? 2 : 0; g.tile < 3; ++g.tile) {
-        g.tm = tms[g.tile]; g.tn = tns[g.tile];
-        g.gx = (unsigned)((M + 32 * g.tm - 1) / (32 * g.tm));
-        g.gy = (unsigned)((Ctot + 32 * g.tn - 1) / (32 * g.tn));
-        tiles = (long)g.gx * g.gy;
-        const int kgroups = 8 / (g.tm * g.tn);
-        if ((tiles >= 32 && (g.spc * Lg) % (4 * kgroups) == 0) || g.tile == 2) break;
-    }
-    const int chunks = (B + g.spc - 1) / g.spc;
-    int want = (int)std::max(1L, target / tiles);
-    want = std::min(want, chunks);
-    g.sps = (chunks + want - 1) / want * g.spc;                // samples per split: whole chunks
-    g.ksplit = (B + g.sps - 1) / g.sps;
-    g.lds = dad::wgrad_lds_floats(g.spc, Lg, Lz, taps, pad, g.tm, g.tn) * sizeof(float);
-    if (ragged) g.tile = 3;
-    return g;
-}
-
-// Scratch of dad_unet_backward, in floats: gradient mirror of the training plan | per-sample partial sums
-// | wgrad split slabs | padded d x | staging of a down-sampling conv's data gradient | split-K slabs;
-// and the geometry of every weight-gradient step of m.bsteps, in order.
-struct TrainScratch {
-    long mirror = 0, part = 0, wslab = 0, dxpad = 0, tmp = 0, bslab = 0, total = 0;
-    struct Wgrad { WgradShape sh; WgradGeom g; };
-    std::vector<Wgrad> wgrads;
-};
-inline const ConvOp& bwd_op(const HostModel& m, const BwdStep& s) { return s.conv < 0 ? m.bfinal : m.bconvs[s.conv].op[s.sub]; }
-// Everything of the backward pass that depends on the batch, with every check of its launches.  `t` is filled even
-// when a check fails: dad_train_workspace_bytes reports the sizes, dad_unet_backward refuses before its first launch.
-inline int train_scratch(const HostModel& m, int B, TrainScratch& t) {
-    const int H = m.cfg.horizon, td = m.cfg.transition_dim;
-    int rc = DAD_OK;
-    t = TrainScratch();
-    t.mirror = m.tplan.floats_per_sample * (long)B;
-    for (const ConvOp& f : m.tplan.convs) t.part += (f.norm.empty() ? 1L : 3L) * B * round_up(f.cout, 4);
-    t.part += (long)B * round_up(td, 4);
-    for (const BwdStep& s : m.bsteps) {
-        if (s.kind == BK_WGRAD) {
-            const WgradShape sh = wgrad_shape(B, s.Lg, s.Lz);             // windows of long layers run as samples
-            const bool ragged = ((s.M | s.C0 | s.C1) & 3) != 0;          // rows that are not whole aligned float4s
-            const WgradGeom g = wgrad_geom(s.M, s.C0 + s.C1, sh.B, sh.Lg, sh.Lz, s.taps, s.pad, m.wgrad_blocks, ragged);
-            const long numel = (long)s.M * (s.C0 + s.C1) * s.taps;
-            const int kgroups = 8 / (g.tm * g.tn);
-            if (rc == DAD_OK && (g.lds > dad::kLdsBytes || g.spc * sh.Lg > dad::WG_MAX_GROWS ||
-                                 g.spc * dad::wgrad_segz(sh.Lz, s.taps, s.pad) > dad::WG_MAX_ZROWS ||
-                                 (g.spc * sh.Lg) % (4 * kgroups) != 0))
-                rc = fail(DAD_E_INVALID, "wgrad: a chunk of %d samples x %d rows does not fit the kernel's staging", g.spc, sh.Lz);
-            if (rc == DAD_OK && std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) == std::end(kWgradTaps))
-                rc = fail(DAD_E_INVALID, "wgrad: %d taps", s.taps);
-            if (rc == DAD_OK && g.ksplit > 1 && numel % 4 != 0)
-                rc = fail(DAD_E_INVALID, "wgrad: %ld gradient elements (not a multiple of 4)", numel);
-            if (g.ksplit > 1) t.wslab = std::max(t.wslab, (long)g.ksplit * numel);
-            t.wgrads.push_back({sh, g});
-        } else if (s.kind == BK_DGRAD) {
-            const ConvOp& op = bwd_op(m, s);
-            const int cfg = choose_tile(m, op, B);
-            if (cfg >= 0) t.bslab = std::max(t.bslab, plan_split(m, op, cfg, B).slab_floats);
-            if (op.kind == CONV_UP) t.tmp = std::max(t.tmp, (long)B * s.n);
-        }
-    }
-    t.dxpad = (long)B * H * round_up(td, 32);
-    if (m.real_horizon > 0 && m.real_horizon != H) t.dxpad += 2L * B * H * round_up(td, 4);      // zero-padded copies of x and d out
-    auto al = [](long v) { return (v + 63) / 64 * 64; };
-    t.mirror = al(t.mirror); t.part = al(t.part); t.wslab = al(t.wslab); t.dxpad = al(t.dxpad);
-    t.tmp = al(t.tmp); t.bslab = al(t.bslab);
-    t.total = t.mirror + t.part + t.wslab + t.dxpad + t.tmp + t.bslab;
-    if (rc == DAD_OK && m.bpart * B > t.part)
-        rc = fail(DAD_E_WORKSPACE, "backward: partial sums overran their region (%ld > %ld floats)", m.bpart * B, t.part);
-    return rc;
-}
-
-inline size_t workspace_bytes(const HostModel& m, int batch);
-
 // ---------------------------------------------------------------------- launch geometry
 // Everything a conv-GEMM launch needs besides pointers, decided on the host and checked here
 // (operand shapes against what the kernel and its grid assume) before anything reaches the GPU.
@@ -1106,22 +1003,31 @@ struct LaunchGeom {
     int xcd_gn = 0, xcd_mts = 0, xcd_ntn = 0;
     bool fused = false;      // the residual conv rides in this launch
     bool padded = false;     // PADDED instantiation (zero-padded rows / channels; every windowed launch)
-    bool windowed = false;   // windowed tiles (layer longer than the tile); a GroupNorm'd layer adds conv_gn_pass
+    bool windowed = false;   // windowed tiles (layer longer than the tile)
+    int gn_npt = 0;          // > 0: a windowed GroupNorm'd layer, finished by gn_pass_kernel<gn_npt> after the conv
     SplitPlan split{1, 0, 0};
     uint64_t xswz = 0;
 };
 
-// Does the residual conv ride in `op`'s launch at this batch?  (Needs the whole K in one block
-// and the sixth tap's weight rows in LDS.)
-inline bool fused_at(const HostModel& m, const ConvOp& op, int batch) {
-    if (!op.ride || !m.fuse_residual) return false;
-    const int cfg = choose_tile(m, op, batch);
-    if (cfg < 0) return false;
-    const TileCfg& t = kTiles[cfg];
-    if (t.KC < 16 || plan_split(m, op, cfg, batch).kslices != 1) return false;
-    const int kc = tile_kc(cfg, op.taps, op.x3, op.bdir);
-    return dad::conv_lds_floats(t.BM, t.BN, kc, op.taps, op.Lin, op.Lout, t.SK, false, op.taps + 1) *
+// Does the residual conv ride in `op`'s launch, given its tile and grid-level split?  (Needs the whole K in one
+// block and the sixth tap's weight rows in LDS.)  The one statement of the rule: a 1x1 residual conv is launched
+// on its own exactly where its carrier's LaunchGeom::fused is false (plan_forward).
+inline bool fused_at(const HostModel& m, const ConvOp& op, const LaunchGeom& g) {
+    if (!op.ride || !m.fuse_residual || g.cfg < 0) return false;
+    const TileCfg& t = kTiles[g.cfg];
+    if (t.KC < 16 || g.split.kslices != 1) return false;
+    return dad::conv_lds_floats(t.BM, t.BN, g.kc, op.taps, op.Lin, op.Lout, t.SK, false, op.taps + 1) *
                sizeof(float) <= dad::kLdsBytes;
+}
+// What a launch of `op` at this batch is made of: tile, K chunk, grid-level split-K, whether the residual conv
+// rides.  Scratch is sized from these alone, so a size does not depend on whether plan_launch accepts the launch.
+inline void choose_launch(const HostModel& m, const ConvOp& op, int batch, LaunchGeom& g) {
+    g = LaunchGeom();
+    g.cfg = choose_tile(m, op, batch);
+    if (g.cfg < 0) return;
+    g.kc = tile_kc(g.cfg, op.taps, op.x3, op.bdir);
+    g.split = plan_split(m, op, g.cfg, batch);
+    g.fused = fused_at(m, op, g);
 }
 
 // Which conv-GEMM instantiations exist.  This is the one statement of it: the registry of dad_lib.hip
@@ -1166,16 +1072,15 @@ constexpr int count_registered() {
 // 223 plain + 79 PADDED + 33 windowed (125 of them RAGGED).  Adding or dropping a kernel form changes this line.
 static_assert(count_registered() == 335, "the set of conv-GEMM kernels changed: kernel_registered");
 
-inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g) {
+inline int plan_launch(const HostModel& m, const ConvOp& op, int batch, LaunchGeom& g) {
+    choose_launch(m, op, batch, g);
     if ((long)batch * op.Lout * op.M >= (1L << 31) ||
         (long)batch * op.Lin * (op.cin0 + op.cin1) >= (1L << 31))
         return fail(DAD_E_INVALID, "batch %d too large: a layer's activation tensor exceeds 2^31 elements", batch);
-    g.cfg = choose_tile(m, op, batch);
     if (g.cfg < 0)
         return fail(DAD_E_INVALID, "no tile configuration for %s (M=%d, C/8=%d, L=%d)",
                     op.name.c_str(), op.M, op.cout / 8, op.Lout);
     const TileCfg& t = kTiles[g.cfg];
-    g.kc = tile_kc(g.cfg, op.taps, op.x3, op.bdir);
     const int cin = op.cin0 + op.cin1;
     g.ragged = (op.cin0 & 3) != 0 || (op.cin1 & 3) != 0 || op.cin0 % g.kc != 0 || cin % g.kc != 0;
     if (g.ragged && !(op.stride == 1 && (op.taps & 1) == 1))
@@ -1187,7 +1092,6 @@ inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g)
         return fail(DAD_E_INVALID, "no direct-B kernel for tile %d taps=%d stride=%d", g.cfg, op.taps, op.stride);
     if (op.x3 && !op.bdir && t.KC < 16)
         return fail(DAD_E_INVALID, "no split-f16 kernel for tile %d taps=%d stride=%d", g.cfg, op.taps, op.stride);
-    g.fused = fused_at(m, op, batch);
     if (g.fused && (op.x3 || op.bdir || op.kind != CONV_K5 || op.stride != 1))
         return fail(DAD_E_INVALID, "no fused-residual kernel for %s on tile %d", op.name.c_str(), g.cfg);
     if (op.cin_pad % g.kc != 0 && !g.ragged)
@@ -1202,6 +1106,12 @@ inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g)
     if (g.windowed && !op.norm.empty() && (long)(op.cout / 8) * op.Lout > kGnPassMaxPair)
         return fail(DAD_E_INVALID, "%s: GroupNorm pair of %ld elements (the pass holds %d)", op.name.c_str(),
                     (long)(op.cout / 8) * op.Lout, kGnPassMaxPair);
+    if (g.windowed && !op.norm.empty()) {
+        const long elems = (long)(op.cout / 8) * op.Lout, per = dad::GNP_THREADS * 4L;     // per: elements per float4 of every thread
+        if (op.kind != CONV_K5 || (op.cout / 8) % 4 != 0)
+            return fail(DAD_E_INVALID, "%s: no GroupNorm pass for %ld-element pairs", op.name.c_str(), elems);
+        for (g.gn_npt = 1; elems > g.gn_npt * per; g.gn_npt *= 2) {}
+    }
     g.threads = 64 * (t.BM / 32) * (t.BN / 32) * t.SK;
     g.lds_bytes = dad::conv_lds_floats(t.BM, t.BN, g.kc, op.taps, op.Lin, op.Lout, t.SK, op.bdir,
                                        op.taps + (g.fused ? 1 : 0)) * sizeof(float);
@@ -1211,7 +1121,6 @@ inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g)
     if (ntn > 65535) return fail(DAD_E_INVALID, "batch too large for one launch (%ld N tiles)", ntn);
     g.ntiles_n = (int)ntn;
     g.mtiles = op.M / t.BM;
-    g.split = plan_split(m, op, g.cfg, batch);
     if (g.split.kslices > 1 && (long)g.mtiles * g.ntiles_n > kMaxSplitTiles)
         return fail(DAD_E_INVALID, "%s: %ld tiles exceed the split-K ticket table", op.name.c_str(),
                     (long)g.mtiles * g.ntiles_n);
@@ -1240,44 +1149,6 @@ inline int plan_launch(HostModel& m, const ConvOp& op, int batch, LaunchGeom& g)
     return DAD_OK;
 }
 
-// dad_debug_backward_plan: which kernels one training step takes at batch B (layout: include/dad.h, DAD_BP_*).
-// Restates what dad_unet_forward_train and dad_unet_backward launch from the same planner calls they make.
-inline int backward_plan_report(const HostModel& m, int B, std::vector<int32_t>& r) {
-    TrainScratch ts;
-    const int rc = train_scratch(m, B, ts);
-    r.assign(DAD_BP_HEADER, 0);
-    r[DAD_BP_RECORD_INTS] = DAD_BP_REC_INTS;
-    size_t nw = 0;
-    auto conv = [&](const ConvOp& op, int at) {
-        const int cfg = choose_tile(m, op, B);
-        if (cfg >= 0) ++r[at + 2 * cfg + (plan_split(m, op, cfg, B).kslices > 1 ? 1 : 0)];
-    };
-    for (const ConvOp& op : m.tplan.convs)             // run_unet: a riding 1x1 residual conv is not launched
-        if (!(op.rider_of >= 0 && fused_at(m, m.tplan.convs[op.rider_of], B))) conv(op, DAD_BP_FWD);
-    for (const BwdStep& s : m.bsteps) {
-        if (s.kind == BK_DGRAD) conv(bwd_op(m, s), DAD_BP_DGRAD);
-        if (s.kind != BK_WGRAD) continue;
-        const WgradShape& sh = ts.wgrads[nw].sh;
-        const WgradGeom& g = ts.wgrads[nw++].g;
-        const int fullest = (std::min(g.sps, sh.B) + g.spc - 1) / g.spc;
-        const int last = (sh.B - (g.ksplit - 1) * g.sps + g.spc - 1) / g.spc;
-        const bool part = sh.B % g.spc != 0;
-        const int ti = (int)(std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) - std::begin(kWgradTaps));
-        ++r[DAD_BP_WGRADS];
-        r[DAD_BP_MULTI] += fullest > 1;
-        r[DAD_BP_MAX_CHUNKS] = std::max(r[DAD_BP_MAX_CHUNKS], fullest);
-        r[DAD_BP_MAX_KSPLIT] = std::max(r[DAD_BP_MAX_KSPLIT], g.ksplit);
-        r[DAD_BP_PART] += part;
-        r[DAD_BP_PART_MULTI] += part && last > 1;
-        r[DAD_BP_WINDOWED] += sh.wshift > 0;
-        ++r[DAD_BP_TILE + g.tile];
-        if (ti < (int)std::size(kWgradTaps)) ++r[DAD_BP_TAPS_TILE + 4 * ti + g.tile];
-        const int32_t rec[DAD_BP_REC_INTS] = {s.taps, g.tile, sh.wshift > 0, sh.B, g.spc, g.sps, g.ksplit, fullest, last};
-        r.insert(r.end(), rec, rec + DAD_BP_REC_INTS);
-    }
-    return rc;
-}
-
 // ------------------------------------------------------------------ small-batch (CC) plan
 // conv_cc.hpp: convs only produce partial sums, consumers finish them.  Decided per batch on the
 // host: which launches exist, their K slices, where their partial slabs live, and for every input
@@ -1298,6 +1169,8 @@ struct CcOp {
     bool wide = false;       // conv_ccw.hpp: weights streamed through registers, K slices of up to 1024 channels
     int slice_ch = 0, kslices = 0, ntiles = 0;
     int tile_rows = 32;      // GEMM rows per tile: 16 for layers of at most 16 positions (16x16x4 MFMAs)
+    bool big = false;        // an input arrives in more than CC_MAX_SLABS slabs (conv_cc's second round trip)
+    bool ride_in = false;    // an input's residual is a 1x1 conv still in pieces (conv_ccw's RIDE form)
     long oslab = 0, orslab = -1;       // float offsets into the CC slab region
     int out_rows = 0, out_cols = 0;
     size_t lds_bytes = 0;
@@ -1315,6 +1188,15 @@ struct CcPlan {
     std::string why;         // when !ok: which rule refused the plan (diagnostic)
 };
 inline CcPlan& refuse(CcPlan& P, const char* why) { P.why = why; return P; }
+// Which small-batch conv kernels exist: what add_cc / add_ccw of dad_lib.hip instantiate (`rows` per tile; `ride`: the
+// launch carries a riding 1x1 conv; conv_ccw has every form of `ride_in`).
+constexpr bool cc_kernel_exists(int taps, int stride, bool ride, bool wide, bool big, int rows, bool windowed) {
+    if ((rows != 16 && rows != 32) || (ride && !(taps == 5 && stride == 1))) return false;
+    const bool shape_ok = (taps == 5 && stride == 1) || (taps == 3 && stride == 2) || (taps == 2 && stride == 1);
+    if (wide) return !big && !windowed && (shape_ok || (taps == 1 && stride == 1));   // a wide conv takes at most CC_MAX_SLABS slabs
+    if (windowed) return taps == 5 && stride == 1 && !big && rows == 32;
+    return shape_ok;
+}
 
 inline CcPlan cc_plan(const HostModel& m, int batch) {
     CcPlan P;
@@ -1368,6 +1250,7 @@ inline CcPlan cc_plan(const HostModel& m, int batch) {
                 const CcOp& qo = P.ops[in->producer];
                 max_slabs_in = std::max(max_slabs_in, qo.kslices);
                 if (qo.res_kind >= 3) max_slabs_in = std::max(max_slabs_in, P.ops[qo.res_ride].kslices);
+                o.ride_in = o.ride_in || qo.res_kind >= 3;
                 if (!q.norm.empty()) {
                     need = std::max(need, q.cout / 8);
                     max_pair = std::max(max_pair, (long)(q.cout / 8) * op.Lin);
@@ -1446,16 +1329,11 @@ inline CcPlan cc_plan(const HostModel& m, int batch) {
         o.oslab = off;
         off += (long)o.kslices * o.out_rows * o.out_cols;
         if (op.ride) { o.orslab = off; off += (long)o.kslices * o.out_rows * o.out_cols; }
-        if (o.wide) {
-            o.lds_bytes = dad::ccw_lds_floats(slice, op.taps, op.Lin, op.Lout, o.tile_rows) * sizeof(float);
-        } else {
-            // the exchange tile needs 2 * 8 * 32 * 36 floats; operands XROWS + weight rows of slice + 4
-            const size_t xs = slice + 4;
-            const size_t k = (size_t)dad::cc_xrows(op.taps, op.Lin, op.Lout, o.tile_rows) * xs + (size_t)op.wtaps() * 32 * xs;
-            const size_t e = (size_t)2 * 8 * o.tile_rows * 36;
-            o.lds_bytes = std::max(k, e) * sizeof(float);
-        }
+        o.lds_bytes = (o.wide ? dad::ccw_lds_floats(slice, op.taps, op.Lin, op.Lout, o.tile_rows)
+                              : dad::cc_lds_floats(slice, op.taps, op.wtaps(), op.Lin, op.Lout, o.tile_rows)) * sizeof(float);
         if (o.lds_bytes > dad::kLdsBytes) return refuse(P, "a launch does not fit LDS");
+        o.big = max_slabs_in > dad::CC_MAX_SLABS;
+        if (!cc_kernel_exists(op.taps, op.stride, op.ride, o.wide, o.big, o.tile_rows, windowed)) return refuse(P, "a launch no small-batch kernel exists for");
         // how the output gets finished
         if (op.res == -2) o.res_kind = 1;
         else if (op.res >= 0) {
@@ -1486,12 +1364,221 @@ inline CcPlan cc_plan(const HostModel& m, int batch) {
     return P;
 }
 
-// activations, then whichever scratch the batch uses: split-K slabs or the CC partial-sum slabs
+// ------------------------------------------------------------------ one forward evaluation at a batch
+// Planning goes on after a refusal (the sizes are reported for such a batch too); the first one is what is returned.
+struct FirstRefusal {
+    int rc = DAD_OK;
+    std::string why;
+    void note(int r) { if (r != DAD_OK && rc == DAD_OK) { rc = r; why = g_err; } }
+    int done() const { return rc == DAD_OK ? DAD_OK : fail(rc, "%s", why.c_str()); }
+};
+// rows per sample of the external tensors (x, noise, guide, means): the horizon before zero-padding
+inline int traj_horizon(const HostModel& m) { return m.real_horizon > 0 ? m.real_horizon : m.cfg.horizon; }
+
+struct FwdLaunch {
+    int conv;                // index into the plan's convs
+    bool ok;                 // plan_launch accepted it
+    LaunchGeom g;
+};
+// Everything one denoiser evaluation launches at a batch, decided before its first launch: every entry point builds
+// it once per call (plan_forward) and replays it; the size queries, the plan report and the sanitizer harness read it.
+struct FwdPlan {
+    bool train = false;      // the launches of m.tplan (dad_unet_forward_train), else of m.plan
+    int batch = 0;
+    CcPlan cc;               // cc.ok: the evaluation takes the small-batch kernels, `launches` stays empty
+    std::vector<FwdLaunch> launches;     // else the conv-GEMM launches in order; a 1x1 residual conv that rides at
+                                         // this batch (its carrier's g.fused) is absent
+    unsigned final_gx = 1, final_gy = 1; // final_cc_kernel / final_posterior_kernel
+    size_t final_lds = 0;
+    size_t bytes = 0;        // activations + the scratch behind them: split-K slabs or the small-batch slabs,
+                             // whichever is larger (a small batch with per-row timesteps runs the batch kernels)
+};
+// `small_ok`: the call may take the small-batch kernels (one shared timestep, not training).  `f` is filled even
+// when a launch is refused, and the refusal returned: dad_workspace_bytes / dad_train_workspace_bytes report the
+// sizes, the launching entry points refuse before their first launch.
+inline int plan_forward(const HostModel& m, bool train, int batch, bool small_ok, FwdPlan& f) {
+    const Plan& plan = train ? m.tplan : m.plan;
+    const dad_cfg& c = m.cfg;
+    FirstRefusal first;
+    f = FwdPlan();
+    f.train = train; f.batch = batch;
+    long scratch = 0;
+    if (!train) {
+        CcPlan cc = cc_plan(m, batch);
+        if (cc.ok) scratch = cc.slab_floats;
+        if (cc.ok && small_ok) f.cc = std::move(cc);
+    }
+    std::vector<char> carries(plan.convs.size(), 0);
+    for (size_t i = 0; i < plan.convs.size(); ++i) {
+        const ConvOp& op = plan.convs[i];
+        FwdLaunch l{(int)i, true, LaunchGeom()};
+        const bool listed = !f.cc.ok && !(op.rider_of >= 0 && carries[op.rider_of]);
+        if (listed) { const int rc = plan_launch(m, op, batch, l.g); l.ok = rc == DAD_OK; first.note(rc); }
+        else choose_launch(m, op, batch, l.g);         // (its split-K slab still counts: sizes are one rule for all calls)
+        carries[i] = l.g.fused;
+        scratch = std::max(scratch, l.g.split.slab_floats);
+        if (listed) f.launches.push_back(l);
+    }
+    f.bytes = ((size_t)plan.floats_per_sample * (size_t)batch + (size_t)scratch) * sizeof(float);
+    if (f.cc.ok) {
+        // one block per (sample, group of output columns): enough columns per block to occupy its
+        // 512 threads once, as long as the grid stays within one wave of blocks
+        const int want = (c.horizon * c.transition_dim + dad::CC_THREADS - 1) / dad::CC_THREADS;
+        f.final_gx = (unsigned)batch;
+        f.final_gy = (unsigned)std::max(1, std::min({want, c.transition_dim, 256 / std::max(batch, 1)}));
+        f.final_lds = dad::final_cc_lds_floats(c.transition_dim, c.dim, c.horizon) * sizeof(float);
+    } else {
+        // columns of the transition are spread over gridDim.y when the row tiles alone leave CUs idle
+        // (a block stages only the weight rows of its own columns), and further until a block fits LDS
+        const long row_tiles = ((long)batch * traj_horizon(m) + dad::FINAL_COLS - 1) / dad::FINAL_COLS;
+        const long col_groups = (c.transition_dim + 256 / dad::FINAL_COLS - 1) / (256 / dad::FINAL_COLS);
+        long gy = std::max(1L, std::min(col_groups, 512 / row_tiles));
+        while (gy < col_groups && dad::final_lds_floats(c.transition_dim, c.dim, (int)gy) * sizeof(float) > dad::kLdsBytes) ++gy;
+        f.final_gx = (unsigned)row_tiles; f.final_gy = (unsigned)gy;
+        f.final_lds = dad::final_lds_floats(c.transition_dim, c.dim, (int)gy) * sizeof(float);
+    }
+    if (f.final_lds > dad::kLdsBytes)
+        first.note(fail(DAD_E_INVALID, "final 1x1 conv does not fit LDS (td=%d, dim=%d)", c.transition_dim, c.dim));
+    return first.done();
+}
 inline size_t workspace_bytes(const HostModel& m, int batch) {
-    const CcPlan cc = cc_plan(m, batch);
-    // (both: a small batch with per-row timesteps still runs the batch-256 kernels)
-    const size_t scratch = std::max(cc.ok ? (size_t)cc.slab_floats : 0, (size_t)slab_floats_for(m, batch));
-    return ((size_t)m.plan.floats_per_sample * (size_t)batch + scratch) * sizeof(float);
+    FwdPlan f;
+    plan_forward(m, false, batch, true, f);
+    return f.bytes;
+}
+
+// ------------------------------------------------------------------ backward pass: per-batch geometry
+// conv_wgrad instantiations exist for these tap counts (the list of dad_lib.hip, wgrad_kernels, is built from them)
+constexpr int kWgradTaps[] = {1, 3, 4, 5, 7};
+struct WgradGeom { int spc, ksplit, sps, tile, tm, tn; unsigned gx, gy; size_t lds; };
+// Layers longer than a chunk stages (more than 128 rows of G or Z per sample: horizons 256 / 512) run the windowed
+// kernel over windows of kWgradWindow rows of G (and the matching rows of Z) as if they were samples.
+constexpr int kWgradWindow = 64;
+struct WgradShape { int B, Lg, Lz, wshift; };
+inline WgradShape wgrad_shape(int B, int Lg, int Lz) {
+    if (Lg <= 128 && Lz <= 128) return {B, Lg, Lz, 0};
+    const int nw = Lg / kWgradWindow;
+    return {B * nw, kWgradWindow, Lz / nw, ilog2(nw)};
+}
+// Block tile: the largest of 64 x 64 / 64 x 32 / 32 x 32 that still gives the layer 32 tiles (the smaller tiles
+// split K inside the block instead of over the grid: fewer partial slabs to write and add); the batch is then split
+// over blockIdx.z until `target` blocks exist (one block = 8 waves = two per SIMD).
+inline WgradGeom wgrad_geom(int M, int Ctot, int B, int Lg, int Lz, int taps, int pad, int target, bool ragged) {
+    WgradGeom g{};
+    g.spc = std::max(1, dad::WG_ROWS / Lg);
+    while (g.spc > 1 && g.spc * dad::wgrad_segz(Lz, taps, pad) > dad::WG_MAX_ZROWS) g.spc /= 2;
+    static const int tms[3] = {2, 2, 1}, tns[3] = {2, 1, 1};
+    long tiles = 0;
+    for (g.tile = ragged ? 2 : 0; g.tile < 3; ++g.tile) {
+        g.tm = tms[g.tile]; g.tn = tns[g.tile];
+        g.gx = (unsigned)((M + 32 * g.tm - 1) / (32 * g.tm));
+        g.gy = (unsigned)((Ctot + 32 * g.tn - 1) / (32 * g.tn));
+        tiles = (long)g.gx * g.gy;
+        const int kgroups = 8 / (g.tm * g.tn);
+        if ((tiles >= 32 && (g.spc * Lg) % (4 * kgroups) == 0) || g.tile == 2) break;
+    }
+    const int chunks = (B + g.spc - 1) / g.spc;
+    int want = (int)std::max(1L, target / tiles);
+    want = std::min(want, chunks);
+    g.sps = (chunks + want - 1) / want * g.spc;                // samples per split: whole chunks
+    g.ksplit = (B + g.sps - 1) / g.sps;
+    g.lds = dad::wgrad_lds_floats(g.spc, Lg, Lz, taps, pad, g.tm, g.tn) * sizeof(float);
+    if (ragged) g.tile = 3;
+    return g;
+}
+
+// Scratch of dad_unet_backward, in floats: gradient mirror of the training plan | per-sample partial sums
+// | wgrad split slabs | padded d x | staging of a down-sampling conv's data gradient | split-K slabs;
+// and the geometry of every weight-gradient and every data-gradient step of m.bsteps, each in order.
+struct TrainScratch {
+    long mirror = 0, part = 0, wslab = 0, dxpad = 0, tmp = 0, bslab = 0, total = 0;
+    struct Wgrad { WgradShape sh; WgradGeom g; };
+    struct Dgrad { bool ok; LaunchGeom g; };       // ok: plan_launch accepted it
+    std::vector<Wgrad> wgrads;
+    std::vector<Dgrad> dgrads;
+};
+inline const ConvOp& bwd_op(const HostModel& m, const BwdStep& s) { return s.conv < 0 ? m.bfinal : m.bconvs[s.conv].op[s.sub]; }
+// Everything of the backward pass that depends on the batch, with every check of its launches.  `t` is filled even
+// when a check fails: dad_train_workspace_bytes reports the sizes, dad_unet_backward refuses before its first launch.
+inline int train_scratch(const HostModel& m, int B, TrainScratch& t) {
+    const int H = m.cfg.horizon, td = m.cfg.transition_dim;
+    FirstRefusal first;
+    t = TrainScratch();
+    t.mirror = m.tplan.floats_per_sample * (long)B;
+    for (const ConvOp& f : m.tplan.convs) t.part += (f.norm.empty() ? 1L : 3L) * B * round_up(f.cout, 4);
+    t.part += (long)B * round_up(td, 4);
+    for (const BwdStep& s : m.bsteps) {
+        if (s.kind == BK_WGRAD) {
+            const WgradShape sh = wgrad_shape(B, s.Lg, s.Lz);             // windows of long layers run as samples
+            const bool ragged = ((s.M | s.C0 | s.C1) & 3) != 0;          // rows that are not whole aligned float4s
+            const WgradGeom g = wgrad_geom(s.M, s.C0 + s.C1, sh.B, sh.Lg, sh.Lz, s.taps, s.pad, m.wgrad_blocks, ragged);
+            const long numel = (long)s.M * (s.C0 + s.C1) * s.taps;
+            const int kgroups = 8 / (g.tm * g.tn);
+            if (g.lds > dad::kLdsBytes || g.spc * sh.Lg > dad::WG_MAX_GROWS ||
+                g.spc * dad::wgrad_segz(sh.Lz, s.taps, s.pad) > dad::WG_MAX_ZROWS || (g.spc * sh.Lg) % (4 * kgroups) != 0)
+                first.note(fail(DAD_E_INVALID, "wgrad: a chunk of %d samples x %d rows does not fit the kernel's staging", g.spc, sh.Lz));
+            if (std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) == std::end(kWgradTaps))
+                first.note(fail(DAD_E_INVALID, "wgrad: %d taps", s.taps));
+            if (g.ksplit > 1 && numel % 4 != 0)
+                first.note(fail(DAD_E_INVALID, "wgrad: %ld gradient elements (not a multiple of 4)", numel));
+            if (g.ksplit > 1) t.wslab = std::max(t.wslab, (long)g.ksplit * numel);
+            t.wgrads.push_back({sh, g});
+        } else if (s.kind == BK_DGRAD) {
+            const ConvOp& op = bwd_op(m, s);
+            TrainScratch::Dgrad d{};
+            const int rc = plan_launch(m, op, B, d.g);
+            d.ok = rc == DAD_OK;
+            first.note(rc);
+            t.bslab = std::max(t.bslab, d.g.split.slab_floats);
+            t.dgrads.push_back(d);
+            if (op.kind == CONV_UP) t.tmp = std::max(t.tmp, (long)B * s.n);
+        }
+    }
+    t.dxpad = (long)B * H * round_up(td, 32);
+    if (m.real_horizon > 0 && m.real_horizon != H) t.dxpad += 2L * B * H * round_up(td, 4);      // zero-padded copies of x and d out
+    auto al = [](long v) { return (v + 63) / 64 * 64; };
+    t.mirror = al(t.mirror); t.part = al(t.part); t.wslab = al(t.wslab); t.dxpad = al(t.dxpad);
+    t.tmp = al(t.tmp); t.bslab = al(t.bslab);
+    t.total = t.mirror + t.part + t.wslab + t.dxpad + t.tmp + t.bslab;
+    if (m.bpart * B > t.part)
+        first.note(fail(DAD_E_WORKSPACE, "backward: partial sums overran their region (%ld > %ld floats)", m.bpart * B, t.part));
+    return first.done();
+}
+
+// dad_debug_backward_plan: which kernels one training step takes at batch B (layout: include/dad.h, DAD_BP_*),
+// read from what dad_unet_forward_train and dad_unet_backward replay: plan_forward of the training plan, train_scratch.
+inline int backward_plan_report(const HostModel& m, int B, std::vector<int32_t>& r) {
+    TrainScratch ts;
+    FwdPlan fwd;
+    plan_forward(m, true, B, false, fwd);
+    const int rc = train_scratch(m, B, ts);
+    r.assign(DAD_BP_HEADER, 0);
+    r[DAD_BP_RECORD_INTS] = DAD_BP_REC_INTS;
+    size_t nw = 0;
+    auto conv = [&](const LaunchGeom& g, int at) { if (g.cfg >= 0) ++r[at + 2 * g.cfg + (g.split.kslices > 1 ? 1 : 0)]; };
+    for (const FwdLaunch& l : fwd.launches) conv(l.g, DAD_BP_FWD);
+    for (const TrainScratch::Dgrad& d : ts.dgrads) conv(d.g, DAD_BP_DGRAD);
+    for (const BwdStep& s : m.bsteps) {
+        if (s.kind != BK_WGRAD) continue;
+        const WgradShape& sh = ts.wgrads[nw].sh;
+        const WgradGeom& g = ts.wgrads[nw++].g;
+        const int fullest = (std::min(g.sps, sh.B) + g.spc - 1) / g.spc;
+        const int last = (sh.B - (g.ksplit - 1) * g.sps + g.spc - 1) / g.spc;
+        const bool part = sh.B % g.spc != 0;
+        const int ti = (int)(std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) - std::begin(kWgradTaps));
+        ++r[DAD_BP_WGRADS];
+        r[DAD_BP_MULTI] += fullest > 1;
+        r[DAD_BP_MAX_CHUNKS] = std::max(r[DAD_BP_MAX_CHUNKS], fullest);
+        r[DAD_BP_MAX_KSPLIT] = std::max(r[DAD_BP_MAX_KSPLIT], g.ksplit);
+        r[DAD_BP_PART] += part;
+        r[DAD_BP_PART_MULTI] += part && last > 1;
+        r[DAD_BP_WINDOWED] += sh.wshift > 0;
+        ++r[DAD_BP_TILE + g.tile];
+        if (ti < (int)std::size(kWgradTaps)) ++r[DAD_BP_TAPS_TILE + 4 * ti + g.tile];
+        const int32_t rec[DAD_BP_REC_INTS] = {s.taps, g.tile, sh.wshift > 0, sh.B, g.spc, g.sps, g.ksplit, fullest, last};
+        r.insert(r.end(), rec, rec + DAD_BP_REC_INTS);
+    }
+    return rc;
 }
 
 // Bytes the parameter arena must hold: the parameter copies, the per-timestep tables, the zero row of the

@@ -92,17 +92,7 @@ struct FinalParams {
                                           // (graph replays take a fresh seed without re-capture)
 };
 
-constexpr int FINAL_COLS = 32;   // trajectory positions per block (256 blocks at B*H = 8192)
-// a block keeps the weight rows of ITS output columns (gy = gridDim.y column groups), the biases and
-// the activation tile
-__host__ __device__ inline int final_rows_local(int td, int gy) {
-    constexpr int JG = 256 / FINAL_COLS;
-    const int col_groups = (td + JG - 1) / JG;
-    return (col_groups + gy - 1) / gy * JG;
-}
-__host__ __device__ inline size_t final_lds_floats(int td, int dim, int gy) {
-    return (size_t)final_rows_local(td, gy) * dim + ((td + 3) & ~3) + (size_t)FINAL_COLS * (dim + 4);
-}
+// (FINAL_COLS, final_rows_local, final_lds_floats: conv_shapes.hpp)
 
 // K output columns j0, j0 + jstep, ... of one position: dot products of the activation row with K
 // weight rows (local rows of the block, JG apart), every read of the activation row shared.

@@ -282,6 +282,57 @@ static void check_arch(const Arch& a, int precision) {
         CHECK(arena <= arena_bytes_needed(m, table), "arena estimate %zu < %zu", arena_bytes_needed(m, table), arena);
     }
 
+    // what the kernels assume of an accepted launch (`floats_per_sample`: activations in front of the split-K slabs,
+    // `ws`: bytes the size query reports for the batch)
+    auto check_geom = [&](const ConvOp& op, const LaunchGeom& g, int B, long floats_per_sample, size_t ws) {
+            const TileCfg& t = kTiles[g.cfg];
+            CHECK(tile_valid(op, g.cfg), "%s: invalid tile %d", op.name.c_str(), g.cfg);
+            CHECK(g.threads == 64 * (t.BM / 32) * (t.BN / 32) * t.SK && g.threads <= 1024, "threads %d", g.threads);
+            CHECK(g.lds_bytes <= dad::kLdsBytes, "%s: LDS %zu", op.name.c_str(), g.lds_bytes);
+            CHECK(g.kc % (op.x3 ? 16 : 8) == 0 && (g.kc / (op.x3 ? 16 : 8)) % t.SK == 0, "%s: K chunk %d", op.name.c_str(), g.kc);
+            const long tiles = (long)g.mtiles * g.ntiles_n;
+            CHECK((long)g.gx * g.gy * g.gz == tiles * g.split.kslices, "%s: grid %u %u %u vs %ld tiles x %d",
+                  op.name.c_str(), g.gx, g.gy, g.gz, tiles, g.split.kslices);
+            CHECK(g.gy <= 65535 && g.gz <= 65535, "grid dims");
+            CHECK(g.ntiles_n * (t.BN / op.Lout) >= B, "%s: N tiles do not cover the batch", op.name.c_str());
+            if (g.split.kslices > 1) {
+                CHECK(tiles <= kMaxSplitTiles, "ticket table");
+                CHECK(!g.fused, "%s: ride under grid split-K", op.name.c_str());
+                const int nchunks = (op.cin0 + op.cin1 + g.kc - 1) / g.kc;
+                CHECK((g.split.kslices - 1) * g.split.chunks_per_slice < nchunks &&
+                      g.split.kslices * g.split.chunks_per_slice >= nchunks, "%s: K slices", op.name.c_str());
+                const size_t slab_end = ((size_t)floats_per_sample * B + (size_t)g.split.slab_floats) * sizeof(float);
+                CHECK(slab_end <= ws, "%s B=%d: slab beyond the workspace", op.name.c_str(), B);
+            }
+            if (g.xcd_gn > 0) {
+                const int gm = 8 / g.xcd_gn;
+                CHECK(g.mtiles % gm == 0 && g.ntiles_n % g.xcd_gn == 0 && (1 << g.xcd_mts) == g.mtiles / gm &&
+                      g.xcd_ntn == g.ntiles_n / g.xcd_gn, "%s: XCD order", op.name.c_str());
+                // the kernel's decode of a linear block id must be a bijection onto tiles
+                std::vector<char> hit((size_t)tiles, 0);
+                for (long wg = 0; wg < tiles; ++wg) {
+                    const int cc = (int)(wg & 7), j = (int)(wg >> 3);
+                    const int im = cc / g.xcd_gn, in = cc - im * g.xcd_gn;
+                    const int mt = (im << g.xcd_mts) + (j & ((1 << g.xcd_mts) - 1));
+                    const int nt = in * g.xcd_ntn + (j >> g.xcd_mts);
+                    CHECK(mt < g.mtiles && nt < g.ntiles_n, "%s: XCD decode out of range", op.name.c_str());
+                    if (mt < g.mtiles && nt < g.ntiles_n) hit[(size_t)mt * g.ntiles_n + nt]++;
+                }
+                for (char h : hit) CHECK(h == 1, "%s: XCD decode not a bijection", op.name.c_str());
+            }
+            if (g.xswz != 0) {
+                const int pad = op.taps / 2, kp4 = (g.kc + 4) / 4;
+                CHECK(xswz_conflict_free(g.xswz, op.Lout, op.stride, pad, kp4, t.BN), "%s: slot shifts conflict", op.name.c_str());
+                const int S = t.BN / op.Lout;
+                for (int s = 0; s + 1 < S; ++s) {
+                    const int d0 = (int)((g.xswz >> (4 * s)) & 15), d1 = (int)((g.xswz >> (4 * (s + 1))) & 15);
+                    CHECK(d0 - d1 <= pad * kp4, "%s: shift pushes a sample onto its neighbour", op.name.c_str());
+                }
+                // the stage was sized with kXSwzPad floats of slack for shifts of at most 15 slots
+                CHECK(15 * 4 <= dad::kXSwzPad, "slot shift slack");
+            }
+            if (g.fused) CHECK(op.ride && op.kind == CONV_K5 && (op.taps & 1) && op.stride == 1 && !op.x3 && !op.bdir, "%s: ride", op.name.c_str());
+    };
     // launches: every batch size, every forced tile, with and without split-K / fusion
     const int batches[] = {1, 2, 3, 5, 8, 13, 31, 33, 64, 100, 128, 256, 257, 1024, 2048};
     long launches = 0;
@@ -302,54 +353,51 @@ static void check_arch(const Arch& a, int precision) {
                         continue;
                     }
                     ++launches;
-                    const TileCfg& t = kTiles[g.cfg];
-                    CHECK(tile_valid(op, g.cfg), "%s: invalid tile %d", op.name.c_str(), g.cfg);
-                    CHECK(g.threads == 64 * (t.BM / 32) * (t.BN / 32) * t.SK && g.threads <= 1024, "threads %d", g.threads);
-                    CHECK(g.lds_bytes <= dad::kLdsBytes, "%s: LDS %zu", op.name.c_str(), g.lds_bytes);
-                    CHECK(g.kc % (op.x3 ? 16 : 8) == 0 && (g.kc / (op.x3 ? 16 : 8)) % t.SK == 0, "%s: K chunk %d", op.name.c_str(), g.kc);
-                    const long tiles = (long)g.mtiles * g.ntiles_n;
-                    CHECK((long)g.gx * g.gy * g.gz == tiles * g.split.kslices, "%s: grid %u %u %u vs %ld tiles x %d",
-                          op.name.c_str(), g.gx, g.gy, g.gz, tiles, g.split.kslices);
-                    CHECK(g.gy <= 65535 && g.gz <= 65535, "grid dims");
-                    CHECK(g.ntiles_n * (t.BN / op.Lout) >= B, "%s: N tiles do not cover the batch", op.name.c_str());
-                    if (g.split.kslices > 1) {
-                        CHECK(tiles <= kMaxSplitTiles, "ticket table");
-                        CHECK(!g.fused, "%s: ride under grid split-K", op.name.c_str());
-                        const int nchunks = (op.cin0 + op.cin1 + g.kc - 1) / g.kc;
-                        CHECK((g.split.kslices - 1) * g.split.chunks_per_slice < nchunks &&
-                              g.split.kslices * g.split.chunks_per_slice >= nchunks, "%s: K slices", op.name.c_str());
-                        const size_t slab_end = ((size_t)P.floats_per_sample * B + (size_t)g.split.slab_floats) * sizeof(float);
-                        CHECK(slab_end <= ws, "%s B=%d: slab beyond the workspace", op.name.c_str(), B);
-                    }
-                    if (g.xcd_gn > 0) {
-                        const int gm = 8 / g.xcd_gn;
-                        CHECK(g.mtiles % gm == 0 && g.ntiles_n % g.xcd_gn == 0 && (1 << g.xcd_mts) == g.mtiles / gm &&
-                              g.xcd_ntn == g.ntiles_n / g.xcd_gn, "%s: XCD order", op.name.c_str());
-                        // the kernel's decode of a linear block id must be a bijection onto tiles
-                        std::vector<char> hit((size_t)tiles, 0);
-                        for (long wg = 0; wg < tiles; ++wg) {
-                            const int cc = (int)(wg & 7), j = (int)(wg >> 3);
-                            const int im = cc / g.xcd_gn, in = cc - im * g.xcd_gn;
-                            const int mt = (im << g.xcd_mts) + (j & ((1 << g.xcd_mts) - 1));
-                            const int nt = in * g.xcd_ntn + (j >> g.xcd_mts);
-                            CHECK(mt < g.mtiles && nt < g.ntiles_n, "%s: XCD decode out of range", op.name.c_str());
-                            if (mt < g.mtiles && nt < g.ntiles_n) hit[(size_t)mt * g.ntiles_n + nt]++;
-                        }
-                        for (char h : hit) CHECK(h == 1, "%s: XCD decode not a bijection", op.name.c_str());
-                    }
-                    if (g.xswz != 0) {
-                        const int pad = op.taps / 2, kp4 = (g.kc + 4) / 4;
-                        CHECK(xswz_conflict_free(g.xswz, op.Lout, op.stride, pad, kp4, t.BN), "%s: slot shifts conflict", op.name.c_str());
-                        const int S = t.BN / op.Lout;
-                        for (int s = 0; s + 1 < S; ++s) {
-                            const int d0 = (int)((g.xswz >> (4 * s)) & 15), d1 = (int)((g.xswz >> (4 * (s + 1))) & 15);
-                            CHECK(d0 - d1 <= pad * kp4, "%s: shift pushes a sample onto its neighbour", op.name.c_str());
-                        }
-                        // the stage was sized with kXSwzPad floats of slack for shifts of at most 15 slots
-                        CHECK(15 * 4 <= dad::kXSwzPad, "slot shift slack");
-                    }
-                    if (g.fused) CHECK(op.ride && op.kind == CONV_K5 && (op.taps & 1) && op.stride == 1 && !op.x3 && !op.bdir, "%s: ride", op.name.c_str());
+                    check_geom(op, g, B, P.floats_per_sample, ws);
                 }
+                // the forward description the entry points replay (plan_forward): the plan's convs minus exactly the
+                // riders whose carrier is fused, every accepted geometry as checked above, a GroupNorm pass where the
+                // launch is windowed and normalised and nowhere else, the slabs inside the size the query reports
+                FwdPlan f;
+                rc = plan_forward(m, false, B, false, f);
+                CHECK(rc == DAD_OK || force >= 0, "B=%d: %s", B, g_err);
+                CHECK(f.bytes == ws && !f.cc.ok && !f.train && f.batch == B, "B=%d: description of another call (%zu bytes, the query says %zu)", B, f.bytes, ws);
+                CHECK(workspace_bytes(m, B) == ws, "B=%d: the size query depends on who asks", B);
+                std::vector<int> at(P.convs.size(), -1);         // conv -> its place in the list
+                bool all_ok = true;
+                for (size_t k = 0; k < f.launches.size(); ++k) {
+                    const FwdLaunch& l = f.launches[k];
+                    CHECK(l.conv >= 0 && l.conv < (int)P.convs.size() && (k == 0 || l.conv > f.launches[k - 1].conv), "B=%d: launch %zu is conv %d", B, k, l.conv);
+                    if (l.conv < 0 || l.conv >= (int)P.convs.size()) continue;
+                    at[l.conv] = (int)k;
+                    const ConvOp& op = P.convs[l.conv];
+                    LaunchGeom g;
+                    CHECK((plan_launch(m, op, B, g) == DAD_OK) == l.ok, "%s B=%d: the description disagrees with plan_launch", op.name.c_str(), B);
+                    all_ok = all_ok && l.ok;
+                    if (l.ok) {
+                        check_geom(op, l.g, B, P.floats_per_sample, ws);
+                        const bool pass = l.g.windowed && !op.norm.empty();
+                        CHECK((l.g.gn_npt > 0) == pass, "%s B=%d: GroupNorm pass %d on a %s launch", op.name.c_str(), B, l.g.gn_npt, pass ? "windowed, normalised" : "plain");
+                        if (pass) {
+                            const long pair = (long)(op.cout / 8) * op.Lout, per = dad::GNP_THREADS * 4L;
+                            CHECK((l.g.gn_npt & (l.g.gn_npt - 1)) == 0 && l.g.gn_npt <= dad::kGnPassMaxNpt && pair <= l.g.gn_npt * per &&
+                                  (l.g.gn_npt == 1 || pair > l.g.gn_npt / 2 * per) && (op.cout / 8) % 4 == 0,
+                                  "%s B=%d: gn_pass_kernel<%d> for pairs of %ld elements", op.name.c_str(), B, l.g.gn_npt, pair);
+                        }
+                    }
+                    // (refused or not: its slab is inside the reported size)
+                    CHECK(((size_t)P.floats_per_sample * B + (size_t)l.g.split.slab_floats) * sizeof(float) <= ws, "%s B=%d: slab beyond the workspace", op.name.c_str(), B);
+                }
+                CHECK((rc == DAD_OK) == all_ok, "B=%d: the description's refusal is not that of its launches", B);
+                for (size_t i = 0; i < P.convs.size(); ++i) {
+                    const ConvOp& op = P.convs[i];
+                    const bool rides = op.rider_of >= 0 && at[op.rider_of] >= 0 && f.launches[at[op.rider_of]].g.fused;
+                    CHECK((at[i] < 0) == rides, "%s B=%d: %s, its carrier is %sfused", op.name.c_str(), B, at[i] < 0 ? "not listed" : "listed", rides ? "" : "not ");
+                    if (at[i] >= 0 && f.launches[at[i]].g.fused)
+                        CHECK(i + 1 < P.convs.size() && P.convs[i + 1].rider_of == (int)i, "%s B=%d: fused without a rider", op.name.c_str(), B);
+                }
+                CHECK(f.final_lds <= dad::kLdsBytes && f.final_gx >= 1 && f.final_gy >= 1 && f.final_gy <= 65535 &&
+                      (long)f.final_gx * dad::FINAL_COLS >= (long)B * traj_horizon(m), "B=%d: final launch %u x %u, %zu bytes", B, f.final_gx, f.final_gy, f.final_lds);
             }
         }
     // small-batch (consumer-combine) plans: slabs disjoint and inside the workspace, inputs finished
@@ -362,6 +410,11 @@ static void check_arch(const Arch& a, int precision) {
         ++cc_plans;
         CHECK(precision == DAD_PREC_FP32 && (long)B * c.horizon <= m.cc_max_rows, "CC plan outside its domain");
         CHECK(workspace_bytes(m, B) >= ((size_t)P.floats_per_sample * B + (size_t)cc.slab_floats) * sizeof(float), "CC workspace");
+        {   // the description of a call that takes these kernels holds this plan and no conv-GEMM launch
+            FwdPlan f;
+            CHECK(plan_forward(m, false, B, true, f) == DAD_OK && f.cc.ok && f.launches.empty() && f.bytes == workspace_bytes(m, B) &&
+                  f.cc.slab_floats == cc.slab_floats && f.final_gx == (unsigned)B && f.final_lds <= dad::kLdsBytes, "B=%d: small-batch description", B);
+        }
         std::vector<std::pair<long, long>> spans;
         std::vector<char> finished(P.convs.size(), 0);
         for (size_t i = 0; i < P.convs.size(); ++i) {
@@ -537,6 +590,28 @@ static void check_arch(const Arch& a, int precision) {
             TrainScratch ts;
             rc = train_scratch(m, B, ts);
             CHECK(rc == DAD_OK, "backward geometry B=%d: %s", B, g_err);
+            {   // the data-gradient geometries dad_unet_backward hands to its launches: a direct plan_launch of the same op
+                size_t nd = 0;
+                for (const BwdStep& s : m.bsteps) {
+                    if (s.kind != BK_DGRAD) continue;
+                    CHECK(nd < ts.dgrads.size(), "B=%d: data-gradient geometries missing", B);
+                    if (nd >= ts.dgrads.size()) break;
+                    const TrainScratch::Dgrad& d = ts.dgrads[nd++];
+                    LaunchGeom g;
+                    const int r = plan_launch(m, bwd_op(m, s), B, g);
+                    CHECK((r == DAD_OK) == d.ok && std::memcmp(&g.split, &d.g.split, sizeof(SplitPlan)) == 0 && g.cfg == d.g.cfg && g.kc == d.g.kc &&
+                          g.ragged == d.g.ragged && g.threads == d.g.threads && g.lds_bytes == d.g.lds_bytes && g.ntiles_n == d.g.ntiles_n &&
+                          g.mtiles == d.g.mtiles && g.gx == d.g.gx && g.gy == d.g.gy && g.gz == d.g.gz && g.xcd_gn == d.g.xcd_gn &&
+                          g.xcd_mts == d.g.xcd_mts && g.xcd_ntn == d.g.xcd_ntn && g.fused == d.g.fused && g.padded == d.g.padded &&
+                          g.windowed == d.g.windowed && g.gn_npt == d.g.gn_npt && g.xswz == d.g.xswz,
+                          "%s B=%d: stored data-gradient geometry differs from plan_launch", bwd_op(m, s).name.c_str(), B);
+                    if (d.ok) {
+                        check_geom(bwd_op(m, s), d.g, B, 0, (size_t)ts.bslab * sizeof(float));
+                        CHECK(d.g.gn_npt == 0 && !d.g.fused, "%s B=%d: a data gradient with a GroupNorm pass or a ride", bwd_op(m, s).name.c_str(), B);
+                    }
+                }
+                CHECK(nd == ts.dgrads.size(), "B=%d: %zu data-gradient geometries for %zu steps", B, ts.dgrads.size(), nd);
+            }
             std::vector<int32_t> report;                  // dad_debug_backward_plan: what the tests prove their path with
             CHECK(backward_plan_report(m, B, report) == rc, "B=%d: the plan report disagrees about the batch", B);
             CHECK(report.size() == DAD_BP_HEADER + ts.wgrads.size() * DAD_BP_REC_INTS && report[DAD_BP_WGRADS] == (int)ts.wgrads.size(),
