@@ -102,6 +102,18 @@ ABI = {
     "dad_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.POINTER(C.c_void_p), C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dad_model_load_train_schedule": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "dad_train_time_grad_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "dad_train_time_grad_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]),
+    "dad_train_objective_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t),
+                                                      C.POINTER(C.c_size_t)]),
+    "dad_train_objective_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dad_train_objective_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+                                               C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dad_debug_objective_offsets": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "dad_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "dad_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double)]),
@@ -157,6 +169,7 @@ def _require_device(t: torch.Tensor, name: str) -> None:
 
 
 PRECISIONS = {"fp32": 0, "f16x3": 1}      # DAD_PREC_* of include/dad.h
+LOSS_TYPES = {"l1": 1, "l2": 2}           # DAD_LOSS_* of include/dad.h
 TABLES = {"sinusoid": 0, "time_mlp": 1, "blocks": 2}      # DAD_TABLE_* of include/dad.h
 
 
@@ -551,14 +564,121 @@ class HipEngine:
             grads = real.gather(flat)
         return d_x, d_temb, grads
 
+    # ------------------------------------------------------------------ fused training objective
+    def bind_train_schedule(self, sqrt_ac: torch.Tensor, sqrt_1m_ac: torch.Tensor) -> None:
+        """Hand over the two schedule vectors q_sample reads (dad_model_load_train_schedule); a no-op while the
+        same buffers are bound."""
+        sig = (sqrt_ac.data_ptr(), sqrt_ac._version, sqrt_1m_ac.data_ptr(), sqrt_1m_ac._version)
+        if getattr(self, "_train_sched_sig", None) == sig:
+            return
+        a = sqrt_ac.detach().to("cpu", torch.float32).contiguous()
+        b = sqrt_1m_ac.detach().to("cpu", torch.float32).contiguous()
+        if a.numel() != self.n_timesteps or b.numel() != self.n_timesteps:
+            raise ValueError(f"training schedule has {a.numel()} / {b.numel()} entries, expected {self.n_timesteps}")
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_model_load_train_schedule(self._h, a.data_ptr(), b.data_ptr(), self.n_timesteps))
+        self._train_sched_sig = sig
+
+    def time_grad_layout(self):
+        """[(time-MLP key, offset in floats, numel)] of the time gradients' own flat buffer and its length."""
+        cached = getattr(self, "_time_grad_layout", None)
+        if cached is not None:
+            return cached
+        n, total = C.c_int32(), C.c_int64()
+        _check(self.lib, self.lib.dad_train_time_grad_count(self._h, C.byref(n), C.byref(total)))
+        out = []
+        for i in range(n.value):
+            key, off, numel = C.c_char_p(), C.c_int64(), C.c_int64()
+            _check(self.lib, self.lib.dad_train_time_grad_info(self._h, i, C.byref(key), C.byref(off), C.byref(numel)))
+            out.append((key.value.decode(), off.value, numel.value))
+        self._time_grad_layout = (out, total.value)
+        return self._time_grad_layout
+
+    def _objective_bytes(self, batch: int):
+        """(saved, scratch) bytes of an objective step at `batch`: asked once per batch size (the debug hooks, which
+        change the plan, drop the answers)."""
+        cache = self.__dict__.setdefault("_objective_sizes", {})
+        if batch not in cache:
+            sv, sc = C.c_size_t(), C.c_size_t()
+            _check(self.lib, self.lib.dad_train_objective_workspace_bytes(self._h, batch, C.byref(sv), C.byref(sc)))
+            cache[batch] = (sv.value, sc.value)
+        return cache[batch]
+
+    def objective_forward(self, x0: torch.Tensor, t32: torch.Tensor, noise: torch.Tensor,
+                          weights: Optional[torch.Tensor], loss_type: int):
+        """The training objective of one batch (dad_train_objective_forward): returns (loss, saved) — a device
+        scalar and what :meth:`objective_backward` needs.  ``t32``: (B) int32 on the device."""
+        B = self._traj(x0, "x_start")
+        for name, ten in (("noise", noise), ("weights", weights)):
+            if ten is not None and self._traj(ten, name) != B:
+                raise RuntimeError(f"{name} batch mismatch")
+        if t32.dtype != torch.int32 or t32.numel() != B or t32.device != x0.device or not t32.is_contiguous():
+            raise RuntimeError("t must be (B) contiguous int32 on the trajectory's device")
+        sv, _ = self._objective_bytes(B)
+        saved = torch.empty(max(sv, 4) // 4 + 4, dtype=torch.float32, device=self.device)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_train_objective_forward(
+                self._h, x0.data_ptr(), t32.data_ptr(), noise.data_ptr(), _ptr(weights), int(loss_type),
+                loss.data_ptr(), B, saved.data_ptr(), saved.numel() * 4, self._stream()))
+        return loss, saved
+
+    def objective_backward(self, x0: torch.Tensor, noise: torch.Tensor, weights: Optional[torch.Tensor],
+                           loss_type: int, d_loss: torch.Tensor, saved: torch.Tensor, shapes):
+        """Every parameter gradient of one batch (dad_train_objective_backward): the tensors of grad_layout() followed
+        by those of time_grad_layout(), shaped like ``shapes`` (the real parameters'), all views of ONE flat allocation.
+        ``d_loss``: autograd's incoming scalar, on the device; it is read there."""
+        B = self._traj(x0, "x_start")
+        _require_device(d_loss, "d_loss")
+        _, sc = self._objective_bytes(B)
+        scratch = torch.empty(max(sc, 4) // 4 + 4, dtype=torch.float32, device=self.device)
+        conv, conv_total = self.grad_layout()
+        time, time_total = self.time_grad_layout()
+        layout = list(conv) + [(k, conv_total + o, n) for k, o, n in time]
+        total = conv_total + time_total
+        if len(shapes) != len(layout):
+            raise RuntimeError(f"{len(shapes)} parameter shapes for {len(layout)} gradient tensors")
+        real = None
+        if self.widths_padded:             # (as train_backward: the library fills padded gradients, one gather picks the real entries)
+            real = self.flat_padding([k for k, _, _ in layout], shapes, [o for _, o, _ in layout], total)
+            shapes = real.padded_shapes
+            for (key, _, numel), n in zip(layout, real.sizes):
+                if n != numel:
+                    raise RuntimeError(f"{key}: {n} padded elements, the library expects {numel}")
+        flat = torch.empty(total, dtype=torch.float32, device=self.device)
+        base = flat.data_ptr()
+        ptrs = (C.c_void_p * len(conv))(*[base + 4 * o for _, o, _ in layout[:len(conv)]])
+        tptrs = (C.c_void_p * len(time))(*[base + 4 * o for _, o, _ in layout[len(conv):]])
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_train_objective_backward(
+                self._h, x0.data_ptr(), noise.data_ptr(), _ptr(weights), int(loss_type), d_loss.data_ptr(),
+                ptrs, len(conv), tptrs, len(time), B, saved.data_ptr(), saved.numel() * 4,
+                scratch.data_ptr(), scratch.numel() * 4, self._stream()))
+        if real is not None:
+            return real.gather(flat)
+        spans = [layout[i + 1][1] - layout[i][1] for i in range(len(layout) - 1)] + [total - layout[-1][1]]
+        pieces = flat.split_with_sizes(spans)
+        return [(pc if pc.numel() == numel else pc[:numel]).view(tuple(shape))
+                for pc, (_, _, numel), shape in zip(pieces, layout, shapes)]
+
+    def objective_saved_views(self, saved: torch.Tensor, batch: int):
+        """(x_t, denoiser output) as the last objective_forward left them in ``saved`` (test hook)."""
+        a, b = C.c_size_t(), C.c_size_t()
+        _check(self.lib, self.lib.dad_debug_objective_offsets(self._h, int(batch), C.byref(a), C.byref(b)))
+        n = batch * self.horizon * self.transition_dim
+        shape = (batch, self.horizon, self.transition_dim)
+        return saved[a.value // 4:a.value // 4 + n].view(shape), saved[b.value // 4:b.value // 4 + n].view(shape)
+
     # ------------------------------------------------------------------ test / tuning hooks
     def debug_set_tile(self, cfg: int) -> None:
         """Force a conv tile (0..9), -1 = heuristic, 100+cfg / 99 = same without grid split-K."""
+        self.__dict__.pop("_objective_sizes", None)
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.dad_debug_set_tile(self._h, int(cfg)))
 
     def debug_set_option(self, name: str, value: int) -> None:
         # (the entry point synchronises the CURRENT device before dropping captured loops)
+        self.__dict__.pop("_objective_sizes", None)
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.dad_debug_set_option(self._h, name.encode(), int(value)))
 

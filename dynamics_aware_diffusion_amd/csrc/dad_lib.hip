@@ -27,6 +27,7 @@
 #include "conv_cc.hpp"
 #include "conv_ccw.hpp"
 #include "train_bwd.hpp"
+#include "train_objective.hpp"
 
 using namespace dadhost;
 
@@ -78,6 +79,8 @@ struct dad_model : HostModel {
     std::map<std::string, float*> d_time;    // time-MLP tensors as uploaded (dad_model_refresh_weights re-derives the tables)
     std::vector<WeightEntry> weights;        // every device copy of a parameter (dad_model_refresh_weights rebuilds them)
     float* d_h1 = nullptr;            // [T][4 time_dim] scratch of the table builder
+    std::vector<float> train_sched[2];         // dad_model_load_train_schedule: sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod
+    float* d_train_sched = nullptr;   // [2][T] their device copy (made when the model is finalized, or at the load after it)
     std::vector<void*> owned;         // every hipMalloc to free
     void* d_repack = nullptr;         // dad_model_refresh_weights: descriptor table of the last refresh (device)
     size_t repack_cap = 0;
@@ -152,6 +155,7 @@ void free_device(dad_model* m) {
     m->d_rng = nullptr;
     m->d_counters = nullptr;
     m->d_zero = nullptr;
+    m->d_train_sched = nullptr;
     m->weights.clear(); m->d_time.clear();
     for (Plan* plan : {&m->plan, &m->tplan})
         for (auto& op : plan->convs) op.d_w = op.d_bias = op.d_gamma = op.d_beta = op.d_rbias = nullptr;
@@ -432,6 +436,21 @@ int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, 
 }
 
 int build_time_tables(dad_model* m, hipStream_t st);
+// device copy of the two q_sample schedule vectors (the model's own allocation, freed with the others).  A load after
+// dad_model_finalize overwrites the copy a step in flight may still read: the device is drained first.
+int upload_train_schedule(dad_model* m) {
+    const size_t T = m->train_sched[0].size();
+    if (m->d_train_sched != nullptr) HIP_TRY(hipDeviceSynchronize());
+    if (m->d_train_sched == nullptr) {
+        void* a = nullptr;
+        HIP_TRY(hipMalloc(&a, 2 * T * sizeof(float)));
+        m->owned.push_back(a);
+        m->d_train_sched = (float*)a;
+    }
+    HIP_TRY(hipMemcpy(m->d_train_sched, m->train_sched[0].data(), T * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_train_sched + T, m->train_sched[1].data(), T * sizeof(float), hipMemcpyHostToDevice));
+    return DAD_OK;
+}
 // The per-timestep tables follow the time-MLP tensors lazily (dad_model_refresh_weights marks them stale): every
 // entry point that reads them calls this first, on the stream it launches on.
 int ensure_tables(dad_model* m, hipStream_t st) {
@@ -744,6 +763,15 @@ int dad_model_load_schedule(dad_model* m, const float* a, const float* b, const 
     return DAD_OK;
 }
 
+int dad_model_load_train_schedule(dad_model* m, const float* sqrt_ac, const float* sqrt_1m_ac, int32_t n) {
+    if (!m || !sqrt_ac || !sqrt_1m_ac) return fail(DAD_E_INVALID, "null argument");
+    if (n != m->cfg.n_timesteps)
+        return fail(DAD_E_INVALID, "training schedule has %d entries, the model %d timesteps", n, m->cfg.n_timesteps);
+    m->train_sched[0].assign(sqrt_ac, sqrt_ac + n);
+    m->train_sched[1].assign(sqrt_1m_ac, sqrt_1m_ac + n);
+    return m->finalized ? upload_train_schedule(m) : DAD_OK;
+}
+
 int dad_model_load_time_embedding(dad_model* m, const float* emb, int32_t n_timesteps, int32_t dim) {
     if (!m || !emb) return fail(DAD_E_INVALID, "null argument");
     if (n_timesteps != m->cfg.n_timesteps || dim != m->cfg.dim)
@@ -866,6 +894,7 @@ int dad_model_finalize(dad_model* m, dad_stream_t stream) {
     HIP_TRY(hipMemsetAsync(cnt, 0, kMaxSplitTiles * sizeof(unsigned), st));
     m->d_counters = (unsigned*)cnt;
     HIP_TRY(hipStreamSynchronize(st));
+    if (!m->train_sched[0].empty() && (rc = upload_train_schedule(m)) != DAD_OK) return rc;
     m->raw.clear();
     m->finalized = true;
     return DAD_OK;
@@ -1204,10 +1233,13 @@ int dad_unet_forward_train(dad_model* m, const float* x, const int32_t* row_inde
     return run_final(m, f, nullptr, x, 0, nullptr, 1, out, (float*)saved, st);
 }
 
-int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d_x, float* d_temb_rows,
-                      float* const* grad_tensors, int32_t n_grad_tensors,
-                      int32_t batch, void* saved_v, size_t saved_bytes, void* scratch_v, size_t scratch_bytes,
-                      dad_stream_t stream) {
+// `pre`: the pass as the fused objective already planned it for this batch (nothing is planned twice per call);
+// `before_launch`: what the fused objective enqueues behind every refusal of the pass and ahead of its first launch
+static int unet_backward(dad_model* m, const float* x, const float* d_out, float* d_x, float* d_temb_rows,
+                         float* const* grad_tensors, int32_t n_grad_tensors,
+                         int32_t batch, void* saved_v, size_t saved_bytes, void* scratch_v, size_t scratch_bytes,
+                         dad_stream_t stream, const ObjectivePlan* pre = nullptr,
+                         const std::function<int()>* before_launch = nullptr) {
     int rc = check_train(m, batch);
     if (rc != DAD_OK) return rc;
     if (!x || !d_out || !d_temb_rows || !grad_tensors || !saved_v || !scratch_v) return fail(DAD_E_INVALID, "null pointer");
@@ -1217,16 +1249,22 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
     for (int32_t i = 0; i < n_grad_tensors; ++i)
         if (!grad_tensors[i]) return fail(DAD_E_INVALID, "gradient tensor %d ('%s') is null", i, m->grad_slots[i].key.c_str());
     const int B = batch;
-    FwdPlan fwd;                                   // (read for the size of `saved` alone)
-    plan_forward(*m, true, B, false, fwd);
-    TrainScratch ts;
-    const int geom_rc = train_scratch(*m, B, ts);
-    if (saved_bytes < fwd.bytes || scratch_bytes < (size_t)ts.total * sizeof(float))
+    FwdPlan fwd_own;                               // (read for the size of `saved` alone)
+    TrainScratch ts_own;
+    int geom_rc = DAD_OK;                          // (a pre-planned pass was refused where it was planned)
+    if (pre == nullptr) {
+        plan_forward(*m, true, B, false, fwd_own);
+        geom_rc = train_scratch(*m, B, ts_own);
+    }
+    const size_t fwd_bytes = pre ? pre->fwd.bytes : fwd_own.bytes;
+    const TrainScratch& ts = pre ? pre->ts : ts_own;
+    if (saved_bytes < fwd_bytes || scratch_bytes < (size_t)ts.total * sizeof(float))
         return fail(DAD_E_WORKSPACE, "backward workspaces too small (saved %zu / %zu, scratch %zu / %zu bytes)", saved_bytes,
-                    fwd.bytes, scratch_bytes, (size_t)ts.total * sizeof(float));
+                    fwd_bytes, scratch_bytes, (size_t)ts.total * sizeof(float));
     if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
     if (geom_rc != DAD_OK) return geom_rc;
     if (d_x != nullptr && !m->bdx) return fail(DAD_E_STATE, "backward: no gradient reached the trajectory");
+    if (before_launch != nullptr && (rc = (*before_launch)()) != DAD_OK) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const Plan& P = m->tplan;
@@ -1341,6 +1379,231 @@ int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d
         HIP_TRY(hipGetLastError());
     }
     return DAD_OK;
+}
+
+int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d_x, float* d_temb_rows,
+                      float* const* grad_tensors, int32_t n_grad_tensors,
+                      int32_t batch, void* saved_v, size_t saved_bytes, void* scratch_v, size_t scratch_bytes,
+                      dad_stream_t stream) {
+    return unet_backward(m, x, d_out, d_x, d_temb_rows, grad_tensors, n_grad_tensors, batch, saved_v, saved_bytes, scratch_v,
+                         scratch_bytes, stream);
+}
+
+// ------------------------------------------------------------------------- fused training objective
+int dad_train_time_grad_count(const dad_model* m, int32_t* count, int64_t* total_floats) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (count) *count = (int32_t)m->time_grad_slots.size();
+    if (total_floats) *total_floats = m->time_grad_numel;
+    return DAD_OK;
+}
+
+int dad_train_time_grad_info(const dad_model* m, int32_t i, const char** key, int64_t* offset, int64_t* numel) {
+    if (!m || i < 0 || i >= (int32_t)m->time_grad_slots.size()) return fail(DAD_E_INVALID, "time gradient slot %d out of range", i);
+    if (key) *key = m->time_grad_slots[i].key.c_str();
+    if (offset) *offset = m->time_grad_slots[i].offset;
+    if (numel) *numel = m->time_grad_slots[i].numel;
+    return DAD_OK;
+}
+
+int dad_train_objective_workspace_bytes(const dad_model* m, int32_t batch, size_t* saved_bytes, size_t* scratch_bytes) {
+    if (!m || batch <= 0) return fail(DAD_E_INVALID, "bad argument");
+    ObjectiveLayout o;
+    objective_layout(*m, batch, o);        // (as dad_train_workspace_bytes: a refused batch still has a size)
+    if (saved_bytes) *saved_bytes = o.saved_bytes;
+    if (scratch_bytes) *scratch_bytes = o.scratch_bytes;
+    return DAD_OK;
+}
+
+int dad_debug_objective_offsets(const dad_model* m, int32_t batch, size_t* xt_offset, size_t* out_offset) {
+    if (!m || batch <= 0) return fail(DAD_E_INVALID, "bad argument");
+    ObjectiveLayout o;
+    objective_layout(*m, batch, o);
+    if (xt_offset) *xt_offset = o.saved_base + (size_t)o.xt * sizeof(float);
+    if (out_offset) *out_offset = o.saved_base + (size_t)o.out * sizeof(float);
+    return DAD_OK;
+}
+
+}  // extern "C"  (helpers of the objective entry points follow)
+
+namespace {
+
+// Every refusal the two objective entry points share, in the order the header documents; `plan`: everything of the
+// call that is planned on the host, once (`backward`: with the backward pass's geometry)
+int check_objective(const dad_model* m, int batch, int loss_type, bool backward, ObjectivePlan& plan) {
+    if (loss_type != DAD_LOSS_L1 && loss_type != DAD_LOSS_L2)
+        return fail(DAD_E_INVALID, "unknown loss_type %d (DAD_LOSS_L1 = 1, DAD_LOSS_L2 = 2)", loss_type);
+    if (!m->training) return fail(DAD_E_INVALID, "training mode is off: dad_model_set_training(m, 1) before dad_model_finalize");
+    if (m->precision != DAD_PREC_FP32) return fail(DAD_E_INVALID, "the training objective exists for the fp32 arithmetic only, not split-f16");
+    if (batch <= 0) return fail(DAD_E_INVALID, "batch must be positive (got %d)", batch);
+    if (!m->finalized) return fail(DAD_E_STATE, "dad_model_finalize has not been called");
+    if (m->d_train_sched == nullptr) return fail(DAD_E_STATE, "dad_model_load_train_schedule has not been called");
+    return objective_plan(*m, batch, backward, plan);
+}
+
+const float* time_tensor(const dad_model* m, const std::string& key) {
+    const auto it = m->d_time.find(key);
+    return it == m->d_time.end() ? nullptr : it->second;
+}
+
+// the blocks' time_mlp.1 tensors (device copies: what dad_model_refresh_weights keeps current) and, backward, their
+// gradient tensors (`tg`: the time gradient list, blocks from entry 4 on)
+int fill_time_blocks(const dad_model* m, dad::TimeBlocks& tb, float* const* tg) {
+    const std::vector<TimeBlockRef> list = time_block_list(*m);
+    tb = dad::TimeBlocks{};
+    tb.n = (int32_t)list.size();
+    for (size_t k = 0; k < list.size(); ++k) {
+        tb.w[k] = time_tensor(m, list[k].base + ".time_mlp.1.weight");
+        tb.b[k] = time_tensor(m, list[k].base + ".time_mlp.1.bias");
+        if (!tb.w[k] || !tb.b[k]) return fail(DAD_E_KEY, "missing key '%s.time_mlp.1'", list[k].base.c_str());
+        tb.off[k] = list[k].off;
+        if (tg != nullptr) { tb.dw[k] = tg[4 + 2 * k]; tb.db[k] = tg[5 + 2 * k]; }
+    }
+    tb.off[list.size()] = m->tplan.temb_width;
+    return DAD_OK;
+}
+
+template <int MODE>
+int launch_time_gemm(const dad::TimeGemmParams& p, int kslices, hipStream_t st) {
+    const dim3 grid((unsigned)((p.M + 31) / 32), (unsigned)((p.N + 31) / 32), (unsigned)kslices);
+    hipLaunchKernelGGL(dad::time_gemm_kernel<MODE>, grid, dim3(dad::TG_THREADS), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
+dad::ObjectiveParams objective_params(const dad_model* m, const ObjectiveLayout& o, float* sv, int batch, int loss_type,
+                                      const float* x0, const float* noise, const float* weights) {
+    dad::ObjectiveParams q{};
+    const int T = m->cfg.n_timesteps;
+    q.x0 = x0; q.noise = noise; q.weights = weights;
+    q.sqrt_ac = m->d_train_sched; q.sqrt_1m_ac = m->d_train_sched + T;
+    q.t_rows = (int32_t*)(sv + o.t_rows); q.row_index = (int32_t*)(sv + o.row_index);
+    q.xt = sv + o.xt; q.out = sv + o.out; q.partial = sv + o.partial;
+    q.row_elems = traj_horizon(*m) * m->cfg.transition_dim;
+    q.n = (long)batch * q.row_elems;
+    q.B = batch; q.T = T;
+    q.l1 = loss_type == DAD_LOSS_L1;
+    q.predict_epsilon = m->cfg.predict_epsilon;
+    q.nblocks = o.loss_blocks;
+    return q;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_rows, const float* noise,
+                                const float* weights, int32_t loss_type, float* loss_out, int32_t batch, void* saved,
+                                size_t saved_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (!x0 || !t_rows || !noise || !loss_out || !saved) return fail(DAD_E_INVALID, "null pointer");
+    ObjectivePlan plan;
+    int rc = check_objective(m, batch, loss_type, false, plan);
+    const ObjectiveLayout& o = plan.o;
+    const FwdPlan& f = plan.fwd;
+    if (rc != DAD_OK) return rc;
+    if (saved_bytes < o.saved_bytes)
+        return fail(DAD_E_WORKSPACE, "saved buffer has %zu bytes, the objective at batch %d needs %zu", saved_bytes, batch, o.saved_bytes);
+    const dad_cfg& c = m->cfg;
+    const int tdm = c.time_dim, W = m->tplan.temb_width;
+    const float *w1 = time_tensor(m, "time_mlp.1.weight"), *b1 = time_tensor(m, "time_mlp.1.bias");
+    const float *w3 = time_tensor(m, "time_mlp.3.weight"), *b3 = time_tensor(m, "time_mlp.3.bias");
+    if (!w1 || !b1 || !w3 || !b3) return fail(DAD_E_KEY, "missing key 'time_mlp'");
+    dad::TimeGemmParams g{};
+    if ((rc = fill_time_blocks(m, g.tb, nullptr)) != DAD_OK) return rc;
+
+    hipStream_t st = (hipStream_t)stream;
+    float* const sv = (float*)((char*)saved + o.saved_base);
+    dad::ObjectiveParams q = objective_params(m, o, sv, batch, loss_type, x0, noise, weights);
+    q.t_in = t_rows; q.loss = loss_out;
+    // 1. x_t = q_sample(x_0, t, noise); clamped timesteps and the row index of the projections (diffusion.py:138-157)
+    hipLaunchKernelGGL(dad::objective_xt_kernel, dim3((unsigned)((std::max<long>(q.n, batch) + 255) / 256)), dim3(dad::OBJ_THREADS), 0, st, q);
+    HIP_TRY(hipGetLastError());
+    // 2. the time chain per row (temporal_unet.py:19-32,155-160 and every block's :97-100)
+    g.emb = m->d_emb; g.t_rows = q.t_rows;
+    g.M = batch; g.N = 4 * tdm; g.K = c.dim; g.kslice = g.K;
+    g.w = w1; g.ldw = c.dim; g.bias = b1; g.out = sv + o.h1;
+    if ((rc = launch_time_gemm<dad::TG_FWD_H1>(g, 1, st)) != DAD_OK) return rc;
+    g.N = tdm; g.K = 4 * tdm; g.kslice = g.K;
+    g.a = sv + o.h1; g.lda = 4 * tdm; g.w = w3; g.ldw = 4 * tdm; g.bias = b3; g.out = sv + o.temb; g.out2 = sv + o.act;
+    if ((rc = launch_time_gemm<dad::TG_FWD_TEMB>(g, 1, st)) != DAD_OK) return rc;
+    g.N = W; g.K = tdm; g.kslice = g.K;
+    g.a = sv + o.act; g.lda = tdm; g.out = sv + o.rows; g.out2 = nullptr;
+    if ((rc = launch_time_gemm<dad::TG_FWD_ROWS>(g, 1, st)) != DAD_OK) return rc;
+    // the denoiser's training forward on x_t (diffusion.py:272), every activation kept
+    if ((rc = run_unet(m, f, q.xt, 0, (float*)saved, st, q.row_index, sv + o.rows)) != DAD_OK) return rc;
+    if ((rc = run_final(m, f, nullptr, q.xt, 0, nullptr, 1, sv + o.out, (float*)saved, st)) != DAD_OK) return rc;
+    // 3. weighted L1 / L2 mean (diffusion.py:274-290)
+    hipLaunchKernelGGL(dad::objective_loss_partial_kernel, dim3((unsigned)q.nblocks), dim3(dad::OBJ_THREADS), 0, st, q);
+    hipLaunchKernelGGL(dad::objective_loss_final_kernel, dim3(1), dim3(dad::OBJ_THREADS), 0, st, q);
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
+int dad_train_objective_backward(dad_model* m, const float* x0, const float* noise, const float* weights, int32_t loss_type,
+                                 const float* d_loss, float* const* grad_tensors, int32_t n_grad_tensors,
+                                 float* const* time_grad_tensors, int32_t n_time_grad_tensors, int32_t batch, void* saved,
+                                 size_t saved_bytes, void* scratch, size_t scratch_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (!x0 || !noise || !d_loss || !grad_tensors || !time_grad_tensors || !saved || !scratch) return fail(DAD_E_INVALID, "null pointer");
+    ObjectivePlan plan;
+    int rc = check_objective(m, batch, loss_type, true, plan);
+    const ObjectiveLayout& o = plan.o;
+    if (rc != DAD_OK) return rc;
+    // (both counts before either list is walked)
+    if (n_grad_tensors != (int32_t)m->grad_slots.size())
+        return fail(DAD_E_INVALID, "%d gradient tensors passed, the model has %zu (dad_train_grad_count)", n_grad_tensors, m->grad_slots.size());
+    if (n_time_grad_tensors != (int32_t)m->time_grad_slots.size())
+        return fail(DAD_E_INVALID, "%d time gradient tensors passed, the model has %zu (dad_train_time_grad_count)", n_time_grad_tensors,
+                    m->time_grad_slots.size());
+    for (int32_t i = 0; i < n_time_grad_tensors; ++i)
+        if (!time_grad_tensors[i]) return fail(DAD_E_INVALID, "time gradient tensor %d ('%s') is null", i, m->time_grad_slots[i].key.c_str());
+    if (saved_bytes < o.saved_bytes || scratch_bytes < o.scratch_bytes)
+        return fail(DAD_E_WORKSPACE, "objective workspaces too small (saved %zu / %zu, scratch %zu / %zu bytes)", saved_bytes, o.saved_bytes,
+                    scratch_bytes, o.scratch_bytes);
+    float* const sv = (float*)((char*)saved + o.saved_base);
+    float* const sc = (float*)((char*)scratch + o.scratch_base);
+    const dad_cfg& c = m->cfg;
+    const int tdm = c.time_dim, W = m->tplan.temb_width;
+    const float* w3 = time_tensor(m, "time_mlp.3.weight");
+    if (!w3) return fail(DAD_E_KEY, "missing key 'time_mlp.3.weight'");
+    dad::TimeGemmParams g{};
+    if ((rc = fill_time_blocks(m, g.tb, time_grad_tensors)) != DAD_OK) return rc;
+
+    hipStream_t st = (hipStream_t)stream;
+    dad::ObjectiveParams q = objective_params(m, o, sv, batch, loss_type, x0, noise, weights);
+    q.d_loss = d_loss; q.d_out = sc + o.d_out;
+    // d loss / d out, scaled by autograd's incoming scalar on the device: enqueued by the denoiser's pass behind its own
+    // refusals, ahead of its first launch
+    const std::function<int()> head = [&]() -> int {
+        hipLaunchKernelGGL(dad::objective_dout_kernel, dim3((unsigned)((q.n + 255) / 256)), dim3(dad::OBJ_THREADS), 0, st, q);
+        HIP_TRY(hipGetLastError());
+        return DAD_OK;
+    };
+    if ((rc = unet_backward(m, sv + o.xt, sc + o.d_out, nullptr, sc + o.d_rows, grad_tensors, n_grad_tensors, batch, saved, saved_bytes,
+                            scratch, scratch_bytes, stream, &plan, &head)) != DAD_OK) return rc;
+    // 4. the time chain backwards: six launches
+    g.emb = m->d_emb; g.t_rows = q.t_rows;
+    g.M = W; g.N = tdm; g.K = batch; g.kslice = g.K;                      // d Wk = d rows^T act, d bk
+    g.a = sc + o.d_rows; g.lda = W; g.w = sv + o.act; g.ldw = tdm;
+    if ((rc = launch_time_gemm<dad::TG_BWD_DWK>(g, 1, st)) != DAD_OK) return rc;
+    g.M = batch; g.N = tdm; g.K = W; g.kslice = o.kslice;                  // d act = d rows W, K slices in slabs
+    g.out = sc + o.dact_slab;
+    if ((rc = launch_time_gemm<dad::TG_BWD_DACT>(g, o.kslices, st)) != DAD_OK) return rc;
+    {
+        const long n = (long)batch * tdm;
+        hipLaunchKernelGGL(dad::time_dtemb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sc + o.dtemb,
+                           sc + o.dact_slab, sv + o.temb, n, o.kslices);
+        HIP_TRY(hipGetLastError());
+    }
+    g.M = tdm; g.N = 4 * tdm; g.K = batch; g.kslice = g.K;                 // d W3 = d temb^T mish(h1), d b3
+    g.a = sc + o.dtemb; g.lda = tdm; g.w = sv + o.h1; g.ldw = 4 * tdm; g.out = time_grad_tensors[2]; g.out2 = time_grad_tensors[3];
+    if ((rc = launch_time_gemm<dad::TG_BWD_DW3>(g, 1, st)) != DAD_OK) return rc;
+    g.M = batch; g.N = 4 * tdm; g.K = tdm; g.kslice = g.K;                 // d h1 = (d temb W3) mish'(h1)
+    g.w = w3; g.ldw = 4 * tdm; g.h1 = sv + o.h1; g.out = sc + o.dh1; g.out2 = nullptr;
+    if ((rc = launch_time_gemm<dad::TG_BWD_DH1>(g, 1, st)) != DAD_OK) return rc;
+    g.M = 4 * tdm; g.N = c.dim; g.K = batch; g.kslice = g.K;               // d W1 = d h1^T emb, d b1
+    g.a = sc + o.dh1; g.lda = 4 * tdm; g.out = time_grad_tensors[0]; g.out2 = time_grad_tensors[1];
+    return launch_time_gemm<dad::TG_BWD_DW1>(g, 1, st);
 }
 
 int dad_fill_normal(float* x, int32_t batch, int32_t row_elems, uint64_t seed, uint64_t row_offset,

@@ -3,7 +3,8 @@
 // weight packing (fp32 and split-f16 images), tile choice, grid-level split-K, the LDS slot
 // shifts, the launch geometry of every conv-GEMM, the small-batch plan, and — per call — one description of
 // everything a forward evaluation launches at a batch (FwdPlan, plan_forward) and of the backward pass (the list
-// of steps of build_backward_plan with its per-batch geometry, train_scratch).  The entry points of dad_lib.hip
+// of steps of build_backward_plan with its per-batch geometry, train_scratch), and the workspace layout of the fused
+// training objective behind both (objective_layout).  The entry points of dad_lib.hip
 // build those two once per call, refuse before their first launch, and only replay them; the size queries and
 // the plan report read the same descriptions.  Plain C++17, no HIP: dad_lib.hip includes it for the product,
 // tests/sanitize/host_check.cpp compiles it host-only under -fsanitize=address,undefined.
@@ -232,6 +233,8 @@ struct HostModel {
     struct GradSlot { std::string key; long offset, numel; };
     std::vector<GradSlot> grad_slots;        // flat gradient buffer: reference state_dict keys, torch layouts
     long grad_numel = 0;
+    std::vector<GradSlot> time_grad_slots;   // the time-MLP gradients of the fused objective: a flat buffer of their own
+    long time_grad_numel = 0;
     std::vector<BwdStep> bsteps;             // the backward pass in launch order
     std::vector<BwdSum> bsums;               // the column sums that end it, in order
     long bpart = 0;                          // partial-sum rows of the pass, in units of B floats
@@ -700,6 +703,33 @@ inline int build_backward_plan(HostModel* m) {
     return DAD_OK;
 }
 // Why a model cannot be trained on this engine, or nullptr.
+// The ResidualTemporalBlocks in launch order: where each one's time projection sits in the (B, temb_width) rows the
+// training forward reads (padded widths at their padded offsets).
+struct TimeBlockRef { std::string base; int off, cout; };
+inline std::vector<TimeBlockRef> time_block_list(const HostModel& m) {
+    std::vector<TimeBlockRef> v;
+    for (const ConvOp& op : m.tplan.convs)
+        if (op.temb_off >= 0)
+            v.push_back({op.name.substr(0, op.name.size() - std::strlen(".blocks.0.block.0")), op.temb_off, op.cout});
+    return v;
+}
+// Gradient tensors of the time MLPs (dad_train_time_grad_info): time_mlp.1 / time_mlp.3, then every block's
+// time_mlp.1 in launch order; torch layouts, each tensor at a multiple of four floats.
+inline void build_time_grad_slots(HostModel* m) {
+    m->time_grad_slots.clear(); m->time_grad_numel = 0;
+    auto slot = [&](const std::string& key, long numel) {
+        m->time_grad_slots.push_back({key, m->time_grad_numel, numel});
+        m->time_grad_numel += (numel + 3) / 4 * 4;
+    };
+    const long tdm = m->cfg.time_dim;
+    slot("time_mlp.1.weight", 4 * tdm * m->cfg.dim); slot("time_mlp.1.bias", 4 * tdm);
+    slot("time_mlp.3.weight", tdm * 4 * tdm); slot("time_mlp.3.bias", tdm);
+    for (const TimeBlockRef& b : time_block_list(*m)) {
+        slot(b.base + ".time_mlp.1.weight", (long)b.cout * tdm);
+        slot(b.base + ".time_mlp.1.bias", b.cout);
+    }
+}
+
 inline const char* training_refusal(const HostModel& m) {
     if (m.precision != DAD_PREC_FP32) return "the backward pass exists for the fp32 arithmetic only";
     return nullptr;
@@ -725,6 +755,7 @@ inline int build_plan(HostModel* m) {
     if (rc == DAD_OK) decide_kernel_families(m);
     if (rc == DAD_OK) rc = check_tiles(*m);
     if (rc == DAD_OK) rc = build_backward_plan(m);
+    if (rc == DAD_OK) build_time_grad_slots(m);
     return rc;
 }
 
@@ -1543,6 +1574,68 @@ inline int train_scratch(const HostModel& m, int B, TrainScratch& t) {
     if (m.bpart * B > t.part)
         first.note(fail(DAD_E_WORKSPACE, "backward: partial sums overran their region (%ld > %ld floats)", m.bpart * B, t.part));
     return first.done();
+}
+
+// ---- the fused training objective (dad_train_objective_forward / dad_train_objective_backward)
+// What it keeps beyond the training forward's activations and the backward pass's scratch: offsets in floats from
+// the start of the new part of `saved` / `scratch`, which begins at the next multiple of 256 bytes behind the
+// existing part; every region starts at a multiple of 64 floats.
+struct ObjectiveLayout {
+    // saved: written by the forward, read by the backward
+    long xt = 0, out = 0, t_rows = 0, row_index = 0, h1 = 0, temb = 0, act = 0, rows = 0, partial = 0, saved_floats = 0;
+    // scratch: the backward pass's own
+    long d_out = 0, d_rows = 0, dact_slab = 0, dtemb = 0, dh1 = 0, scratch_floats = 0;
+    int loss_blocks = 1;     // blocks of the loss's partial sums
+    int kslices = 1;         // K slices of d act = d rows . W (K = temb_width), added in slice order
+    int kslice = 0;          //   columns per slice (a multiple of 128: 32 per wave)
+    size_t saved_base = 0, scratch_base = 0;      // bytes of the existing parts (rounded up to 256)
+    size_t saved_bytes = 0, scratch_bytes = 0;    // totals: what dad_train_objective_workspace_bytes reports
+};
+constexpr int kObjectiveMaxLossBlocks = 1024;
+// Everything one objective call plans on the host, planned once: the layout, the training forward it replays and
+// (`backward`) the geometry of the backward pass, which dad_unet_backward's body takes over instead of planning again.
+// Without `backward` the scratch half of the layout stays empty (the forward does not touch `scratch`).
+struct ObjectivePlan { ObjectiveLayout o; FwdPlan fwd; TrainScratch ts; };
+inline int objective_plan(const HostModel& m, int B, bool backward, ObjectivePlan& p) {
+    ObjectiveLayout& o = p.o;
+    FwdPlan& f = p.fwd;
+    TrainScratch& ts = p.ts;
+    o = ObjectiveLayout();
+    FirstRefusal first;
+    first.note(plan_forward(m, true, B, false, f));
+    ts = TrainScratch();
+    if (backward) first.note(train_scratch(m, B, ts));
+    const long tdm = m.cfg.time_dim, W = std::max(1, m.tplan.temb_width);
+    const long n = (long)B * traj_horizon(m) * m.cfg.transition_dim;
+    auto al = [](long v) { return (v + 63) / 64 * 64; };
+    o.loss_blocks = (int)std::max(1L, std::min((long)kObjectiveMaxLossBlocks, (n + 1023) / 1024));
+    const long tiles = (long)((B + 31) / 32) * ((tdm + 31) / 32);
+    const long want = std::max(1L, std::min(256 / tiles, (W + 127) / 128));
+    o.kslice = (int)(((W + want - 1) / want + 127) / 128 * 128);
+    o.kslices = (int)((W + o.kslice - 1) / o.kslice);
+    long at = 0;
+    auto take = [&](long floats) { const long q = at; at += al(floats); return q; };
+    o.xt = take(n); o.out = take(n); o.t_rows = take(B); o.row_index = take(B);
+    o.h1 = take(B * 4 * tdm); o.temb = take(B * tdm); o.act = take(B * tdm); o.rows = take(B * W);
+    o.partial = take(o.loss_blocks);
+    o.saved_floats = at;
+    at = 0;
+    o.d_out = take(n); o.d_rows = take(B * W); o.dact_slab = take((long)o.kslices * B * tdm);
+    o.dtemb = take(B * tdm); o.dh1 = take(B * 4 * tdm);
+    o.scratch_floats = at;
+    o.saved_base = (f.bytes + 255) / 256 * 256;
+    o.scratch_base = ((size_t)ts.total * sizeof(float) + 255) / 256 * 256;
+    o.saved_bytes = o.saved_base + (size_t)o.saved_floats * sizeof(float);
+    o.scratch_bytes = o.scratch_base + (size_t)o.scratch_floats * sizeof(float);
+    if ((int)time_block_list(m).size() > 4 * DAD_MAX_LEVELS)
+        first.note(fail(DAD_E_INVALID, "objective: %zu residual blocks", time_block_list(m).size()));
+    return first.done();
+}
+inline int objective_layout(const HostModel& m, int B, ObjectiveLayout& o) {
+    ObjectivePlan p;
+    const int rc = objective_plan(m, B, true, p);
+    o = p.o;
+    return rc;
 }
 
 // dad_debug_backward_plan: which kernels one training step takes at batch B (layout: include/dad.h, DAD_BP_*),

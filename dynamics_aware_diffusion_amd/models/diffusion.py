@@ -114,6 +114,9 @@ class GaussianDiffusion(nn.Module):
         # "torch" RNG: the fused loop takes the whole z stack (T, B, H, td) up to this many bytes;
         # beyond it z is drawn step by step (same draws, same order, O(1) memory in T)
         self.max_noise_stack_bytes = 256 << 20
+        # True: ``loss`` runs q_sample, the time MLPs, the denoiser and the L1 / L2 mean inside the library, as one
+        # autograd node over the parameters (dad_train_objective_forward / _backward).  Opt-in; False changes nothing.
+        self.fused_objective = False
 
     @staticmethod
     def noise_stack_bytes(shape, n_steps: int) -> int:
@@ -226,11 +229,22 @@ class GaussianDiffusion(nn.Module):
         autograd graph whose denoiser node is the engine's explicit backward pass
         (``dad_unet_backward``): ``loss.backward()`` fills ``.grad`` of every parameter, as the
         reference's training step expects (utils/training.py:152-156).  Under ``torch.no_grad()`` it
-        is the forward-only validation loss."""
+        is the forward-only validation loss.
+
+        ``fused_objective = True`` (opt-in) keeps the two draws here and hands everything after them to the library:
+        the result is the scalar of one autograd node whose inputs are the parameters, the time MLPs included.  A
+        trajectory that itself requires grad takes the path above."""
         batch = x_start.shape[0]
         self._engine(x_start.device)              # bind schedule / options before the model call
         t = torch.randint(0, self.n_timesteps, (batch,), device=x_start.device).long()
         noise = torch.randn_like(x_start)
+        # (the library knows the two elementwise losses the constructor builds; a replaced loss_fn runs as it is, below)
+        fused_loss = "l1" if type(self.loss_fn) is nn.L1Loss else "l2" if type(self.loss_fn) is nn.MSELoss else None
+        if fused_loss is not None and getattr(self.loss_fn, "reduction", None) != "none":
+            fused_loss = None
+        if self.fused_objective and fused_loss is not None and not (torch.is_grad_enabled() and x_start.requires_grad):
+            return self.model.objective(x_start, t, noise, weights, fused_loss,
+                                        self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
         x_noisy = self.q_sample(x_start, t, noise)
         model_output = self.model(x_noisy, t)
         target = noise if self.predict_epsilon else x_start

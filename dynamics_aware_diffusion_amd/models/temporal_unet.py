@@ -237,6 +237,25 @@ class TemporalUnet(nn.Module):
             rows = torch.zeros(rows.shape[0], width, dtype=rows.dtype, device=rows.device).index_copy(1, index, rows)
         return _UnetFunction.apply(eng, layout, x.contiguous().float(), rows, *tensors)
 
+    def objective(self, x_start: torch.Tensor, t: torch.Tensor, noise: torch.Tensor, weights, loss_type: str,
+                  sqrt_ac: torch.Tensor, sqrt_1m_ac: torch.Tensor) -> torch.Tensor:
+        """The whole training objective on the engine (``GaussianDiffusion.fused_objective``): q_sample, the time
+        MLPs, the denoiser and the weighted L1 / L2 mean as ONE autograd node whose differentiable inputs are the
+        parameters, time MLPs included (dad_train_objective_forward / dad_train_objective_backward).  Under
+        ``torch.no_grad()`` the forward alone: the validation loss."""
+        from .._engine import LOSS_TYPES
+        x0 = x_start.contiguous().float()
+        eng = self.engine(int(x0.shape[1]), x0.device, training=True)
+        eng.bind_train_schedule(sqrt_ac, sqrt_1m_ac)
+        layout, _ = eng.grad_layout()
+        tlayout, _ = eng.time_grad_layout()
+        params = self._params()
+        tensors = [params[k] for k, _, _ in layout] + [params[k] for k, _, _ in tlayout]
+        if weights is not None:            # anything broadcastable to (B, H, td), as the reference's product takes
+            weights = torch.as_tensor(weights, dtype=torch.float32, device=x0.device).expand(x0.shape).contiguous()
+        t32 = t.reshape(-1).to(device=x0.device, dtype=torch.int32).contiguous()
+        return _ObjectiveFunction.apply(eng, LOSS_TYPES[loss_type], x0, t32, noise.contiguous().float(), weights, *tensors)
+
     def forward(self, x: torch.Tensor, time: Union[int, torch.Tensor]) -> torch.Tensor:
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._params().values())):
             if isinstance(time, int):
@@ -283,3 +302,24 @@ class _UnetFunction(torch.autograd.Function):
         d_x, d_rows, grads = ctx.eng.train_backward(x, d_out.contiguous().float(), ctx.saved, ctx.temb_width, ctx.shapes)
         ctx.saved = None
         return (None, None, d_x, d_rows, *grads)
+
+
+class _ObjectiveFunction(torch.autograd.Function):
+    """GaussianDiffusion.loss after its two draws, on the HIP engine (include/dad.h, the fused training objective).
+    Differentiable inputs: every parameter — the conv / GroupNorm tensors in the order of ``HipEngine.grad_layout()``,
+    then the time-MLP tensors in the order of ``HipEngine.time_grad_layout()``; the data are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, eng, loss_type, x0, t32, noise, weights, *params):
+        loss, saved = eng.objective_forward(x0, t32, noise, weights, loss_type)
+        ctx.eng, ctx.loss_type, ctx.saved = eng, loss_type, saved
+        ctx.data = (x0, noise, weights)
+        ctx.shapes = [tuple(p.shape) for p in params]
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        x0, noise, weights = ctx.data
+        grads = ctx.eng.objective_backward(x0, noise, weights, ctx.loss_type, d_loss.contiguous().float(), ctx.saved, ctx.shapes)
+        ctx.saved = ctx.data = None
+        return (None, None, None, None, None, None, *grads)

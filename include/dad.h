@@ -155,15 +155,17 @@ int dad_unet_forward_rows(dad_model* m, const float* x, const int32_t* t_rows, f
  *   - GroupNorm(8) + Mish backward (temporal_unet.py:71-72) is one kernel per conv, fed by the
  *     pre-normalisation output and the (mean, rstd) pairs the training forward keeps.
  * The time MLPs (SinusoidalPosEmb -> Linear -> Mish -> Linear and every block's Mish -> Linear,
- * temporal_unet.py:97-100,155-160) stay with the caller: the forward takes their per-row outputs
- * (B, temb_width) — the concatenation, in launch order, of every ResidualTemporalBlock's projection —
- * and the backward returns the gradient with respect to them.  fp32 only; no optimiser, no EMA.
+ * temporal_unet.py:97-100,155-160) come in two forms.  dad_unet_forward_train / dad_unet_backward take their
+ * per-row outputs (B, temb_width) — the concatenation, in launch order, of every ResidualTemporalBlock's
+ * projection — and return the gradient with respect to them: a caller with an autograd of its own keeps the MLPs
+ * there.  dad_train_objective_forward / dad_train_objective_backward (below) run the whole objective in the
+ * library: q_sample, the time MLPs forward and backward, the denoiser, the loss.  fp32 only; no optimiser, no EMA.
  *
  * dad_model_set_training(m, 1) must precede dad_model_finalize (the extra weight images are packed
  * there).  dad_train_grad_info enumerates the gradient tensors (reference state_dict key without "model.",
  * element count; `offset` is their position in a packed buffer for callers that want one) — every tensor in
  * the reference's own layout (Conv1d (out, in, k); ConvTranspose1d (in, out, k)).  The time-MLP tensors are
- * not in the list. */
+ * not in the list (dad_train_time_grad_info has them). */
 int dad_model_set_training(dad_model* m, int32_t on);
 /* Replaces: nothing in the reference (its modules ARE the parameters); here the engine holds packed copies,
  * and an optimiser step (utils/training.py:166) changes the parameters every iteration.  Re-derives, ON THE
@@ -193,6 +195,51 @@ int dad_unet_forward_train(dad_model* m, const float* x, const int32_t* row_inde
 int dad_unet_backward(dad_model* m, const float* x, const float* d_out, float* d_x, float* d_temb_rows,
                       float* const* grad_tensors, int32_t n_grad_tensors, int32_t batch, void* saved,
                       size_t saved_bytes, void* scratch, size_t scratch_bytes, dad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The whole training objective in the library: GaussianDiffusion.loss (m_diffuser/models/diffusion.py:253-290)
+ * and loss.backward() (m_diffuser/utils/training.py:152-156) as two calls.  Only the random draws stay with the
+ * caller (t ~ randint, noise ~ randn_like, diffusion.py:265-268).  Needs dad_model_set_training(m, 1), the fp32
+ * arithmetic and dad_model_load_train_schedule.  Argument errors — a null pointer, a loss_type other than
+ * DAD_LOSS_L1 / DAD_LOSS_L2, training mode off, the split-f16 arithmetic, a wrong tensor count — return
+ * DAD_E_INVALID with a message, before the first launch.  Nothing synchronises with the host. */
+#define DAD_LOSS_L1 1        /* nn.L1Loss  (diffusion.py:85)  */
+#define DAD_LOSS_L2 2        /* nn.MSELoss (diffusion.py:87)  */
+
+/* The two schedule vectors q_sample reads (diffusion.py:113-114, 138-157): sqrt_alphas_cumprod and
+ * sqrt_one_minus_alphas_cumprod, HOST fp32, n == cfg.n_timesteps.  Before or after dad_model_finalize; a load after it replaces the device copy and
+ * waits for the device first (a step in flight may still read the old one). */
+int dad_model_load_train_schedule(dad_model* m, const float* sqrt_ac, const float* sqrt_1m_ac, int32_t n);
+
+/* The time-MLP gradient tensors, a list of its own beside dad_train_grad_info (which is unchanged): time_mlp.1.weight,
+ * time_mlp.1.bias, time_mlp.3.weight, time_mlp.3.bias, then every ResidualTemporalBlock's time_mlp.1.weight / .bias in
+ * launch order (temporal_unet.py:97-100,155-160); torch layouts, `offset` in floats within a packed buffer of
+ * *total_floats. */
+int dad_train_time_grad_count(const dad_model* m, int32_t* count, int64_t* total_floats);
+int dad_train_time_grad_info(const dad_model* m, int32_t i, const char** key, int64_t* offset, int64_t* numel);
+
+/* saved / scratch of the two calls below: what dad_train_workspace_bytes reports (those results are unchanged) plus
+ * the objective's own regions behind them (x_t, the denoiser output, the time chain's activations; d loss / d out,
+ * the projections' gradient, the time chain's gradients). */
+int dad_train_objective_workspace_bytes(const dad_model* m, int32_t batch, size_t* saved_bytes, size_t* scratch_bytes);
+
+/* Replaces: GaussianDiffusion.loss (diffusion.py:253-290) after its two draws — q_sample (diffusion.py:138-157; x_t
+ * bit-identical to torch's two products and one sum), SinusoidalPosEmb lookup + time_mlp + every block's Mish -> Linear
+ * per row (temporal_unet.py:19-32,97-100,155-160), TemporalUnet.forward in training mode (diffusion.py:272), the
+ * elementwise L1 / L2 against the noise (or x_0: cfg.predict_epsilon), optional weights, mean (diffusion.py:274-290).
+ * x0, noise, weights (or NULL): (B, H, td) device fp32; t_rows: (B) int32 device, clamped to [0, n_timesteps - 1]
+ * before any table read; loss_out: device scalar.  `saved` is handed to dad_train_objective_backward. */
+int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_rows, const float* noise,
+                                const float* weights, int32_t loss_type, float* loss_out, int32_t batch, void* saved,
+                                size_t saved_bytes, dad_stream_t stream);
+/* Replaces: loss.backward() (utils/training.py:152-156): autograd's walk from the scalar through the mean, the
+ * elementwise loss (sign(0) = 0 for L1, as torch), the denoiser (dad_unet_backward) and the time MLPs.  d_loss: DEVICE
+ * scalar, autograd's incoming gradient, read on the device.  grad_tensors: as dad_unet_backward; time_grad_tensors: one
+ * device tensor per entry of dad_train_time_grad_info; all fully overwritten, fixed summation order. */
+int dad_train_objective_backward(dad_model* m, const float* x0, const float* noise, const float* weights, int32_t loss_type,
+                                 const float* d_loss, float* const* grad_tensors, int32_t n_grad_tensors,
+                                 float* const* time_grad_tensors, int32_t n_time_grad_tensors, int32_t batch, void* saved,
+                                 size_t saved_bytes, void* scratch, size_t scratch_bytes, dad_stream_t stream);
 
 /* Arguments of one reverse step beyond (x, t). All pointers may be NULL unless noted. */
 typedef struct dad_step_args {
@@ -309,6 +356,9 @@ int dad_debug_set_option(dad_model* m, const char* name, int32_t value);
 int dad_debug_read_table(dad_model* m, int32_t which, int32_t t, float* host_out, int32_t capacity,
                          int32_t* width_out);
 int dad_debug_mish(const float* in, float* out, int64_t n, dad_stream_t stream);
+/* Where dad_train_objective_forward keeps x_t and the denoiser's output inside `saved` (byte offsets; host-side
+ * query): lets a test compare x_t with q_sample (diffusion.py:138-157) bit for bit. */
+int dad_debug_objective_offsets(const dad_model* m, int32_t batch, size_t* xt_offset, size_t* out_offset);
 /* 1 when the kernel registry, generated from the planner's statement of which conv-GEMM kernels exist, covers that
  * statement's whole domain and holds nothing else (no device call) */
 int dad_debug_kernel_table_consistent(void);

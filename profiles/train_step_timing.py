@@ -24,6 +24,8 @@ ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--dim", type=int, default=0, help="override the architecture's dim (48 / 96: zero-padded GroupNorm groups)")
 ap.add_argument("--horizon", type=int, default=32, help="24 / 48 / 100: zero-padded rows")
+ap.add_argument("--fused-objective", action="store_true", help="GaussianDiffusion.fused_objective: q_sample, time MLPs and loss inside the library")
+ap.add_argument("--steps", type=int, default=10, help="steps of each back-to-back loop")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 od, ad, dim, mults, T = synth.ARCHS[args.arch]
@@ -33,6 +35,7 @@ td = od + ad
 unet = TemporalUnet(td, dim=dim, dim_mults=mults)
 unet.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_unet_state(td, dim, mults, seed=0).items()})
 diff = GaussianDiffusion(unet, H, od, ad, n_timesteps=T).to(dev)
+diff.fused_objective = args.fused_objective
 x0 = torch.from_numpy(synth.normal_like(3, "train.x0", (args.batch, H, td))).to(dev).clamp(-1, 1)
 f = synth.unet_flops_per_sample(td, dim, mults, H) * args.batch      # (the REAL net's FLOPs: padding is overhead)
 fwd, bwd = [], []
@@ -52,7 +55,7 @@ for rep in range(args.repeats + 1):
         bwd.append(t2 - t1)
 # steady state: steps back to back as a training loop issues them (no synchronisation in between — the host side of
 # step i + 1 runs under the kernels of step i)
-N = 10
+N = args.steps
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(N):
@@ -77,7 +80,7 @@ for _ in range(N):
 torch.cuda.synchronize()
 steady_opt = (time.perf_counter() - t0) / N
 fm, bm = min(fwd) * 1e3, min(bwd) * 1e3
-print(f"{args.arch} dim={dim} H={H} B={args.batch}: training forward {fm:.2f} ms ({f / fm / 1e9:.1f} TFLOP/s), backward {bm:.2f} ms "
+print(f"{args.arch} dim={dim} H={H} B={args.batch}{' fused objective' if args.fused_objective else ''}: training forward {fm:.2f} ms ({f / fm / 1e9:.1f} TFLOP/s), backward {bm:.2f} ms "
       f"({2 * f / bm / 1e9:.1f} TFLOP/s algorithmic), {N} steps back to back {steady * 1e3:.2f} ms per step "
       f"({3 * f / steady / 1e12:.1f} TFLOP/s, {args.batch / steady:.0f} samples/s), with SGD step + weight refresh "
       f"{steady_opt * 1e3:.2f} ms per step ({args.batch / steady_opt:.0f} samples/s), loss {float(loss):.5f}", flush=True)
