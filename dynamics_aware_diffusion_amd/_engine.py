@@ -114,6 +114,8 @@ ABI = {
                                                C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dad_debug_objective_offsets": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "dad_debug_objective_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                           C.POINTER(C.c_int32)]),
     "dad_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "dad_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double)]),
@@ -171,6 +173,8 @@ def _require_device(t: torch.Tensor, name: str) -> None:
 PRECISIONS = {"fp32": 0, "f16x3": 1}      # DAD_PREC_* of include/dad.h
 LOSS_TYPES = {"l1": 1, "l2": 2}           # DAD_LOSS_* of include/dad.h
 TABLES = {"sinusoid": 0, "time_mlp": 1, "blocks": 2}      # DAD_TABLE_* of include/dad.h
+# DAD_OP_TG_* of include/dad.h: the eight modes of time_gemm_kernel, then time_dtemb_kernel
+TIME_GEMM_MODES = ("FWD_H1", "FWD_TEMB", "FWD_ROWS", "BWD_DWK", "BWD_DACT", "BWD_DW3", "BWD_DH1", "BWD_DW1", "DTEMB")
 
 
 def sinusoid_table(n_timesteps: int, dim: int) -> torch.Tensor:
@@ -720,6 +724,28 @@ class HipEngine:
             "fwd": hist(31), "dgrad": hist(51),
             "launches": [dict(zip(fields, r[at:at + len(fields)])) for at in range(72, len(r), len(fields))],
         }
+
+    def objective_plan(self, batch: int) -> dict:
+        """The time chain of one fused objective step at `batch` (host logic only, as :meth:`backward_plan`).  Keys as
+        DAD_OP_* of include/dad.h: ``loss_blocks``, ``kslices``, ``kslice``, ``temb_width``, ``blocks``, ``n``, and
+        ``launches``: one dict per launch in launch order with ``mode`` (a name of TIME_GEMM_MODES), ``M``, ``N``,
+        ``K``, ``grid`` (x, y, z), ``chunks`` (32-wide K chunks of a full slice), ``last_chunks``, ``ktail`` (K % 32)
+        and ``kslice``."""
+        need = C.c_int32()
+        _check(self.lib, self.lib.dad_debug_objective_plan(self._h, int(batch), None, 0, C.byref(need)))
+        buf = (C.c_int32 * need.value)()
+        _check(self.lib, self.lib.dad_debug_objective_plan(self._h, int(batch), buf, need.value, C.byref(need)))
+        r = list(buf)
+        fields = ("mode", "M", "N", "K", "gx", "gy", "gz", "chunks", "last_chunks", "ktail", "kslice")
+        assert r[6] == len(fields) and (len(r) - 8) == r[7] * r[6]
+        launches = []
+        for at in range(8, len(r), len(fields)):
+            q = dict(zip(fields, r[at:at + len(fields)]))
+            q["mode"] = TIME_GEMM_MODES[q["mode"]]
+            q["grid"] = (q.pop("gx"), q.pop("gy"), q.pop("gz"))
+            launches.append(q)
+        return {"loss_blocks": r[0], "kslices": r[1], "kslice": r[2], "temb_width": r[3], "blocks": r[4], "n": r[5],
+                "launches": launches}
 
     def mish(self, x: torch.Tensor) -> torch.Tensor:
         """The conv epilogue's Mish applied to a device tensor (test hook)."""

@@ -1462,10 +1462,16 @@ int fill_time_blocks(const dad_model* m, dad::TimeBlocks& tb, float* const* tg) 
     return DAD_OK;
 }
 
+static_assert(dad::TG_FWD_H1 == DAD_OP_TG_FWD_H1 && dad::TG_FWD_TEMB == DAD_OP_TG_FWD_TEMB && dad::TG_FWD_ROWS == DAD_OP_TG_FWD_ROWS &&
+              dad::TG_BWD_DWK == DAD_OP_TG_BWD_DWK && dad::TG_BWD_DACT == DAD_OP_TG_BWD_DACT && dad::TG_BWD_DW3 == DAD_OP_TG_BWD_DW3 &&
+              dad::TG_BWD_DH1 == DAD_OP_TG_BWD_DH1 && dad::TG_BWD_DW1 == DAD_OP_TG_BWD_DW1, "DAD_OP_TG_* name the TimeGemm modes");
+
+// Launch `l` of the planned time chain (ObjectivePlan::time): its geometry is the list's, the operands are `p`'s
 template <int MODE>
-int launch_time_gemm(const dad::TimeGemmParams& p, int kslices, hipStream_t st) {
-    const dim3 grid((unsigned)((p.M + 31) / 32), (unsigned)((p.N + 31) / 32), (unsigned)kslices);
-    hipLaunchKernelGGL(dad::time_gemm_kernel<MODE>, grid, dim3(dad::TG_THREADS), 0, st, p);
+int launch_time_gemm(dad::TimeGemmParams& p, const TimeLaunch& l, hipStream_t st) {
+    if (l.mode != MODE) return fail(DAD_E_STATE, "time chain: launch %d planned where %d runs", l.mode, MODE);
+    p.M = l.M; p.N = l.N; p.K = l.K; p.kslice = l.kslice;
+    hipLaunchKernelGGL(dad::time_gemm_kernel<MODE>, dim3(l.gx(), l.gy(), l.gz()), dim3(dad::TG_THREADS), 0, st, p);
     HIP_TRY(hipGetLastError());
     return DAD_OK;
 }
@@ -1504,7 +1510,8 @@ int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_
     if (saved_bytes < o.saved_bytes)
         return fail(DAD_E_WORKSPACE, "saved buffer has %zu bytes, the objective at batch %d needs %zu", saved_bytes, batch, o.saved_bytes);
     const dad_cfg& c = m->cfg;
-    const int tdm = c.time_dim, W = m->tplan.temb_width;
+    const int tdm = c.time_dim;
+    const std::vector<TimeLaunch>& tl = plan.time;        // [0, 3): the forward's
     const float *w1 = time_tensor(m, "time_mlp.1.weight"), *b1 = time_tensor(m, "time_mlp.1.bias");
     const float *w3 = time_tensor(m, "time_mlp.3.weight"), *b3 = time_tensor(m, "time_mlp.3.bias");
     if (!w1 || !b1 || !w3 || !b3) return fail(DAD_E_KEY, "missing key 'time_mlp'");
@@ -1520,15 +1527,12 @@ int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_
     HIP_TRY(hipGetLastError());
     // 2. the time chain per row (temporal_unet.py:19-32,155-160 and every block's :97-100)
     g.emb = m->d_emb; g.t_rows = q.t_rows;
-    g.M = batch; g.N = 4 * tdm; g.K = c.dim; g.kslice = g.K;
     g.w = w1; g.ldw = c.dim; g.bias = b1; g.out = sv + o.h1;
-    if ((rc = launch_time_gemm<dad::TG_FWD_H1>(g, 1, st)) != DAD_OK) return rc;
-    g.N = tdm; g.K = 4 * tdm; g.kslice = g.K;
+    if ((rc = launch_time_gemm<dad::TG_FWD_H1>(g, tl[0], st)) != DAD_OK) return rc;
     g.a = sv + o.h1; g.lda = 4 * tdm; g.w = w3; g.ldw = 4 * tdm; g.bias = b3; g.out = sv + o.temb; g.out2 = sv + o.act;
-    if ((rc = launch_time_gemm<dad::TG_FWD_TEMB>(g, 1, st)) != DAD_OK) return rc;
-    g.N = W; g.K = tdm; g.kslice = g.K;
+    if ((rc = launch_time_gemm<dad::TG_FWD_TEMB>(g, tl[1], st)) != DAD_OK) return rc;
     g.a = sv + o.act; g.lda = tdm; g.out = sv + o.rows; g.out2 = nullptr;
-    if ((rc = launch_time_gemm<dad::TG_FWD_ROWS>(g, 1, st)) != DAD_OK) return rc;
+    if ((rc = launch_time_gemm<dad::TG_FWD_ROWS>(g, tl[2], st)) != DAD_OK) return rc;
     // the denoiser's training forward on x_t (diffusion.py:272), every activation kept
     if ((rc = run_unet(m, f, q.xt, 0, (float*)saved, st, q.row_index, sv + o.rows)) != DAD_OK) return rc;
     if ((rc = run_final(m, f, nullptr, q.xt, 0, nullptr, 1, sv + o.out, (float*)saved, st)) != DAD_OK) return rc;
@@ -1562,8 +1566,8 @@ int dad_train_objective_backward(dad_model* m, const float* x0, const float* noi
                     scratch_bytes, o.scratch_bytes);
     float* const sv = (float*)((char*)saved + o.saved_base);
     float* const sc = (float*)((char*)scratch + o.scratch_base);
-    const dad_cfg& c = m->cfg;
-    const int tdm = c.time_dim, W = m->tplan.temb_width;
+    const int tdm = m->cfg.time_dim, W = m->tplan.temb_width;
+    const std::vector<TimeLaunch>& tl = plan.time;        // [3, 9): the backward's
     const float* w3 = time_tensor(m, "time_mlp.3.weight");
     if (!w3) return fail(DAD_E_KEY, "missing key 'time_mlp.3.weight'");
     dad::TimeGemmParams g{};
@@ -1583,27 +1587,23 @@ int dad_train_objective_backward(dad_model* m, const float* x0, const float* noi
                             scratch, scratch_bytes, stream, &plan, &head)) != DAD_OK) return rc;
     // 4. the time chain backwards: six launches
     g.emb = m->d_emb; g.t_rows = q.t_rows;
-    g.M = W; g.N = tdm; g.K = batch; g.kslice = g.K;                      // d Wk = d rows^T act, d bk
-    g.a = sc + o.d_rows; g.lda = W; g.w = sv + o.act; g.ldw = tdm;
-    if ((rc = launch_time_gemm<dad::TG_BWD_DWK>(g, 1, st)) != DAD_OK) return rc;
-    g.M = batch; g.N = tdm; g.K = W; g.kslice = o.kslice;                  // d act = d rows W, K slices in slabs
-    g.out = sc + o.dact_slab;
-    if ((rc = launch_time_gemm<dad::TG_BWD_DACT>(g, o.kslices, st)) != DAD_OK) return rc;
+    g.a = sc + o.d_rows; g.lda = W; g.w = sv + o.act; g.ldw = tdm;         // d Wk = d rows^T act, d bk
+    if ((rc = launch_time_gemm<dad::TG_BWD_DWK>(g, tl[3], st)) != DAD_OK) return rc;
+    g.out = sc + o.dact_slab;                                              // d act = d rows W, K slices in slabs
+    if ((rc = launch_time_gemm<dad::TG_BWD_DACT>(g, tl[4], st)) != DAD_OK) return rc;
     {
-        const long n = (long)batch * tdm;
-        hipLaunchKernelGGL(dad::time_dtemb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sc + o.dtemb,
-                           sc + o.dact_slab, sv + o.temb, n, o.kslices);
+        const TimeLaunch& l = tl[5];
+        if (l.mode != DAD_OP_TG_DTEMB) return fail(DAD_E_STATE, "time chain: launch %d planned where the slab sum runs", l.mode);
+        hipLaunchKernelGGL(dad::time_dtemb_kernel, dim3(l.gx(), l.gy(), l.gz()), dim3(256), 0, st, sc + o.dtemb,
+                           sc + o.dact_slab, sv + o.temb, (long)l.M * l.N, l.K);
         HIP_TRY(hipGetLastError());
     }
-    g.M = tdm; g.N = 4 * tdm; g.K = batch; g.kslice = g.K;                 // d W3 = d temb^T mish(h1), d b3
     g.a = sc + o.dtemb; g.lda = tdm; g.w = sv + o.h1; g.ldw = 4 * tdm; g.out = time_grad_tensors[2]; g.out2 = time_grad_tensors[3];
-    if ((rc = launch_time_gemm<dad::TG_BWD_DW3>(g, 1, st)) != DAD_OK) return rc;
-    g.M = batch; g.N = 4 * tdm; g.K = tdm; g.kslice = g.K;                 // d h1 = (d temb W3) mish'(h1)
-    g.w = w3; g.ldw = 4 * tdm; g.h1 = sv + o.h1; g.out = sc + o.dh1; g.out2 = nullptr;
-    if ((rc = launch_time_gemm<dad::TG_BWD_DH1>(g, 1, st)) != DAD_OK) return rc;
-    g.M = 4 * tdm; g.N = c.dim; g.K = batch; g.kslice = g.K;               // d W1 = d h1^T emb, d b1
+    if ((rc = launch_time_gemm<dad::TG_BWD_DW3>(g, tl[6], st)) != DAD_OK) return rc;        // d W3 = d temb^T mish(h1), d b3
+    g.w = w3; g.ldw = 4 * tdm; g.h1 = sv + o.h1; g.out = sc + o.dh1; g.out2 = nullptr;      // d h1 = (d temb W3) mish'(h1)
+    if ((rc = launch_time_gemm<dad::TG_BWD_DH1>(g, tl[7], st)) != DAD_OK) return rc;
     g.a = sc + o.dh1; g.lda = 4 * tdm; g.out = time_grad_tensors[0]; g.out2 = time_grad_tensors[1];
-    return launch_time_gemm<dad::TG_BWD_DW1>(g, 1, st);
+    return launch_time_gemm<dad::TG_BWD_DW1>(g, tl[8], st);                                 // d W1 = d h1^T emb, d b1
 }
 
 int dad_fill_normal(float* x, int32_t batch, int32_t row_elems, uint64_t seed, uint64_t row_offset,
@@ -1733,6 +1733,18 @@ int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t c
     if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
     std::vector<int32_t> r;
     const int rc = backward_plan_report(*m, batch, r);      // (a batch the backward pass refuses is refused here too)
+    if (rc != DAD_OK) return rc;
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
+}
+
+int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
+    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
+    std::vector<int32_t> r;
+    const int rc = objective_plan_report(*m, batch, r);     // (a batch the objective refuses is refused here too)
     if (rc != DAD_OK) return rc;
     if (needed_out) *needed_out = (int32_t)r.size();
     std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);

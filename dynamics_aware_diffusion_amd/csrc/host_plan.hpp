@@ -1592,10 +1592,21 @@ struct ObjectiveLayout {
     size_t saved_bytes = 0, scratch_bytes = 0;    // totals: what dad_train_objective_workspace_bytes reports
 };
 constexpr int kObjectiveMaxLossBlocks = 1024;
-// Everything one objective call plans on the host, planned once: the layout, the training forward it replays and
-// (`backward`) the geometry of the backward pass, which dad_unet_backward's body takes over instead of planning again.
+// One launch of the time chain (csrc/train_objective.hpp): out[M][N] = sum over K, `kslices` slices of `kslice` k values
+// over blockIdx.z.  mode: DAD_OP_TG_* of include/dad.h (the TimeGemm of time_gemm_kernel; DAD_OP_TG_DTEMB: the slab
+// sum time_dtemb_kernel, M x N elements over K = kslices slabs).
+struct TimeLaunch {
+    int mode, M, N, K, kslice, kslices;
+    unsigned gx() const { return mode == DAD_OP_TG_DTEMB ? (unsigned)(((long)M * N + 255) / 256) : (unsigned)((M + 31) / 32); }
+    unsigned gy() const { return mode == DAD_OP_TG_DTEMB ? 1u : (unsigned)((N + 31) / 32); }
+    unsigned gz() const { return mode == DAD_OP_TG_DTEMB ? 1u : (unsigned)kslices; }
+};
+constexpr int kObjectiveForwardLaunches = 3, kObjectiveTimeLaunches = 9;
+// Everything one objective call plans on the host, planned once: the layout, the training forward it replays,
+// (`backward`) the geometry of the backward pass, which dad_unet_backward's body takes over instead of planning again,
+// and the time chain's launches in launch order (`time`: 3 forward, 6 backward; the entry points only replay them).
 // Without `backward` the scratch half of the layout stays empty (the forward does not touch `scratch`).
-struct ObjectivePlan { ObjectiveLayout o; FwdPlan fwd; TrainScratch ts; };
+struct ObjectivePlan { ObjectiveLayout o; FwdPlan fwd; TrainScratch ts; std::vector<TimeLaunch> time; };
 inline int objective_plan(const HostModel& m, int B, bool backward, ObjectivePlan& p) {
     ObjectiveLayout& o = p.o;
     FwdPlan& f = p.fwd;
@@ -1627,6 +1638,20 @@ inline int objective_plan(const HostModel& m, int B, bool backward, ObjectivePla
     o.scratch_base = ((size_t)ts.total * sizeof(float) + 255) / 256 * 256;
     o.saved_bytes = o.saved_base + (size_t)o.saved_floats * sizeof(float);
     o.scratch_bytes = o.scratch_base + (size_t)o.scratch_floats * sizeof(float);
+    {
+        const int t1 = m.cfg.time_dim, t4 = 4 * t1, E = m.cfg.dim, Wt = m.tplan.temb_width;
+        p.time = {
+            {DAD_OP_TG_FWD_H1, B, t4, E, E, 1},                     // h1 = emb W1^T + b1
+            {DAD_OP_TG_FWD_TEMB, B, t1, t4, t4, 1},                 // temb = mish(h1) W3^T + b3, act = mish(temb)
+            {DAD_OP_TG_FWD_ROWS, B, Wt, t1, t1, 1},                 // rows = act Wk^T + bk, all blocks
+            {DAD_OP_TG_BWD_DWK, Wt, t1, B, B, 1},                   // d Wk = d rows^T act, d bk
+            {DAD_OP_TG_BWD_DACT, B, t1, Wt, o.kslice, o.kslices},   // d act = d rows W, K slices in slabs
+            {DAD_OP_TG_DTEMB, B, t1, o.kslices, o.kslices, 1},      // d temb = (sum of the slabs) mish'(temb)
+            {DAD_OP_TG_BWD_DW3, t1, t4, B, B, 1},                   // d W3 = d temb^T mish(h1), d b3
+            {DAD_OP_TG_BWD_DH1, B, t4, t1, t1, 1},                  // d h1 = (d temb W3) mish'(h1)
+            {DAD_OP_TG_BWD_DW1, t4, E, B, B, 1},                    // d W1 = d h1^T emb, d b1
+        };
+    }
     if ((int)time_block_list(m).size() > 4 * DAD_MAX_LEVELS)
         first.note(fail(DAD_E_INVALID, "objective: %zu residual blocks", time_block_list(m).size()));
     return first.done();
@@ -1670,6 +1695,31 @@ inline int backward_plan_report(const HostModel& m, int B, std::vector<int32_t>&
         if (ti < (int)std::size(kWgradTaps)) ++r[DAD_BP_TAPS_TILE + 4 * ti + g.tile];
         const int32_t rec[DAD_BP_REC_INTS] = {s.taps, g.tile, sh.wshift > 0, sh.B, g.spc, g.sps, g.ksplit, fullest, last};
         r.insert(r.end(), rec, rec + DAD_BP_REC_INTS);
+    }
+    return rc;
+}
+
+// dad_debug_objective_plan: the time chain of one fused objective step at batch B (layout: include/dad.h, DAD_OP_*),
+// read from the list dad_train_objective_forward / _backward replay (ObjectivePlan::time).
+inline int objective_plan_report(const HostModel& m, int B, std::vector<int32_t>& r) {
+    ObjectivePlan p;
+    const int rc = objective_plan(m, B, true, p);
+    const long n = (long)B * traj_horizon(m) * m.cfg.transition_dim;
+    r.assign(DAD_OP_HEADER, 0);
+    r[DAD_OP_LOSS_BLOCKS] = p.o.loss_blocks;
+    r[DAD_OP_KSLICES] = p.o.kslices;
+    r[DAD_OP_KSLICE] = p.o.kslice;
+    r[DAD_OP_TEMB_WIDTH] = m.tplan.temb_width;
+    r[DAD_OP_BLOCKS] = (int32_t)time_block_list(m).size();
+    r[DAD_OP_N] = (int32_t)std::min<long>(n, INT32_MAX);
+    r[DAD_OP_RECORD_INTS] = DAD_OP_REC_INTS;
+    r[DAD_OP_LAUNCHES] = (int32_t)p.time.size();
+    for (const TimeLaunch& l : p.time) {
+        const bool gemm = l.mode != DAD_OP_TG_DTEMB;
+        const int full = std::min(l.kslice, l.K), last = l.K - (l.kslices - 1) * l.kslice;
+        const int32_t rec[DAD_OP_REC_INTS] = {l.mode, l.M, l.N, l.K, (int32_t)l.gx(), (int32_t)l.gy(), (int32_t)l.gz(),
+                                              gemm ? (full + 31) / 32 : 0, gemm ? (last + 31) / 32 : 0, gemm ? l.K % 32 : 0, l.kslice};
+        r.insert(r.end(), rec, rec + DAD_OP_REC_INTS);
     }
     return rc;
 }

@@ -414,6 +414,55 @@ int dad_debug_small_batch_plan(dad_model* m, int32_t batch, int32_t* launches_ou
 #define DAD_BP_REC_INTS 9
 int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
 
+/* The time chain of one fused objective step (dad_train_objective_forward + dad_train_objective_backward) at a batch:
+ * the list of launches the two entry points replay (host-side query, no device work; needs
+ * dad_model_set_training(m, 1) but neither weights nor dad_model_finalize; a batch the objective refuses is refused
+ * here too).  Writes min(capacity, *needed_out) int32 values to `out`:
+ *   [DAD_OP_LOSS_BLOCKS]    blocks of the loss's partial sums (at most 1024)
+ *   [DAD_OP_KSLICES]        K slices of d act = d rows . W (slabs time_dtemb_kernel adds in slice order)
+ *   [DAD_OP_KSLICE]         k values per slice (a multiple of 128)
+ *   [DAD_OP_TEMB_WIDTH]     columns of the time projections (padded widths), the K of that product
+ *   [DAD_OP_BLOCKS]         ResidualTemporalBlocks
+ *   [DAD_OP_N]              batch x horizon x transition_dim: the elements the loss is a mean of (real ones only)
+ *   [DAD_OP_RECORD_INTS]    ints per record (DAD_OP_REC_*)
+ *   [DAD_OP_LAUNCHES]       records: 9, one per launch in launch order (3 forward, 6 backward), from DAD_OP_HEADER on:
+ *     mode (DAD_OP_TG_*: the eight instantiations of time_gemm_kernel in the order of its TimeGemm enumeration, and
+ *     DAD_OP_TG_DTEMB for time_dtemb_kernel: M x N elements, K = slabs added), M, N, K of out[M][N] = sum over K, the
+ *     grid x / y / z (32 x 32 output tiles, K slices), 32-wide K chunks in a full slice (the block's four waves take
+ *     them round robin) and in the last slice, K % 32, k values per slice; the three chunk / tail fields are 0 for
+ *     DAD_OP_TG_DTEMB. */
+#define DAD_OP_LOSS_BLOCKS 0
+#define DAD_OP_KSLICES 1
+#define DAD_OP_KSLICE 2
+#define DAD_OP_TEMB_WIDTH 3
+#define DAD_OP_BLOCKS 4
+#define DAD_OP_N 5
+#define DAD_OP_RECORD_INTS 6
+#define DAD_OP_LAUNCHES 7
+#define DAD_OP_HEADER 8
+#define DAD_OP_REC_MODE 0
+#define DAD_OP_REC_M 1
+#define DAD_OP_REC_N 2
+#define DAD_OP_REC_K 3
+#define DAD_OP_REC_GRID_X 4
+#define DAD_OP_REC_GRID_Y 5
+#define DAD_OP_REC_GRID_Z 6
+#define DAD_OP_REC_CHUNKS 7
+#define DAD_OP_REC_LAST_CHUNKS 8
+#define DAD_OP_REC_KTAIL 9
+#define DAD_OP_REC_KSLICE 10
+#define DAD_OP_REC_INTS 11
+#define DAD_OP_TG_FWD_H1 0
+#define DAD_OP_TG_FWD_TEMB 1
+#define DAD_OP_TG_FWD_ROWS 2
+#define DAD_OP_TG_BWD_DWK 3
+#define DAD_OP_TG_BWD_DACT 4
+#define DAD_OP_TG_BWD_DW3 5
+#define DAD_OP_TG_BWD_DH1 6
+#define DAD_OP_TG_BWD_DW1 7
+#define DAD_OP_TG_DTEMB 8
+int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
+
 #ifdef __cplusplus
 }
 #endif

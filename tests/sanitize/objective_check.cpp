@@ -7,7 +7,11 @@
 //   * the K slices of d act = d rows . W cover temb_width exactly once in whole 128-column steps (32 per wave), and a
 //     32-column chunk never straddles two ResidualTemporalBlocks;
 //   * the time gradient list names every time-MLP tensor once, at aligned offsets, with the element counts of the
-//     expected shapes.
+//     expected shapes;
+//   * the nine launches of the time chain (ObjectivePlan::time, what the two entry points replay) come in launch order,
+//     their grids cover their outputs in 32 x 32 tiles, and every launch writes exactly the region of the layout (or
+//     the gradient slots) it is given: each store of time_gemm_kernel / time_dtemb_kernel is replayed into a byte map
+//     of that region the sanitizer watches.
 // Built and run by tests/test_objective_host.py (CPU suite).
 #include <cstdio>
 #include <set>
@@ -56,6 +60,100 @@ static void check_regions(const char* arch, int B, const char* what, const std::
             if (owner[(size_t)i] != 0) break;
             owner[(size_t)i] = (unsigned char)id;
         }
+    }
+}
+
+// Every element a launch stores, as the kernels index them (train_objective.hpp: out[i * N + j] for i < M, j < N of
+// the tiles of the grid; TG_BWD_DACT: slab blockIdx.z; weight gradients of the blocks: rows relative to the block's
+// first; bias gradients: one per row), replayed into maps of exactly the destination's size.
+static void check_time_launches(const Arch& a, const HostModel& m, int B, const ObjectivePlan& p) {
+    const ObjectiveLayout& o = p.o;
+    const long tdm = m.cfg.time_dim;
+    const int W = m.tplan.temb_width;
+    const std::vector<TimeBlockRef> blocks = time_block_list(m);
+    static const int order[kObjectiveTimeLaunches] = {DAD_OP_TG_FWD_H1, DAD_OP_TG_FWD_TEMB, DAD_OP_TG_FWD_ROWS, DAD_OP_TG_BWD_DWK, DAD_OP_TG_BWD_DACT,
+                                                      DAD_OP_TG_DTEMB, DAD_OP_TG_BWD_DW3, DAD_OP_TG_BWD_DH1, DAD_OP_TG_BWD_DW1};
+    CHECK(p.time.size() == (size_t)kObjectiveTimeLaunches, "%s B=%d: %zu time launches", a.name, B, p.time.size());
+    if (p.time.size() != (size_t)kObjectiveTimeLaunches) return;
+    auto slot = [&](size_t i) { return (long)m.time_grad_slots[i].numel; };
+    // the float count of a saved / scratch region: up to the next region's start
+    const long saved_regions[] = {o.xt, o.out, o.t_rows, o.row_index, o.h1, o.temb, o.act, o.rows, o.partial, o.saved_floats};
+    const long scratch_regions[] = {o.d_out, o.d_rows, o.dact_slab, o.dtemb, o.dh1, o.scratch_floats};
+    auto room = [&](const long* rs, size_t n, long at) {
+        for (size_t i = 0; i + 1 < n; ++i) if (rs[i] == at) return rs[i + 1] - at;
+        return -1L;
+    };
+    for (int li = 0; li < kObjectiveTimeLaunches; ++li) {
+        const TimeLaunch& l = p.time[(size_t)li];
+        CHECK(l.mode == order[li], "%s B=%d: launch %d is mode %d", a.name, B, li, l.mode);
+        CHECK(l.M > 0 && l.N > 0 && l.K > 0 && l.kslice > 0 && l.kslices > 0, "%s B=%d launch %d: %d x %d x %d, %d x %d", a.name, B, li, l.M, l.N, l.K,
+              l.kslices, l.kslice);
+        if (l.M <= 0 || l.N <= 0 || l.K <= 0 || l.kslice <= 0 || l.kslices <= 0) continue;
+        if (l.mode == DAD_OP_TG_DTEMB) {
+            const long n = (long)l.M * l.N;
+            CHECK(n == B * tdm && l.K == o.kslices && (long)l.gx() * 256 >= n && (long)(l.gx() - 1) * 256 < n && l.gy() == 1 && l.gz() == 1,
+                  "%s B=%d: slab sum over %ld elements, %d slabs, grid %u", a.name, B, n, l.K, l.gx());
+            CHECK((long)l.K * n <= room(scratch_regions, 6, o.dact_slab) && n <= room(scratch_regions, 6, o.dtemb) && n <= room(saved_regions, 10, o.temb),
+                  "%s B=%d: slab sum reads %d x %ld floats", a.name, B, l.K, n);
+            continue;
+        }
+        // the K slices cover K once, in whole chunks per wave except in the last slice
+        CHECK((long)(l.kslices - 1) * l.kslice < l.K && (long)l.kslices * l.kslice >= l.K && (l.kslices == 1 || l.kslice % 32 == 0),
+              "%s B=%d launch %d: %d slices of %d over K = %d", a.name, B, li, l.kslices, l.kslice, l.K);
+        CHECK(l.gx() == (unsigned)((l.M + 31) / 32) && l.gy() == (unsigned)((l.N + 31) / 32) && l.gz() == (unsigned)l.kslices, "%s B=%d launch %d: grid", a.name,
+              B, li);
+        // destination(s): {name, floats the destination holds, writes}
+        long want = 0, want2 = -1, have = -1;
+        switch (l.mode) {
+            case DAD_OP_TG_FWD_H1: want = B * 4 * tdm; have = room(saved_regions, 10, o.h1); CHECK(l.K == m.cfg.dim, "%s: K of h1", a.name); break;
+            case DAD_OP_TG_FWD_TEMB:
+                want = B * tdm; have = std::min(room(saved_regions, 10, o.temb), room(saved_regions, 10, o.act));
+                CHECK(l.K == 4 * tdm, "%s: K of temb", a.name);
+                break;
+            case DAD_OP_TG_FWD_ROWS: want = (long)B * W; have = room(saved_regions, 10, o.rows); CHECK(l.K == tdm, "%s: K of rows", a.name); break;
+            case DAD_OP_TG_BWD_DACT:
+                want = (long)o.kslices * B * tdm; have = room(scratch_regions, 6, o.dact_slab);
+                CHECK(l.K == W && l.kslice == o.kslice && l.kslices == o.kslices, "%s B=%d: d act slices %d x %d, layout %d x %d", a.name, B, l.kslices, l.kslice,
+                      o.kslices, o.kslice);
+                break;
+            case DAD_OP_TG_BWD_DH1: want = B * 4 * tdm; have = room(scratch_regions, 6, o.dh1); CHECK(l.K == tdm, "%s: K of d h1", a.name); break;
+            case DAD_OP_TG_BWD_DW3: want = have = slot(2); want2 = slot(3); CHECK(l.K == B, "%s: K of d W3", a.name); break;
+            case DAD_OP_TG_BWD_DW1: want = have = slot(0); want2 = slot(1); CHECK(l.K == B, "%s: K of d W1", a.name); break;
+            default: break;
+        }
+        if (l.mode == DAD_OP_TG_BWD_DWK) {
+            // per block: rows [off, off + cout) of the M = temb_width rows go to the block's own weight / bias gradient
+            CHECK(l.M == W && l.N == tdm && l.K == B, "%s B=%d: d Wk is %d x %d over %d", a.name, B, l.M, l.N, l.K);
+            std::vector<std::vector<unsigned char>> dw(blocks.size()), db(blocks.size());
+            for (size_t k = 0; k < blocks.size(); ++k) { dw[k].assign((size_t)slot(4 + 2 * k), 0); db[k].assign((size_t)slot(5 + 2 * k), 0); }
+            for (unsigned bx = 0; bx < l.gx(); ++bx) {
+                int blk = 0;
+                while (blk + 1 < (int)blocks.size() && blocks[(size_t)blk + 1].off <= (int)bx * 32) ++blk;
+                for (int i = (int)bx * 32; i < std::min(l.M, (int)bx * 32 + 32); ++i) {
+                    const long row = i - blocks[(size_t)blk].off;
+                    CHECK(row >= 0 && row < blocks[(size_t)blk].cout, "%s B=%d: row %d of d Wk leaves block %d", a.name, B, i, blk);
+                    if (row < 0 || row >= blocks[(size_t)blk].cout) continue;
+                    for (int j = 0; j < l.N; ++j) ++dw[(size_t)blk].at((size_t)(row * l.N + j));
+                    ++db[(size_t)blk].at((size_t)row);
+                }
+            }
+            for (size_t k = 0; k < blocks.size(); ++k) {
+                for (unsigned char c : dw[k]) CHECK(c == 1, "%s B=%d: an element of %s.time_mlp.1.weight.grad written %d times", a.name, B, blocks[k].base.c_str(), c);
+                for (unsigned char c : db[k]) CHECK(c == 1, "%s B=%d: an element of %s.time_mlp.1.bias.grad written %d times", a.name, B, blocks[k].base.c_str(), c);
+            }
+            continue;
+        }
+        CHECK(have >= 0 && want <= have, "%s B=%d launch %d (mode %d): writes %ld floats into %ld", a.name, B, li, l.mode, want, have);
+        if (have < 0 || want > have) continue;
+        std::vector<unsigned char> hit((size_t)want, 0);
+        for (unsigned z = 0; z < l.gz(); ++z)
+            for (unsigned bx = 0; bx < l.gx(); ++bx)
+                for (unsigned by = 0; by < l.gy(); ++by)
+                    for (int i = (int)bx * 32; i < std::min(l.M, (int)bx * 32 + 32); ++i)
+                        for (int j = (int)by * 32; j < std::min(l.N, (int)by * 32 + 32); ++j)
+                            ++hit.at((size_t)((l.mode == DAD_OP_TG_BWD_DACT ? (long)z * l.M + i : (long)i) * l.N + j));
+        for (unsigned char c : hit) CHECK(c == 1, "%s B=%d launch %d (mode %d): an output element written %d times", a.name, B, li, l.mode, c);
+        if (want2 >= 0) CHECK(want2 == l.M, "%s B=%d launch %d: %d bias gradients into %ld", a.name, B, li, l.M, want2);
     }
 }
 
@@ -110,9 +208,16 @@ static void check_arch(const Arch& a) {
 
     const int Hr = traj_horizon(m);
     for (int B : {1, 5, 9, 250, 256, 512}) {
-        ObjectiveLayout o;
-        rc = objective_layout(m, B, o);
-        CHECK(rc == DAD_OK, "%s B=%d: objective_layout: %s", a.name, B, g_err);
+        ObjectivePlan op;
+        rc = objective_plan(m, B, true, op);
+        const ObjectiveLayout& o = op.o;
+        CHECK(rc == DAD_OK, "%s B=%d: objective_plan: %s", a.name, B, g_err);
+        check_time_launches(a, m, B, op);
+        {
+            std::vector<int32_t> rep;
+            CHECK(objective_plan_report(m, B, rep) == rc && rep.size() == (size_t)(DAD_OP_HEADER + kObjectiveTimeLaunches * DAD_OP_REC_INTS),
+                  "%s B=%d: report of %zu ints", a.name, B, rep.size());
+        }
         // the existing parts: exactly what dad_train_workspace_bytes reports, rounded up to 256 bytes
         FwdPlan f;
         plan_forward(m, true, B, false, f);
@@ -170,6 +275,8 @@ int main() {
         {"tiny", 6, 32, 32, 32, {1, 2, 4}, {}, 0},
         {"tiny4", 8, 32, 32, 32, {1, 2, 2, 4}, {}, 0},
         {"tiny_td64", 6, 32, 64, 32, {1, 2, 4}, {}, 0},
+        {"tiny_td20", 6, 32, 20, 32, {1, 2, 4}, {}, 0},       // time_dim no multiple of the 32-wide tile
+        {"tiny_td72", 6, 32, 72, 32, {1, 2, 4}, {}, 0},
         {"pointmaze", 6, 128, 128, 32, {1, 2, 4}, {}, 0},
         {"halfcheetah", 23, 256, 256, 32, {1, 4, 8}, {}, 0},
         {"d48_padded", 6, 64, 48, 32, {1, 2}, {48, 96}, 0},

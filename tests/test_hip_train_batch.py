@@ -281,23 +281,17 @@ def _train_step(diff, x0, t, noise, dev, reduce="mean"):
             {k: p.grad.detach().cpu().numpy().copy() for k, p in diff.model.named_parameters()})
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("case", LARGE, ids=lambda c: c[0])
-def test_large_batch_gradients_vs_float64(case, dev):
+@functools.lru_cache(maxsize=None)
+def _large_oracle(name):
+    """The weights, the draws and the float64 oracle of a case of LARGE, computed once per run (this module and
+    tests/test_hip_objective_batch.py both ask): state, (x0, t, noise), loss / gradients / d x_t / output in float64,
+    and the fp32 oracle's own distance from them (per gradient on the scale of grad_scales, d x_t, output).  Nobody
+    writes into what this returns."""
     from dynamics_aware_diffusion_amd.utils import synth
     from oracle import denoiser as orc
-    name, td, dim, mults, H, B, ks, wb, why, props = case
+    _, td, dim, mults, H, B, ks, _, _, _ = next(c for c in LARGE if c[0] == name)
     state = synth.synth_unet_state(td, dim, mults, seed=41, affine_jitter=0.3, kernel_size=ks)
-    diff = _diffusion(td, td - 1, 1, dim, mults, H, T, state, dev, ks=ks)
-    eng = diff.model.engine(H, dev, training=True)
-    if wb is not None:
-        eng.debug_set_option("wgrad_blocks", wb)
-    path = _assert_path(name, eng.backward_plan(B), props)
     x0, t, noise = _inputs(name, B, H, td)
-    loss, out, dx, grads = _train_step(diff, x0, t, noise, dev)
-    loss2, out2, dx2, grads2 = _train_step(diff, x0, t, noise, dev)
-    assert diff.model._engine is eng, "the engine was rebuilt: the plan asserted above is not the one that ran"
-
     w = as_torch(state)
     sched = orc.schedule_buffers("cosine", T)
     x0t, tt, nz = torch.from_numpy(x0), torch.from_numpy(t), torch.from_numpy(noise)
@@ -307,16 +301,36 @@ def test_large_batch_gradients_vs_float64(case, dev):
     _, _, out64 = orc.training_loss(w64, s64, x0t.double(), tt, nz.double())
     l32, g32, dx32 = orc.training_gradients(w, sched, x0t, tt, nz)               # only to print its own distance
     _, _, out32 = orc.training_loss(w, sched, x0t, tt, nz)
-
     scales = grad_scales(g64)
+    orc_errs = {k: max_abs(g32[k].numpy(), g64[k].numpy()) / scales[k] for k in g64}
+    orc_errs["d x_t"] = max_abs(dx32.numpy(), dx64.numpy()) / float(dx64.abs().max())
+    return {"state": state, "inputs": (x0, t, noise), "l64": l64, "g64": g64, "dx64": dx64, "out64": out64, "scales": scales,
+            "orc_errs": orc_errs, "o_out": max_abs(out32.numpy(), out64.numpy())}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", LARGE, ids=lambda c: c[0])
+def test_large_batch_gradients_vs_float64(case, dev):
+    name, td, dim, mults, H, B, ks, wb, why, props = case
+    ref = _large_oracle(name)
+    state = ref["state"]
+    diff = _diffusion(td, td - 1, 1, dim, mults, H, T, state, dev, ks=ks)
+    eng = diff.model.engine(H, dev, training=True)
+    if wb is not None:
+        eng.debug_set_option("wgrad_blocks", wb)
+    path = _assert_path(name, eng.backward_plan(B), props)
+    x0, t, noise = ref["inputs"]
+    loss, out, dx, grads = _train_step(diff, x0, t, noise, dev)
+    loss2, out2, dx2, grads2 = _train_step(diff, x0, t, noise, dev)
+    assert diff.model._engine is eng, "the engine was rebuilt: the plan asserted above is not the one that ran"
+
+    l64, g64, dx64, out64, scales, orc_errs, o_out = (ref[k] for k in ("l64", "g64", "dx64", "out64", "scales", "orc_errs", "o_out"))
     assert set(grads) == set(g64)
     errs = {k: max_abs(grads[k], g64[k].numpy()) / scales[k] for k in grads}
     errs["d x_t"] = max_abs(dx, dx64.numpy()) / float(dx64.abs().max())
-    orc_errs = {k: max_abs(g32[k].numpy(), g64[k].numpy()) / scales[k] for k in grads}
-    orc_errs["d x_t"] = max_abs(dx32.numpy(), dx64.numpy()) / float(dx64.abs().max())
     worst = max(errs, key=errs.get)
     oworst = max(orc_errs, key=orc_errs.get)
-    e_out, o_out = max_abs(out, out64.numpy()), max_abs(out32.numpy(), out64.numpy())
+    e_out = max_abs(out, out64.numpy())
     e_loss = abs(loss - float(l64)) / max(1.0, abs(float(l64)))
     print(f"\n{name} ({why})\n  path: {path}\n  gradients vs float64, x max|g|: engine {errs[worst]:.2e} ({worst}), d x_t {errs['d x_t']:.2e}; "
           f"fp32 oracle {orc_errs[oworst]:.2e} ({oworst}), d x_t {orc_errs['d x_t']:.2e}\n"

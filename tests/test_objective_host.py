@@ -14,7 +14,7 @@ INVALID = -1
 
 NEW_SYMBOLS = ("dad_model_load_train_schedule", "dad_train_time_grad_count", "dad_train_time_grad_info",
                "dad_train_objective_workspace_bytes", "dad_train_objective_forward", "dad_train_objective_backward",
-               "dad_debug_objective_offsets")
+               "dad_debug_objective_offsets", "dad_debug_objective_plan")
 
 
 def _model(lib, training=True, td=6, dim=32, mults=(1, 2, 4), horizon=32):
@@ -144,6 +144,58 @@ def test_argument_errors_are_invalid_with_a_message():
         assert bwd(h) == INVALID and b"split-f16" in lib.dad_last_error()
     finally:
         lib.dad_model_destroy(h)
+
+
+def test_objective_plan_needs_training_and_a_batch():
+    import pytest
+    from dynamics_aware_diffusion_amd._engine import DadError, HipEngine
+    eng = HipEngine(transition_dim=6, dim=32, channels=(32, 64, 128), horizon=32, n_timesteps=20)
+    with pytest.raises(DadError, match="dad_model_set_training"):
+        eng.objective_plan(4)
+    eng = HipEngine(transition_dim=6, dim=32, channels=(32, 64, 128), horizon=32, n_timesteps=20, training=True)
+    for bad in (0, -3):
+        with pytest.raises(DadError):
+            eng.objective_plan(bad)
+    need = C.c_int32()
+    assert eng.lib.dad_debug_objective_plan(None, 4, None, 0, C.byref(need)) == INVALID
+    assert eng.lib.dad_debug_objective_plan(eng._h, 4, None, 5, C.byref(need)) == INVALID      # capacity without a buffer
+    # a short buffer is filled as far as it goes and the full length is reported
+    buf = (C.c_int32 * 8)()
+    assert eng.lib.dad_debug_objective_plan(eng._h, 4, buf, 8, C.byref(need)) == 0
+    assert need.value == 8 + 9 * 11 and buf[6] == 11 and buf[7] == 9
+
+
+def test_objective_plan_of_one_hand_computed_case():
+    """The tiny net (dim = time_dim = 32, channels 32 / 64 / 128: temb_width = 4 * 224 = 896) at batch 250, worked out
+    from the kernel's own statement (32 x 32 output tiles, 32-wide K chunks): ceil(250 / 32) = 8 row tiles, 250 = 7 * 32
+    + 26 as K.  d act = d rows . W: 8 x 1 output tiles, so min(256 / 8, 896 / 128) = 7 slices of 128 columns."""
+    from dynamics_aware_diffusion_amd._engine import TIME_GEMM_MODES, HipEngine
+    eng = HipEngine(transition_dim=6, dim=32, channels=(32, 64, 128), horizon=32, n_timesteps=20, training=True)
+    p = eng.objective_plan(250)
+    assert {k: v for k, v in p.items() if k != "launches"} == {
+        "loss_blocks": 47, "kslices": 7, "kslice": 128, "temb_width": 896, "blocks": 12, "n": 250 * 32 * 6}
+    want = [  # mode, M, N, K, grid, chunks, last_chunks, ktail, kslice
+        ("FWD_H1", 250, 128, 32, (8, 4, 1), 1, 1, 0, 32),
+        ("FWD_TEMB", 250, 32, 128, (8, 1, 1), 4, 4, 0, 128),
+        ("FWD_ROWS", 250, 896, 32, (8, 28, 1), 1, 1, 0, 32),
+        ("BWD_DWK", 896, 32, 250, (28, 1, 1), 8, 8, 26, 250),
+        ("BWD_DACT", 250, 32, 896, (8, 1, 7), 4, 4, 0, 128),
+        ("DTEMB", 250, 32, 7, (32, 1, 1), 0, 0, 0, 7),
+        ("BWD_DW3", 32, 128, 250, (1, 4, 1), 8, 8, 26, 250),
+        ("BWD_DH1", 250, 128, 32, (8, 4, 1), 1, 1, 0, 32),
+        ("BWD_DW1", 128, 32, 250, (4, 1, 1), 8, 8, 26, 250),
+    ]
+    fields = ("mode", "M", "N", "K", "grid", "chunks", "last_chunks", "ktail", "kslice")
+    assert len(p["launches"]) == 9 and len(TIME_GEMM_MODES) == 9
+    for got, w in zip(p["launches"], want):
+        assert got == dict(zip(fields, w)), (got, w)
+    # the grids multiply out to the 32 x 32 tiles of every output (and the slab sum's 256 elements per block)
+    blocks = sum(q["grid"][0] * q["grid"][1] * q["grid"][2] for q in p["launches"])
+    assert blocks == 32 + 8 + 224 + 28 + 56 + 32 + 4 + 32 + 4
+    # the loss's partial sums: one block per 1024 elements, at most 1024 of them
+    assert eng.objective_plan(1)["loss_blocks"] == 1 and eng.objective_plan(1)["n"] == 192
+    big = HipEngine(transition_dim=17, dim=32, channels=(32, 64), horizon=128, n_timesteps=20, training=True).objective_plan(512)
+    assert big["n"] == 512 * 128 * 17 > 1 << 20 and big["loss_blocks"] == 1024
 
 
 def test_engine_gradient_lists_are_disjoint():
