@@ -116,6 +116,10 @@ ABI = {
     "dad_debug_objective_offsets": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "dad_debug_objective_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                            C.POINTER(C.c_int32)]),
+    "dad_debug_forward_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                         C.POINTER(C.c_int32)]),
+    "dad_debug_kernel_registered": (C.c_int, [C.c_int32] * 4),
+    "dad_debug_small_kernel_exists": (C.c_int, [C.c_int32] * 8),
     "dad_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "dad_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double)]),
@@ -175,6 +179,35 @@ LOSS_TYPES = {"l1": 1, "l2": 2}           # DAD_LOSS_* of include/dad.h
 TABLES = {"sinusoid": 0, "time_mlp": 1, "blocks": 2}      # DAD_TABLE_* of include/dad.h
 # DAD_OP_TG_* of include/dad.h: the eight modes of time_gemm_kernel, then time_dtemb_kernel
 TIME_GEMM_MODES = ("FWD_H1", "FWD_TEMB", "FWD_ROWS", "BWD_DWK", "BWD_DACT", "BWD_DW3", "BWD_DH1", "BWD_DW1", "DTEMB")
+
+
+# DAD_FP_* of include/dad.h: the records of dad_debug_forward_plan
+FP_REC_FIELDS = ("conv", "sub", "cfg", "taps", "stride", "flags", "kc", "kslices", "gn_npt", "ntiles_n", "mtiles", "part_tile")
+FP_CC_FIELDS = ("conv", "taps", "stride", "wide", "ride", "big", "ride_in", "tile_rows", "windowed", "slice_ch", "kslices",
+                "ntiles", "res_kind")
+FP_FINAL_KERNELS = (None, "final_posterior_kernel", "final_cc_kernel")
+FP_FLAGS = ("x3", "bdir", "ragged", "res", "padded", "windowed")      # bits 0..5 of a record's flag word
+
+
+def registered_kernels():
+    """Every kernel key the planner says exists, in the form HipEngine.forward_plan reports them: the conv-GEMM
+    instantiations (dad_debug_kernel_registered over its whole domain) and the small-batch ones
+    (dad_debug_small_kernel_exists).  Returns (gemm keys, cc keys, ccw keys) as sets; host logic only."""
+    lib = load_library()
+    gemm = {("gemm", cfg, taps, stride, f) for cfg in range(10) for taps in range(1, 8) for stride in (1, 2) for f in range(64)
+            if lib.dad_debug_kernel_registered(cfg, taps, stride, f)}
+    cc, ccw = set(), set()
+    for taps in range(1, 8):
+        for stride in (1, 2):
+            for ride in (0, 1):
+                for rows in (8, 16, 32, 64):
+                    for a in (0, 1):
+                        for win in (0, 1):
+                            if lib.dad_debug_small_kernel_exists(taps, stride, ride, 0, a, 0, rows, win):
+                                cc.add(("cc", taps, stride, ride, a, rows, win))
+                        if lib.dad_debug_small_kernel_exists(taps, stride, ride, 1, 0, a, rows, 0):
+                            ccw.add(("ccw", taps, stride, ride, a, rows))
+    return gemm, cc, ccw
 
 
 def sinusoid_table(n_timesteps: int, dim: int) -> torch.Tensor:
@@ -746,6 +779,35 @@ class HipEngine:
             launches.append(q)
         return {"loss_blocks": r[0], "kslices": r[1], "kslice": r[2], "temb_width": r[3], "blocks": r[4], "n": r[5],
                 "launches": launches}
+
+    def forward_plan(self, batch: int, mode: int = 0) -> dict:
+        """What one evaluation launches at `batch` under the current debug options (dad_debug_forward_plan: host logic
+        only, needs neither weights nor a device).  ``mode``: 0 the shared-timestep forward (may take the small-batch
+        kernels), 1 the same on the batch kernels (per-row timesteps), 2 the training forward, 3 the data-gradient
+        convs of the backward pass (2 / 3 need ``training=True``).  Returns ``mode``, ``batch``, ``small`` (the
+        small-batch plan is taken), ``final`` (grid x, grid y, kernel name or None) and ``launches``: one dict per
+        launch with the fields of DAD_FP_REC_* (``flags``: the flag word of kernel_registered_f) or, with ``small``,
+        of DAD_FP_CC_*; each has ``key``, the instantiation it runs: ("gemm", cfg, taps, stride, flags),
+        ("cc", taps, stride, ride, big, rows, windowed) or ("ccw", taps, stride, ride, ride_in, rows)."""
+        need = C.c_int32()
+        _check(self.lib, self.lib.dad_debug_forward_plan(self._h, int(batch), int(mode), None, 0, C.byref(need)))
+        buf = (C.c_int32 * need.value)()
+        _check(self.lib, self.lib.dad_debug_forward_plan(self._h, int(batch), int(mode), buf, need.value, C.byref(need)))
+        r = list(buf)
+        small = bool(r[2])
+        fields = FP_CC_FIELDS if small else FP_REC_FIELDS
+        assert r[4] == len(fields) and len(r) - 8 == r[3] * r[4]
+        launches = []
+        for at in range(8, len(r), len(fields)):
+            q = dict(zip(fields, r[at:at + len(fields)]))
+            if not small:
+                q["key"] = ("gemm", q["cfg"], q["taps"], q["stride"], q["flags"])
+            elif q["wide"]:
+                q["key"] = ("ccw", q["taps"], q["stride"], q["ride"], q["ride_in"], q["tile_rows"])
+            else:
+                q["key"] = ("cc", q["taps"], q["stride"], q["ride"], q["big"], q["tile_rows"], q["windowed"])
+            launches.append(q)
+        return {"mode": r[0], "batch": r[1], "small": small, "final": (r[5], r[6], FP_FINAL_KERNELS[r[7]]), "launches": launches}
 
     def mish(self, x: torch.Tensor) -> torch.Tensor:
         """The conv epilogue's Mish applied to a device tensor (test hook)."""

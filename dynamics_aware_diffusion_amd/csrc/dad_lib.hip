@@ -1751,6 +1751,28 @@ int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t 
     return DAD_OK;
 }
 
+int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (!m || batch <= 0 || mode < 0 || mode > 3 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    if (mode >= 2 && !m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
+    if (mode == 3 && m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
+    std::vector<int32_t> r;
+    const int rc = forward_plan_report(*m, batch, mode, r);     // (a batch the call refuses is refused here too)
+    if (rc != DAD_OK) return rc;
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
+}
+
+int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32_t flags) {
+    if (taps < 1 || taps > kRegMaxTaps || stride < 1 || stride > 2 || flags < 0 || flags >= (1 << kRegFlags)) return 0;
+    return kernel_registered_f(cfg, taps, stride, flags) ? 1 : 0;
+}
+
+int dad_debug_small_kernel_exists(int32_t taps, int32_t stride, int32_t ride, int32_t wide, int32_t big, int32_t ride_in,
+                                  int32_t rows, int32_t windowed) {
+    return small_kernel_exists(taps, stride, ride != 0, wide != 0, big != 0, ride_in != 0, rows, windowed != 0) ? 1 : 0;
+}
+
 int dad_profile_enable(dad_model* m, int32_t on) {
     if (!m) return fail(DAD_E_INVALID, "null model");
     m->profile = on != 0;

@@ -1040,6 +1040,12 @@ struct LaunchGeom {
     uint64_t xswz = 0;
 };
 
+// The general staging path (RAGGED kernels): a K chunk may straddle the concat's seam or the end of the channels, or
+// a source's rows are not whole float4s.
+inline bool ragged_operands(const ConvOp& op, int kc) {
+    const int cin = op.cin0 + op.cin1;
+    return (op.cin0 & 3) != 0 || (op.cin1 & 3) != 0 || op.cin0 % kc != 0 || cin % kc != 0;
+}
 // Does the residual conv ride in `op`'s launch, given its tile and grid-level split?  (Needs the whole K in one
 // block and the sixth tap's weight rows in LDS.)  The one statement of the rule: a 1x1 residual conv is launched
 // on its own exactly where its carrier's LaunchGeom::fused is false (plan_forward).
@@ -1047,6 +1053,9 @@ inline bool fused_at(const HostModel& m, const ConvOp& op, const LaunchGeom& g) 
     if (!op.ride || !m.fuse_residual || g.cfg < 0) return false;
     const TileCfg& t = kTiles[g.cfg];
     if (t.KC < 16 || g.split.kslices != 1) return false;
+    // Tile 5's ride with whole K chunks (conv_gemm_f32<32, 64, 2, 16, k, 1, RAGGED = false, RES>) computes wrong values
+    // ("Forward kernel census"; tests/test_hip_forward_paths.py): the 1x1 conv is launched on its own there.
+    if (g.cfg == 5 && !ragged_operands(op, g.kc)) return false;
     return dad::conv_lds_floats(t.BM, t.BN, g.kc, op.taps, op.Lin, op.Lout, t.SK, false, op.taps + 1) *
                sizeof(float) <= dad::kLdsBytes;
 }
@@ -1113,7 +1122,7 @@ inline int plan_launch(const HostModel& m, const ConvOp& op, int batch, LaunchGe
                     op.name.c_str(), op.M, op.cout / 8, op.Lout);
     const TileCfg& t = kTiles[g.cfg];
     const int cin = op.cin0 + op.cin1;
-    g.ragged = (op.cin0 & 3) != 0 || (op.cin1 & 3) != 0 || op.cin0 % g.kc != 0 || cin % g.kc != 0;
+    g.ragged = ragged_operands(op, g.kc);
     if (g.ragged && !(op.stride == 1 && (op.taps & 1) == 1))
         return fail(DAD_E_INVALID, "channel count %d+%d needs the general staging path, which exists "
                     "for stride-1 k-tap and 1x1 convs only", op.cin0, op.cin1);
@@ -1721,6 +1730,70 @@ inline int objective_plan_report(const HostModel& m, int B, std::vector<int32_t>
                                               gemm ? (full + 31) / 32 : 0, gemm ? (last + 31) / 32 : 0, gemm ? l.K % 32 : 0, l.kslice};
         r.insert(r.end(), rec, rec + DAD_OP_REC_INTS);
     }
+    return rc;
+}
+
+// The small-batch kernels as one domain for a walk (dad_debug_small_kernel_exists): conv_cc by (taps, stride, ride, big,
+// rows, windowed) — it has no `ride_in` form, a consumer of ride slabs runs the same instantiation — and conv_ccw
+// (`wide`) by (taps, stride, ride, ride_in, rows): 18 + 20 kernels.
+constexpr bool small_kernel_exists(int taps, int stride, bool ride, bool wide, bool big, bool ride_in, int rows, bool windowed) {
+    if (wide) return !big && cc_kernel_exists(taps, stride, ride, true, false, rows, windowed);
+    return !ride_in && cc_kernel_exists(taps, stride, ride, false, big, rows, windowed);
+}
+
+// dad_debug_forward_plan: what one forward evaluation (modes 0 .. 2) or the data-gradient half of one backward pass
+// (mode 3) launches at a batch (layout: include/dad.h, DAD_FP_*).  forward_plan_encode writes down a description the
+// entry points replay — `f`: plan_forward's (modes 0 .. 2), `ts`: train_scratch's (mode 3) — and decides nothing;
+// forward_plan_report plans the call the mode names, as its entry point does, and encodes that.
+inline int32_t launch_flags(const ConvOp& op, const LaunchGeom& g) {
+    return (op.x3 ? 1 : 0) | (op.bdir ? 2 : 0) | (g.ragged ? 4 : 0) | (g.fused ? 8 : 0) | (g.padded ? 16 : 0) | (g.windowed ? 32 : 0);
+}
+inline void forward_plan_encode(const HostModel& m, int mode, int batch, const FwdPlan* f, const TrainScratch* ts,
+                                std::vector<int32_t>& r) {
+    r.assign(DAD_FP_HEADER, 0);
+    r[DAD_FP_MODE] = mode;
+    r[DAD_FP_BATCH] = batch;
+    r[DAD_FP_FINAL_KERNEL] = DAD_FP_FINAL_NONE;
+    auto conv = [&](int index, int sub, const ConvOp& op, const LaunchGeom& g) {
+        const int bn = g.cfg >= 0 ? kTiles[g.cfg].BN : 0;
+        const bool part = g.cfg >= 0 && op.Lout <= bn && batch % (bn / op.Lout) != 0;
+        const int32_t rec[DAD_FP_REC_INTS] = {index, sub, g.cfg, op.taps, op.stride, launch_flags(op, g), g.kc, g.split.kslices,
+                                              g.gn_npt, g.ntiles_n, g.mtiles, part};
+        r.insert(r.end(), rec, rec + DAD_FP_REC_INTS);
+        ++r[DAD_FP_RECORDS];
+    };
+    r[DAD_FP_RECORD_INTS] = DAD_FP_REC_INTS;
+    if (mode == 3) {
+        size_t nd = 0;
+        for (const BwdStep& s : m.bsteps)
+            if (s.kind == BK_DGRAD && nd < ts->dgrads.size()) conv(s.conv, s.sub, bwd_op(m, s), ts->dgrads[nd++].g);
+        return;
+    }
+    const Plan& plan = f->train ? m.tplan : m.plan;
+    r[DAD_FP_FINAL_GX] = (int32_t)f->final_gx;
+    r[DAD_FP_FINAL_GY] = (int32_t)f->final_gy;
+    r[DAD_FP_FINAL_KERNEL] = f->cc.ok ? DAD_FP_FINAL_CC : DAD_FP_FINAL_POSTERIOR;
+    if (!f->cc.ok) {
+        for (const FwdLaunch& l : f->launches) conv(l.conv, 0, plan.convs[l.conv], l.g);
+        return;
+    }
+    r[DAD_FP_SMALL] = 1;
+    r[DAD_FP_RECORD_INTS] = DAD_FP_CC_INTS;
+    for (size_t i = 0; i < f->cc.ops.size(); ++i) {
+        const CcOp& o = f->cc.ops[i];
+        if (!o.launched) continue;
+        const ConvOp& op = plan.convs[i];
+        const int32_t rec[DAD_FP_CC_INTS] = {(int32_t)i, op.taps, op.stride, o.wide, op.ride, o.big, o.ride_in, o.tile_rows,
+                                             op.Lout > 32, o.slice_ch, o.kslices, o.ntiles, o.res_kind};
+        r.insert(r.end(), rec, rec + DAD_FP_CC_INTS);
+        ++r[DAD_FP_RECORDS];
+    }
+}
+inline int forward_plan_report(const HostModel& m, int batch, int mode, std::vector<int32_t>& r) {
+    FwdPlan f;
+    TrainScratch ts;
+    const int rc = mode == 3 ? train_scratch(m, batch, ts) : plan_forward(m, mode == 2, batch, mode == 0, f);
+    forward_plan_encode(m, mode, batch, &f, &ts, r);
     return rc;
 }
 

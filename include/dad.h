@@ -463,6 +463,79 @@ int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t c
 #define DAD_OP_TG_DTEMB 8
 int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
 
+/* What one forward evaluation launches at a batch under the current debug options: the description the entry point
+ * itself replays (csrc/host_plan.hpp: FwdPlan of plan_forward; mode 3: TrainScratch of train_scratch), written down
+ * (host-side query, no device work; needs neither weights nor dad_model_finalize; modes 2 / 3 need
+ * dad_model_set_training(m, 1); a batch the call refuses is refused here too).  `mode`:
+ *   0  dad_unet_forward / dad_denoise_step with one shared timestep (may take the small-batch kernels)
+ *   1  the same evaluation on the batch kernels: dad_unet_forward_rows (per-row timesteps)
+ *   2  dad_unet_forward_train (the training plan)
+ *   3  the data-gradient conv launches of dad_unet_backward, in launch order
+ * Writes min(capacity, *needed_out) int32 values to `out`:
+ *   [DAD_FP_MODE] [DAD_FP_BATCH]   as asked
+ *   [DAD_FP_SMALL]          1: the small-batch plan is taken (csrc/conv_cc.hpp, conv_ccw.hpp), the records are DAD_FP_CC_*
+ *   [DAD_FP_RECORDS]        records that follow from DAD_FP_HEADER on, [DAD_FP_RECORD_INTS] ints each
+ *   [DAD_FP_FINAL_GX] [DAD_FP_FINAL_GY]   grid of the final kernel (0 in mode 3)
+ *   [DAD_FP_FINAL_KERNEL]   DAD_FP_FINAL_POSTERIOR (final_posterior_kernel), DAD_FP_FINAL_CC (final_cc_kernel) or
+ *                           DAD_FP_FINAL_NONE (mode 3)
+ * One record per conv-GEMM launch in launch order (a 1x1 residual conv that rides in its carrier's launch has none):
+ *   conv index into the plan (mode 3: the forward conv whose data gradient this is, -1 = final_conv[1]), sub (mode 3:
+ *   which of that conv's data-gradient launches), tile cfg, taps, stride, flags (bit 0 x3, 1 bdir, 2 ragged, 3 res —
+ *   the ride —, 4 padded, 5 windowed: the flag word of kernel_registered_f, so (cfg, taps, stride, flags) names the
+ *   instantiation), K chunk, grid-level K slices, npt of the gn_pass_kernel<npt> launch that follows (0: none),
+ *   N tiles, M tiles, 1 when the last N tile holds fewer samples than it has room for.
+ * With [DAD_FP_SMALL] one record per launched small-batch conv instead:
+ *   conv index, taps, stride, wide (conv_ccw), ride, big, ride_in, rows per tile (16 / 32), windowed, channels per K
+ *   slice, K slices, N tiles, res_kind (how the output's residual reaches its consumer: 0 none, 1 the trajectory,
+ *   2 a finished tensor, 3 the ride slabs of a carrier, 4 the slabs of a stand-alone 1x1 conv). */
+#define DAD_FP_MODE 0
+#define DAD_FP_BATCH 1
+#define DAD_FP_SMALL 2
+#define DAD_FP_RECORDS 3
+#define DAD_FP_RECORD_INTS 4
+#define DAD_FP_FINAL_GX 5
+#define DAD_FP_FINAL_GY 6
+#define DAD_FP_FINAL_KERNEL 7
+#define DAD_FP_HEADER 8
+#define DAD_FP_FINAL_NONE 0
+#define DAD_FP_FINAL_POSTERIOR 1
+#define DAD_FP_FINAL_CC 2
+#define DAD_FP_REC_CONV 0
+#define DAD_FP_REC_SUB 1
+#define DAD_FP_REC_CFG 2
+#define DAD_FP_REC_TAPS 3
+#define DAD_FP_REC_STRIDE 4
+#define DAD_FP_REC_FLAGS 5
+#define DAD_FP_REC_KC 6
+#define DAD_FP_REC_KSLICES 7
+#define DAD_FP_REC_GN_NPT 8
+#define DAD_FP_REC_NTILES_N 9
+#define DAD_FP_REC_MTILES 10
+#define DAD_FP_REC_PART_TILE 11
+#define DAD_FP_REC_INTS 12
+#define DAD_FP_CC_CONV 0
+#define DAD_FP_CC_TAPS 1
+#define DAD_FP_CC_STRIDE 2
+#define DAD_FP_CC_WIDE 3
+#define DAD_FP_CC_RIDE 4
+#define DAD_FP_CC_BIG 5
+#define DAD_FP_CC_RIDE_IN 6
+#define DAD_FP_CC_TILE_ROWS 7
+#define DAD_FP_CC_WINDOWED 8
+#define DAD_FP_CC_SLICE_CH 9
+#define DAD_FP_CC_KSLICES 10
+#define DAD_FP_CC_NTILES 11
+#define DAD_FP_CC_RES_KIND 12
+#define DAD_FP_CC_INTS 13
+int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out);
+/* 1 where the conv-GEMM instantiation (tile cfg, taps, stride, flag word as above) exists: the planner's one statement of
+ * it (kernel_registered_f), whose domain is cfg 0..9, taps 1..7, stride 1..2, flags 0..63.  No device call. */
+int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32_t flags);
+/* 1 where the small-batch conv instantiation exists (cc_kernel_exists): conv_cc by (taps, stride, ride, big, rows,
+ * windowed) with wide = ride_in = 0, conv_ccw by (taps, stride, ride, ride_in, rows) with wide = 1, big = windowed = 0. */
+int dad_debug_small_kernel_exists(int32_t taps, int32_t stride, int32_t ride, int32_t wide, int32_t big, int32_t ride_in,
+                                  int32_t rows, int32_t windowed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,79 @@ static std::vector<float> ref_bfinal_image(const HostModel& m) {
     return out;
 }
 
+// dad_debug_forward_plan: the report must say what the description it was read from says — every field of every launch, in
+// order, and the kernel its flag word names must be the one launch_conv looks up (and must exist).  `f`: modes 0 .. 2,
+// `ts`: mode 3.  Counts the reports it compared.
+static long g_reports = 0;
+static void check_forward_report(const HostModel& m, int mode, int B, const FwdPlan* f, const TrainScratch* ts, int rc_plan) {
+    std::vector<int32_t> r;
+    const int rc = forward_plan_report(m, B, mode, r);
+    CHECK(rc == rc_plan, "mode %d B=%d: the plan report returns %d, the description %d", mode, B, rc, rc_plan);
+    CHECK(r.size() >= DAD_FP_HEADER && r[DAD_FP_MODE] == mode && r[DAD_FP_BATCH] == B, "mode %d B=%d: report header", mode, B);
+    if (r.size() < DAD_FP_HEADER) return;
+    const int n = r[DAD_FP_RECORDS], ints = r[DAD_FP_RECORD_INTS];
+    CHECK(r.size() == (size_t)DAD_FP_HEADER + (size_t)n * ints, "mode %d B=%d: %zu ints for %d records of %d", mode, B, r.size(), n, ints);
+    if (r.size() != (size_t)DAD_FP_HEADER + (size_t)n * ints) return;
+    ++g_reports;
+    auto conv = [&](const int32_t* q, int index, int sub, const ConvOp& op, const LaunchGeom& g, bool ok) {
+        const int fl = q[DAD_FP_REC_FLAGS];
+        CHECK(q[DAD_FP_REC_CONV] == index && q[DAD_FP_REC_SUB] == sub && q[DAD_FP_REC_CFG] == g.cfg && q[DAD_FP_REC_TAPS] == op.taps &&
+              q[DAD_FP_REC_STRIDE] == op.stride && q[DAD_FP_REC_KC] == g.kc && q[DAD_FP_REC_KSLICES] == g.split.kslices &&
+              q[DAD_FP_REC_GN_NPT] == g.gn_npt && q[DAD_FP_REC_NTILES_N] == g.ntiles_n && q[DAD_FP_REC_MTILES] == g.mtiles,
+              "%s mode %d B=%d: report record differs from the launch", op.name.c_str(), mode, B);
+        CHECK(((fl & 1) != 0) == op.x3 && ((fl & 2) != 0) == op.bdir && ((fl & 4) != 0) == g.ragged && ((fl & 8) != 0) == g.fused &&
+              ((fl & 16) != 0) == g.padded && ((fl & 32) != 0) == g.windowed && fl < (1 << kRegFlags),
+              "%s mode %d B=%d: flag word %d", op.name.c_str(), mode, B, fl);
+        if (!ok) return;
+        CHECK(kernel_registered_f(g.cfg, op.taps, op.stride, fl) &&
+              kernel_registered(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded, g.windowed),
+              "%s mode %d B=%d: the report names a kernel that does not exist", op.name.c_str(), mode, B);
+        // samples the launch's N tiles have room for against the batch
+        const TileCfg& t = kTiles[g.cfg];
+        const long room = op.Lout > t.BN ? B : (long)g.ntiles_n * (t.BN / op.Lout);
+        CHECK((q[DAD_FP_REC_PART_TILE] != 0) == (room != B), "%s mode %d B=%d: part-filled tile %d, room for %ld samples", op.name.c_str(),
+              mode, B, q[DAD_FP_REC_PART_TILE], room);
+    };
+    if (mode == 3) {
+        CHECK(ints == DAD_FP_REC_INTS && !r[DAD_FP_SMALL] && r[DAD_FP_FINAL_KERNEL] == DAD_FP_FINAL_NONE && n == (int)ts->dgrads.size(),
+              "mode 3 B=%d: %d records for %zu data-gradient launches", B, n, ts->dgrads.size());
+        int k = 0;
+        for (const BwdStep& s : m.bsteps)
+            if (s.kind == BK_DGRAD && k < n) { conv(&r[DAD_FP_HEADER + (size_t)k * ints], s.conv, s.sub, bwd_op(m, s), ts->dgrads[k].g, ts->dgrads[k].ok); ++k; }
+        CHECK(k == n, "mode 3 B=%d: %d data-gradient steps, %d records", B, k, n);
+        return;
+    }
+    const Plan& plan = f->train ? m.tplan : m.plan;
+    CHECK(f->train == (mode == 2) && r[DAD_FP_FINAL_GX] == (int)f->final_gx && r[DAD_FP_FINAL_GY] == (int)f->final_gy &&
+          r[DAD_FP_FINAL_KERNEL] == (f->cc.ok ? DAD_FP_FINAL_CC : DAD_FP_FINAL_POSTERIOR) && (r[DAD_FP_SMALL] != 0) == f->cc.ok,
+          "mode %d B=%d: report of the final launch", mode, B);
+    if (!f->cc.ok) {
+        CHECK(ints == DAD_FP_REC_INTS && n == (int)f->launches.size(), "mode %d B=%d: %d records for %zu launches", mode, B, n, f->launches.size());
+        for (int k = 0; k < n && k < (int)f->launches.size(); ++k) {
+            const FwdLaunch& l = f->launches[k];
+            conv(&r[DAD_FP_HEADER + (size_t)k * ints], l.conv, 0, plan.convs[l.conv], l.g, l.ok);
+        }
+        return;
+    }
+    int launched = 0, k = 0;
+    for (const CcOp& o : f->cc.ops) launched += o.launched;
+    CHECK(ints == DAD_FP_CC_INTS && n == launched && f->launches.empty(), "mode %d B=%d: %d records for %d small-batch launches", mode, B, n, launched);
+    for (size_t i = 0; i < f->cc.ops.size() && k < n; ++i) {
+        const CcOp& o = f->cc.ops[i];
+        if (!o.launched) continue;
+        const ConvOp& op = plan.convs[i];
+        const int32_t* q = &r[DAD_FP_HEADER + (size_t)k++ * ints];
+        CHECK(q[DAD_FP_CC_CONV] == (int)i && q[DAD_FP_CC_TAPS] == op.taps && q[DAD_FP_CC_STRIDE] == op.stride && (q[DAD_FP_CC_WIDE] != 0) == o.wide &&
+              (q[DAD_FP_CC_RIDE] != 0) == op.ride && (q[DAD_FP_CC_BIG] != 0) == o.big && (q[DAD_FP_CC_RIDE_IN] != 0) == o.ride_in &&
+              q[DAD_FP_CC_TILE_ROWS] == o.tile_rows && (q[DAD_FP_CC_WINDOWED] != 0) == (op.Lout > 32) && q[DAD_FP_CC_SLICE_CH] == o.slice_ch &&
+              q[DAD_FP_CC_KSLICES] == o.kslices && q[DAD_FP_CC_NTILES] == o.ntiles && q[DAD_FP_CC_RES_KIND] == o.res_kind,
+              "%s B=%d: small-batch report record differs from the launch", op.name.c_str(), B);
+        // the instantiation run_conv_cc looks up: conv_ccw by ride_in, conv_cc by big and windowed
+        CHECK(small_kernel_exists(op.taps, op.stride, op.ride, o.wide, o.wide ? false : o.big, o.wide ? o.ride_in : false, o.tile_rows, op.Lout > 32),
+              "%s B=%d: the report names a small-batch kernel that does not exist", op.name.c_str(), B);
+    }
+}
+
 static void check_arch(const Arch& a, int precision) {
     HostModel m;
     dad_cfg& c = m.cfg;
@@ -362,6 +435,12 @@ static void check_arch(const Arch& a, int precision) {
                 rc = plan_forward(m, false, B, false, f);
                 CHECK(rc == DAD_OK || force >= 0, "B=%d: %s", B, g_err);
                 CHECK(f.bytes == ws && !f.cc.ok && !f.train && f.batch == B, "B=%d: description of another call (%zu bytes, the query says %zu)", B, f.bytes, ws);
+                check_forward_report(m, 1, B, &f, nullptr, rc);
+                {   // ... and of the shared-timestep call, which may take the small-batch kernels
+                    FwdPlan f0;
+                    const int rc0 = plan_forward(m, false, B, true, f0);
+                    check_forward_report(m, 0, B, &f0, nullptr, rc0);
+                }
                 CHECK(workspace_bytes(m, B) == ws, "B=%d: the size query depends on who asks", B);
                 std::vector<int> at(P.convs.size(), -1);         // conv -> its place in the list
                 bool all_ok = true;
@@ -414,6 +493,7 @@ static void check_arch(const Arch& a, int precision) {
             FwdPlan f;
             CHECK(plan_forward(m, false, B, true, f) == DAD_OK && f.cc.ok && f.launches.empty() && f.bytes == workspace_bytes(m, B) &&
                   f.cc.slab_floats == cc.slab_floats && f.final_gx == (unsigned)B && f.final_lds <= dad::kLdsBytes, "B=%d: small-batch description", B);
+            check_forward_report(m, 0, B, &f, nullptr, DAD_OK);
         }
         std::vector<std::pair<long, long>> spans;
         std::vector<char> finished(P.convs.size(), 0);
@@ -590,6 +670,12 @@ static void check_arch(const Arch& a, int precision) {
             TrainScratch ts;
             rc = train_scratch(m, B, ts);
             CHECK(rc == DAD_OK, "backward geometry B=%d: %s", B, g_err);
+            check_forward_report(m, 3, B, nullptr, &ts, rc);
+            {
+                FwdPlan ft;
+                const int rct = plan_forward(m, true, B, false, ft);
+                check_forward_report(m, 2, B, &ft, nullptr, rct);
+            }
             {   // the data-gradient geometries dad_unet_backward hands to its launches: a direct plan_launch of the same op
                 size_t nd = 0;
                 for (const BwdStep& s : m.bsteps) {
@@ -755,7 +841,8 @@ int main(int argc, char** argv) {
         CHECK(e.size() == 320 && e[0] == 0.0f && e[16] == 1.0f, "sinusoid table t=0");
         CHECK(std::fabs(e[32] - std::sin(1.0f)) < 1e-7, "sinusoid table t=1");
     }
+    CHECK(g_reports > 0, "no forward-plan report was compared");
     if (g_failures) { fprintf(stderr, "%d host-logic checks FAILED\n", g_failures); return 1; }
-    printf("host logic ok\n");
+    printf("host logic ok (%ld forward-plan reports equal the descriptions they were read from)\n", g_reports);
     return 0;
 }

@@ -26,9 +26,18 @@ def _oracle_eps(net, x, t):
         return orc.unet_forward(net_weights_torch(net), x, torch.full((x.shape[0],), t, dtype=torch.long))
 
 
+# (tile, net) on which NO launch runs on the forced tile: choose_tile ignores a forced tile that is not valid for a layer,
+# and the test would pass on the heuristic's tiles without having run the one it names.  These zeros are known: tile 3
+# (256 x 32, 8-channel K chunk) holds GroupNorm groups of 256 channels, which neither net has — it runs on the wide nets
+# (test_wide_group_tiles_on_big_architectures, tests/test_hip_forward_paths.py).  Everywhere else at least FORCED_TILE_MIN
+# of the 32 .. 34 launches must sit on the forced tile, in either conv arithmetic.
+FORCED_TILE_ZERO = {(3, "tiny"), (3, "pointmaze")}
+FORCED_TILE_MIN = 9
+
+
 @pytest.mark.parametrize("tile", list(range(10)))
 def test_every_tile_variant_matches_oracle(tile, dev):
-    """Force each (BM, BN, split-K, K-chunk) instantiation wherever it is valid."""
+    """Force each (BM, BN, split-K, K-chunk) instantiation wherever it is valid, and know from the plan where that is."""
     from dynamics_aware_diffusion_amd.utils import synth
     for net, B in (("tiny", 5), ("pointmaze", 9)):
         diff = build(net, cases.NETS[net][4], "cosine", dev)
@@ -36,6 +45,11 @@ def test_every_tile_variant_matches_oracle(tile, dev):
         try:
             eng.debug_set_option("cc", 0)               # tiles belong to the batch-256 kernels
             eng.debug_set_tile(tile)
+            plan = eng.forward_plan(B, 0)
+            on_tile = sum(q["cfg"] == tile for q in plan["launches"])
+            want = "none" if (tile, net) in FORCED_TILE_ZERO else f"at least {FORCED_TILE_MIN}"
+            assert not plan["small"] and (on_tile == 0 if (tile, net) in FORCED_TILE_ZERO else on_tile >= FORCED_TILE_MIN), \
+                f"tile {tile} on {net}: {on_tile} of {len(plan['launches'])} launches run on the forced tile, expected {want}"
             x = torch.from_numpy(synth.normal_like(61, f"tile{tile}.{net}", (B, 32, diff.transition_dim)))
             want = _oracle_eps(net, x, 3)
             got = diff.model(x.to(dev), 3)
@@ -192,6 +206,12 @@ def test_eight_environments_cost_less_per_plan_than_four(dev):
     assert us[8] <= 1.5 * us[4]
 
 
+# (conv_ccw launches on 16-row tiles, on 32-row tiles) of the cases below at ccw_max_rows 512: 16 rows where that needs no
+# more N tiles than 32 would or where a 32-row tile's K slice would halve (ccw_prefer16), else 32
+WIDE_TILE_ROWS = {("halfcheetah", 1): (19, 0), ("halfcheetah", 2): (18, 1), ("halfcheetah", 5): (12, 7), ("halfcheetah", 16): (19, 0),
+                  ("door", 1): (19, 0), ("door", 3): (18, 1), ("door", 4): (18, 1), ("door", 16): (19, 0)}
+
+
 @pytest.mark.parametrize("net,B", [("halfcheetah", 1), ("halfcheetah", 2), ("halfcheetah", 5), ("halfcheetah", 16),
                                    ("door", 1), ("door", 3), ("door", 4), ("door", 16)])
 def test_wide_nets_small_batches_take_the_streamed_weight_kernels(net, B, dev):
@@ -209,6 +229,10 @@ def test_wide_nets_small_batches_take_the_streamed_weight_kernels(net, B, dev):
     try:
         launches, wide = eng.small_batch_plan(B)
         assert launches > 0 and wide >= 10, (launches, wide)
+        plan = eng.forward_plan(B, 0)
+        rows = tuple(sum(q["wide"] and q["tile_rows"] == r for q in plan["launches"]) for r in (16, 32))
+        assert plan["small"] and len(plan["launches"]) == launches and sum(rows) == wide and rows == WIDE_TILE_ROWS[net, B], rows
+        assert plan["final"][2] == "final_cc_kernel"
         t = 123
         x = torch.from_numpy(synth.normal_like(69, f"widecc.{net}.{B}", (B, 32, diff.transition_dim)))
         want = _oracle_eps(net, x, t).numpy()
