@@ -47,6 +47,34 @@ class DadProjectArgs(C.Structure):
     ]
 
 
+class DadOptimTensor(C.Structure):
+    _fields_ = [
+        ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("ema", C.c_void_p), ("numel", C.c_int64), ("group", C.c_int32),
+    ]
+
+
+class DadOptimGroup(C.Structure):
+    _fields_ = [
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("weight_decay", C.c_float), ("step_size", C.c_float), ("bc2_sqrt", C.c_float),
+        ("decoupled", C.c_int32), ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float),
+    ]
+
+
+class DadOptimArgs(C.Structure):
+    _fields_ = [
+        ("groups", C.POINTER(DadOptimGroup)), ("n_groups", C.c_int32), ("max_grad_norm", C.c_float),
+        ("ema_decay", C.c_float), ("grad_norm_out", C.c_void_p),
+    ]
+
+
+OPTIM_MAX_GROUPS = 8
+# DAD_OS_* of include/dad.h: header and record of dad_debug_optim_plan
+OS_HEADER = ("chunk", "chunks", "grid", "partials", "record_ints")
+OS_REC_FIELDS = ("tensor", "first", "first_hi", "count", "block")
+
+
 # name -> (restype, argtypes); also the list of symbols include/dad.h declares.
 ABI = {
     "dad_last_error": (C.c_char_p, []),
@@ -120,6 +148,11 @@ ABI = {
                                          C.POINTER(C.c_int32)]),
     "dad_debug_kernel_registered": (C.c_int, [C.c_int32] * 4),
     "dad_debug_small_kernel_exists": (C.c_int, [C.c_int32] * 8),
+    "dad_optim_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "dad_optim_destroy": (None, [C.c_void_p]),
+    "dad_optim_step": (C.c_int, [C.c_void_p, C.POINTER(DadOptimTensor), C.c_int32, C.POINTER(DadOptimArgs), C.c_void_p]),
+    "dad_debug_optim_plan": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                       C.POINTER(C.c_int32)]),
     "dad_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "dad_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double)]),
@@ -208,6 +241,28 @@ def registered_kernels():
                         if lib.dad_debug_small_kernel_exists(taps, stride, ride, 1, 0, a, rows, 0):
                             ccw.add(("ccw", taps, stride, ride, a, rows))
     return gemm, cc, ccw
+
+
+def optim_plan(numel: Sequence[int]) -> dict:
+    """The work split of one optimiser step over tensors of these sizes (dad_debug_optim_plan; host logic only):
+    chunk size, chunks, grid, partials and one record per chunk, with ``first`` as the whole element index."""
+    lib = load_library()
+    n = len(numel)
+    sizes = (C.c_int64 * max(n, 1))(*[int(v) for v in numel])
+    needed = C.c_int32()
+    _check(lib, lib.dad_debug_optim_plan(sizes, n, None, 0, C.byref(needed)))
+    out = (C.c_int32 * needed.value)()
+    _check(lib, lib.dad_debug_optim_plan(sizes, n, out, needed.value, C.byref(needed)))
+    head = dict(zip(OS_HEADER, out[:len(OS_HEADER)]))
+    k = head.pop("record_ints")
+    assert k == len(OS_REC_FIELDS)
+    recs = []
+    for i in range(head["chunks"]):
+        r = dict(zip(OS_REC_FIELDS, out[len(OS_HEADER) + i * k:len(OS_HEADER) + (i + 1) * k]))
+        r["first"] += r.pop("first_hi") << 31
+        recs.append(r)
+    head["records"] = recs
+    return head
 
 
 def sinusoid_table(n_timesteps: int, dim: int) -> torch.Tensor:

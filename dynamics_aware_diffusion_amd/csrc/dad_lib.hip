@@ -28,6 +28,7 @@
 #include "conv_ccw.hpp"
 #include "train_bwd.hpp"
 #include "train_objective.hpp"
+#include "optim_step.hpp"
 
 using namespace dadhost;
 
@@ -1797,6 +1798,161 @@ int dad_profile_read(dad_model* m, double* conv_ms, int64_t* conv_launches, doub
     m->ev_used = 0;
     m->prof_flops = 0;
     m->prof_launches = 0;
+    return DAD_OK;
+}
+
+}  // extern "C"  (the optimiser step follows)
+
+// ------------------------------------------------------------------ the optimiser step (csrc/optim_step.hpp)
+// The device table of a step: n descriptors, then first[n + 1] of the plan.  `image` is its host copy as last
+// uploaded; a step whose table equals it launches straight away.  An upload copies the table into a pinned staging
+// buffer nobody is reading (each buffer carries an event recorded behind its last copy; a buffer whose event has not
+// completed is left alone and another one is made) and enqueues the copy on the caller's stream, where it runs
+// behind the previous step's kernels: no synchronisation.  A table that outgrows its device buffer gets a new one;
+// the old one is freed with the object (a step still in flight may read it).
+struct dad_optim {
+    struct Stage { void* host; size_t cap; hipEvent_t done; };
+    std::vector<Stage> stages;
+    std::vector<void*> owned;             // device allocations
+    void* d_table = nullptr;
+    size_t table_cap = 0;
+    double* d_partials = nullptr;         // kOptimMaxGrid partial square sums
+    std::vector<char> image;
+    std::vector<int64_t> numel;           // sizes `plan` was made for
+    OptimPlan plan;
+};
+
+namespace {
+
+int optim_upload(dad_optim* o, const std::vector<char>& image, hipStream_t st) {
+    const size_t bytes = image.size();
+    if (o->table_cap < bytes) {
+        void* a = nullptr;
+        HIP_TRY(hipMalloc(&a, bytes * 2));
+        o->owned.push_back(a);
+        o->d_table = a;
+        o->table_cap = bytes * 2;
+    }
+    dad_optim::Stage* use = nullptr;
+    for (auto& sg : o->stages) {
+        if (sg.cap < bytes) continue;
+        const hipError_t q = hipEventQuery(sg.done);
+        if (q == hipSuccess) { use = &sg; break; }
+        if (q != hipErrorNotReady) return fail(DAD_E_HIP, "hipEventQuery failed: %s", hipGetErrorString(q));
+        (void)hipGetLastError();          // (not ready is no error of this call)
+    }
+    if (!use) {
+        dad_optim::Stage sg{nullptr, bytes * 2, nullptr};
+        HIP_TRY(hipHostMalloc(&sg.host, sg.cap, hipHostMallocDefault));
+        const hipError_t e = hipEventCreateWithFlags(&sg.done, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)hipHostFree(sg.host);
+            return fail(DAD_E_HIP, "hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
+        }
+        o->stages.push_back(sg);
+        use = &o->stages.back();
+    }
+    std::memcpy(use->host, image.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(o->d_table, use->host, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(use->done, st));
+    return DAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dad_optim_create(dad_optim** out) {
+    if (!out) return fail(DAD_E_INVALID, "null out");
+    *out = new dad_optim();
+    return DAD_OK;
+}
+
+void dad_optim_destroy(dad_optim* o) {
+    if (!o) return;
+    for (auto& sg : o->stages) { (void)hipEventDestroy(sg.done); (void)hipHostFree(sg.host); }
+    for (void* p : o->owned) (void)hipFree(p);
+    delete o;
+}
+
+int dad_optim_step(dad_optim* o, const dad_optim_tensor* tensors, int32_t n, const dad_optim_args* a, dad_stream_t s) {
+    if (!o || !tensors || !a) return fail(DAD_E_INVALID, "optimiser step: null %s", !o ? "dad_optim" : !tensors ? "tensor list" : "arguments");
+    if (n <= 0) return fail(DAD_E_INVALID, "optimiser step: n = %d tensors", n);
+    if (!a->groups) return fail(DAD_E_INVALID, "optimiser step: null groups");
+    if (a->n_groups <= 0 || a->n_groups > kOptimMaxGroups)
+        return fail(DAD_E_INVALID, "optimiser step: %d groups (1 .. %d)", a->n_groups, kOptimMaxGroups);
+    bool any_grad = false, same_numel = o->numel.size() == (size_t)n;
+    for (int i = 0; i < n; ++i) {
+        const dad_optim_tensor& t = tensors[i];
+        if (!t.param) return fail(DAD_E_INVALID, "optimiser step: tensor %d has a null param", i);
+        if (t.numel <= 0) return fail(DAD_E_INVALID, "optimiser step: tensor %d has numel %lld", i, (long long)t.numel);
+        if (t.group < 0 || t.group >= a->n_groups)
+            return fail(DAD_E_INVALID, "optimiser step: tensor %d is in group %d of %d", i, t.group, a->n_groups);
+        if (t.grad && (!t.exp_avg || !t.exp_avg_sq))
+            return fail(DAD_E_INVALID, "optimiser step: tensor %d has a grad but no %s", i, !t.exp_avg ? "exp_avg" : "exp_avg_sq");
+        if (!t.grad && !t.ema) return fail(DAD_E_INVALID, "optimiser step: tensor %d has neither grad nor ema: nothing to do", i);
+        any_grad = any_grad || t.grad;
+        same_numel = same_numel && o->numel[(size_t)i] == t.numel;
+    }
+    if (!same_numel) {
+        std::vector<int64_t> numel((size_t)n);
+        for (int i = 0; i < n; ++i) numel[(size_t)i] = tensors[i].numel;
+        OptimPlan p;
+        const int rc = optim_plan(numel.data(), n, p);
+        if (rc != DAD_OK) return rc;
+        o->plan = std::move(p);
+        o->numel = std::move(numel);
+    }
+    hipStream_t st = (hipStream_t)s;
+    const size_t desc_bytes = (size_t)n * sizeof(dad::OptimDesc), first_bytes = o->plan.first.size() * sizeof(int32_t);
+    std::vector<char> image(desc_bytes + first_bytes, 0);
+    for (int i = 0; i < n; ++i) {
+        const dad_optim_tensor& t = tensors[i];
+        dad::OptimDesc d{};                // (built in place: padding bytes stay zero for the comparison)
+        d.p = t.param; d.g = t.grad; d.m = t.exp_avg; d.v = t.exp_avg_sq; d.ema = t.ema;
+        d.numel = t.numel; d.group = t.group;
+        const uintptr_t bits = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq | (uintptr_t)t.ema;
+        d.vec = (bits & 15) == 0;
+        std::memcpy(image.data() + (size_t)i * sizeof(dad::OptimDesc), &d, sizeof(d));
+    }
+    std::memcpy(image.data() + desc_bytes, o->plan.first.data(), first_bytes);
+    if (image != o->image) {
+        const int rc = optim_upload(o, image, st);
+        if (rc != DAD_OK) { o->image.clear(); return rc; }
+        o->image.swap(image);
+    }
+    if (!o->d_partials) {
+        void* p = nullptr;
+        HIP_TRY(hipMalloc(&p, kOptimMaxGrid * sizeof(double)));
+        o->owned.push_back(p);
+        o->d_partials = (double*)p;
+    }
+    const auto* descs = (const dad::OptimDesc*)o->d_table;
+    const int* first = (const int*)((const char*)o->d_table + desc_bytes);
+    const OptimGeom g = o->plan.g;
+    const bool norm = any_grad && (a->max_grad_norm > 0.f || a->grad_norm_out);
+    if (!any_grad && a->grad_norm_out)      // nothing to sum: the norm of no gradients is 0, as clip_grad_norm_ gives
+        HIP_TRY(hipMemsetAsync(a->grad_norm_out, 0, sizeof(float), st));
+    if (norm) {
+        hipLaunchKernelGGL(dad::optim_sqsum_kernel, dim3((unsigned)g.grid), dim3(dad::OPT_THREADS), 0, st, descs, first, (int)n, g,
+                           o->d_partials);
+        HIP_TRY(hipGetLastError());
+    }
+    dad::OptimGroups groups{};
+    std::copy(a->groups, a->groups + a->n_groups, groups.g);
+    hipLaunchKernelGGL(dad::optim_update_kernel, dim3((unsigned)g.grid), dim3(dad::OPT_THREADS), 0, st, descs, first, (int)n, g,
+                       groups, (const double*)o->d_partials, norm ? g.grid : 0, a->max_grad_norm, a->ema_decay, a->grad_norm_out);
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
+int dad_debug_optim_plan(const int64_t* numel, int32_t n, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (!numel || n <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    std::vector<int32_t> r;
+    const int rc = optim_plan_report(numel, n, r);
+    if (rc != DAD_OK) return rc;
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
     return DAD_OK;
 }
 

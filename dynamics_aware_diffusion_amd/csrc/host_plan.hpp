@@ -1827,4 +1827,70 @@ inline std::vector<float> sinusoid_table(int T, int dim) {
     return emb;
 }
 
+// ------------------------------------------------------------------ optimiser step (dad_optim_step, csrc/optim_step.hpp)
+// One step over a list of tensors is cut into chunks of kOptimChunk elements (the last chunk of a tensor is shorter;
+// a chunk never spans two tensors, and starts at a multiple of 4 elements so that 16-byte accesses stay aligned).
+// Chunks are numbered tensor by tensor; block b of the two kernels walks chunks [b * per_block, (b + 1) * per_block)
+// in ascending order and finds the tensor of its first chunk by bisection over first[] (first[t] = first chunk of
+// tensor t, first[n] = all chunks).  The square-sum pass writes one partial per block: partials == grid.
+constexpr int kOptimChunk = 2048;        // elements: two float4 per thread of a 256-thread block
+constexpr int kOptimMaxGrid = 2048;      // blocks of a memory-bound pass; beyond it a block walks several chunks
+constexpr int kOptimMaxGroups = 8;
+struct OptimGeom { int32_t chunk, nchunks, per_block, grid; };
+DAD_HD inline void optim_block_chunks(const OptimGeom& g, int block, int& lo, int& hi) {
+    lo = block * g.per_block;
+    hi = lo + g.per_block < g.nchunks ? lo + g.per_block : g.nchunks;
+}
+// chunk c of a tensor of `numel` elements whose first chunk is `first_chunk`: elements [first, first + count)
+DAD_HD inline void optim_chunk_span(const OptimGeom& g, int c, int first_chunk, int64_t numel, int64_t& first, int32_t& count) {
+    first = (int64_t)(c - first_chunk) * g.chunk;
+    const int64_t left = numel - first;
+    count = (int32_t)(left < g.chunk ? left : g.chunk);
+}
+struct OptimPlan { OptimGeom g{}; std::vector<int32_t> first; };
+inline int optim_plan(const int64_t* numel, int n, OptimPlan& p) {
+    if (!numel || n <= 0) return fail(DAD_E_INVALID, "optimiser plan: no tensors");
+    p.first.assign((size_t)n + 1, 0);
+    int64_t chunks = 0;
+    for (int t = 0; t < n; ++t) {
+        if (numel[t] <= 0) return fail(DAD_E_INVALID, "optimiser plan: tensor %d has numel %lld", t, (long long)numel[t]);
+        chunks += (numel[t] + kOptimChunk - 1) / kOptimChunk;
+        if (chunks >= INT32_MAX) return fail(DAD_E_INVALID, "optimiser plan: too many elements for one launch");
+        p.first[(size_t)t + 1] = (int32_t)chunks;
+    }
+    p.g.chunk = kOptimChunk;
+    p.g.nchunks = (int32_t)chunks;
+    p.g.per_block = (p.g.nchunks + kOptimMaxGrid - 1) / kOptimMaxGrid;
+    p.g.grid = (p.g.nchunks + p.g.per_block - 1) / p.g.per_block;
+    return DAD_OK;
+}
+
+// dad_debug_optim_plan: the plan above written down chunk by chunk (layout: include/dad.h, DAD_OS_*), by walking
+// the blocks with the two functions the kernels walk them with.
+inline int optim_plan_report(const int64_t* numel, int n, std::vector<int32_t>& r) {
+    OptimPlan p;
+    const int rc = optim_plan(numel, n, p);
+    if (rc != DAD_OK) return rc;
+    r.assign(DAD_OS_HEADER, 0);
+    r[DAD_OS_CHUNK] = p.g.chunk;
+    r[DAD_OS_CHUNKS] = p.g.nchunks;
+    r[DAD_OS_GRID] = p.g.grid;
+    r[DAD_OS_PARTIALS] = p.g.grid;
+    r[DAD_OS_RECORD_INTS] = DAD_OS_REC_INTS;
+    for (int b = 0; b < p.g.grid; ++b) {
+        int lo, hi;
+        optim_block_chunks(p.g, b, lo, hi);
+        int t = (int)(std::upper_bound(p.first.begin(), p.first.end(), lo) - p.first.begin()) - 1;
+        for (int c = lo; c < hi; ++c) {
+            while (c >= p.first[(size_t)t + 1]) ++t;
+            int64_t first;
+            int32_t count;
+            optim_chunk_span(p.g, c, p.first[(size_t)t], numel[t], first, count);
+            const int32_t rec[DAD_OS_REC_INTS] = {t, (int32_t)(first & 0x7fffffff), (int32_t)(first >> 31), count, b};
+            r.insert(r.end(), rec, rec + DAD_OS_REC_INTS);
+        }
+    }
+    return DAD_OK;
+}
+
 }  // namespace dadhost

@@ -179,6 +179,12 @@ class TemporalUnet(nn.Module):
         self._engine, self._engine_sig, self._engine_params = eng, sig, params
         return eng
 
+    def mark_weights_changed(self) -> None:
+        """For callers that update the weights through ``.data`` (the reference's EMA loop, utils/training.py:187-189) or
+        from their own kernels: such writes bump no version counter, so ``engine()`` cannot see them.  Bumps every
+        parameter's version; the next call refreshes the engine from the parameters."""
+        torch.autograd.graph.increment_version(list(self._params().values()))
+
     # ------------------------------------------------------------------ forward
     @staticmethod
     def shared_timestep(time: Union[int, torch.Tensor]) -> int:

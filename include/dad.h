@@ -536,6 +536,84 @@ int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32
 int dad_debug_small_kernel_exists(int32_t taps, int32_t stride, int32_t ride, int32_t wide, int32_t big, int32_t ride_in,
                                   int32_t rows, int32_t windowed);
 
+/* ------------------------------------------------------------------------------------------------
+ * The optimiser step.  Replaces what Trainer.train_step does after loss.backward() (utils/training.py:158-189):
+ * clip_grad_norm_(parameters, max_norm), torch.optim.Adam.step() and the update_ema loop, as at most two launches
+ * over a list of tensors, with no host synchronisation.  A dad_optim is independent of dad_model: it sees pointers.
+ *
+ * Per tensor (utils/training.py:158-189; torch.optim.Adam's arithmetic in its operation order):
+ *   coef = min(1, max_grad_norm / (total_norm + 1e-6)),  total_norm = sqrt(sum of g^2 over every tensor with a grad)
+ *          (clip_grad_norm_, utils/training.py:158-163; not special-cased for non-finite values)
+ *   g'   = coef g  (+ weight_decay p: L2 weight decay);   with `decoupled`, p *= 1 - lr weight_decay first (AdamW)
+ *   m    = m + (g' - m) one_minus_beta1;   v = beta2 v + one_minus_beta2 g'^2
+ *   p    = p - step_size m / (sqrt(v) / bc2_sqrt + eps)                        (utils/training.py:165-166)
+ *   ema  = ema_decay ema + (1 - ema_decay) p                                    (utils/training.py:180-189)
+ * THE GRADIENT IS READ ONLY: after the step `grad` still holds the unclipped gradient, where clip_grad_norm_ scales
+ * it in place.  A tensor with grad == NULL only has its EMA updated (update_ema covers every parameter); one with
+ * ema == NULL has none.  Tensors are fp32 and contiguous; a tensor whose pointers are all 16-byte aligned is read
+ * and written 16 bytes at a time, any other one element at a time.
+ * The summation order of total_norm is fixed by the plan (dad_debug_optim_plan): one partial per block, added in
+ * block order, no atomics: two runs give the same bits.
+ * The descriptor table lives on the device and is uploaded (stream-ordered, from pinned staging buffers that are
+ * not rewritten while a copy may be in flight) only when a pointer, size or group index changed since the last
+ * step.  ONE STREAM PER dad_optim AT A TIME; device memory is allocated at the first step on the current device.
+ * A table that outgrows its device buffer gets a new one of twice the size; the old buffer (a step in flight may
+ * still read it) and the staging buffers are kept until dad_optim_destroy.
+ * When no tensor of a step has a grad, total_norm is 0: grad_norm_out receives 0 and nothing is clipped. */
+typedef struct dad_optim dad_optim;
+typedef struct dad_optim_tensor {
+    float* param;
+    const float* grad;    /* NULL: EMA only                                                        */
+    float* exp_avg;       /* m and v: required when grad is set                                    */
+    float* exp_avg_sq;
+    float* ema;           /* NULL: no EMA                                                          */
+    int64_t numel;
+    int32_t group;        /* index into dad_optim_args.groups                                      */
+} dad_optim_tensor;
+/* One set of hyper-parameters: a torch param group at one step count.  step_size = lr / (1 - beta1^step),
+ * bc2_sqrt = sqrt(1 - beta2^step), one_minus_beta1 = 1 - beta1 and one_minus_beta2 = 1 - beta2 are computed by the
+ * caller in double, as torch does, and rounded once (1 - 0.999f is 1.3e-5 away from 0.001). */
+typedef struct dad_optim_group {
+    float lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt;
+    int32_t decoupled;
+    float one_minus_beta1, one_minus_beta2;
+} dad_optim_group;        /* at most 8 per step */
+typedef struct dad_optim_args {
+    const dad_optim_group* groups;
+    int32_t n_groups;
+    float max_grad_norm;  /* <= 0: no clipping (the square-sum pass then runs only if grad_norm_out is set) */
+    float ema_decay;
+    float* grad_norm_out; /* device scalar that receives the pre-clip total_norm, or NULL         */
+} dad_optim_args;
+int dad_optim_create(dad_optim** out);             /* no device call */
+void dad_optim_destroy(dad_optim* o);
+/* Enqueues one step on `s`.  DAD_E_INVALID, with a message and before any device call, for: a null pointer, n <= 0,
+ * numel <= 0, a group index out of range, n_groups outside 1 .. 8, grad set but a moment missing, a tensor with
+ * neither grad nor ema. */
+int dad_optim_step(dad_optim* o, const dad_optim_tensor* tensors, int32_t n, const dad_optim_args* a, dad_stream_t s);
+/* The work split dad_optim_step replays for tensors of these sizes (csrc/host_plan.hpp: optim_plan; host-side query,
+ * no device call).  Writes min(capacity, *needed_out) int32 values to `out`:
+ *   [DAD_OS_CHUNK]        elements per chunk (a multiple of 4)
+ *   [DAD_OS_CHUNKS]       chunks = records that follow from DAD_OS_HEADER on
+ *   [DAD_OS_GRID]         blocks of each of the two kernels (at most 2048)
+ *   [DAD_OS_PARTIALS]     partial square sums (one per block)
+ *   [DAD_OS_RECORD_INTS]  ints per record (DAD_OS_REC_*)
+ * One record per chunk in chunk order: tensor, first element (its low 31 bits, then the bits above), elements, and
+ * the block that owns the chunk (a block walks its chunks in this order). */
+#define DAD_OS_CHUNK 0
+#define DAD_OS_CHUNKS 1
+#define DAD_OS_GRID 2
+#define DAD_OS_PARTIALS 3
+#define DAD_OS_RECORD_INTS 4
+#define DAD_OS_HEADER 5
+#define DAD_OS_REC_TENSOR 0
+#define DAD_OS_REC_FIRST 1
+#define DAD_OS_REC_FIRST_HI 2
+#define DAD_OS_REC_COUNT 3
+#define DAD_OS_REC_BLOCK 4
+#define DAD_OS_REC_INTS 5
+int dad_debug_optim_plan(const int64_t* numel, int32_t n, int32_t* out, int32_t capacity, int32_t* needed_out);
+
 #ifdef __cplusplus
 }
 #endif
