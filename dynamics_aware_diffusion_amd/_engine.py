@@ -215,7 +215,9 @@ TIME_GEMM_MODES = ("FWD_H1", "FWD_TEMB", "FWD_ROWS", "BWD_DWK", "BWD_DACT", "BWD
 
 
 # DAD_FP_* of include/dad.h: the records of dad_debug_forward_plan
-FP_REC_FIELDS = ("conv", "sub", "cfg", "taps", "stride", "flags", "kc", "kslices", "gn_npt", "ntiles_n", "mtiles", "part_tile")
+FP_REC_FIELDS = ("conv", "sub", "cfg", "taps", "stride", "flags", "kc", "kslices", "gn_npt", "ntiles_n", "mtiles", "part_tile",
+                 "family")
+FP_FAMILIES = ("gemm", "halo8")           # DAD_FP_FAMILY_* of include/dad.h
 FP_CC_FIELDS = ("conv", "taps", "stride", "wide", "ride", "big", "ride_in", "tile_rows", "windowed", "slice_ch", "kslices",
                 "ntiles", "res_kind")
 FP_FINAL_KERNELS = (None, "final_posterior_kernel", "final_cc_kernel")
@@ -843,7 +845,8 @@ class HipEngine:
         small-batch plan is taken), ``final`` (grid x, grid y, kernel name or None) and ``launches``: one dict per
         launch with the fields of DAD_FP_REC_* (``flags``: the flag word of kernel_registered_f) or, with ``small``,
         of DAD_FP_CC_*; each has ``key``, the instantiation it runs: ("gemm", cfg, taps, stride, flags),
-        ("cc", taps, stride, ride, big, rows, windowed) or ("ccw", taps, stride, ride, ride_in, rows)."""
+        ("halo8", cfg, ride) — conv_halo8_f32 on tile cfg —, ("cc", taps, stride, ride, big, rows, windowed) or
+        ("ccw", taps, stride, ride, ride_in, rows)."""
         need = C.c_int32()
         _check(self.lib, self.lib.dad_debug_forward_plan(self._h, int(batch), int(mode), None, 0, C.byref(need)))
         buf = (C.c_int32 * need.value)()
@@ -855,7 +858,9 @@ class HipEngine:
         launches = []
         for at in range(8, len(r), len(fields)):
             q = dict(zip(fields, r[at:at + len(fields)]))
-            if not small:
+            if not small and FP_FAMILIES[q["family"]] == "halo8":
+                q["key"] = ("halo8", q["cfg"], (q["flags"] >> 3) & 1)
+            elif not small:
                 q["key"] = ("gemm", q["cfg"], q["taps"], q["stride"], q["flags"])
             elif q["wide"]:
                 q["key"] = ("ccw", q["taps"], q["stride"], q["ride"], q["ride_in"], q["tile_rows"])

@@ -33,8 +33,19 @@ DAD_HD inline size_t conv_lds_floats(int BM, int BN, int KC, int taps, int Lin, 
     return k > epi ? k : epi;
 }
 
+// conv_halo8.hpp: the 64 columns of a tile of eight 8-position samples in position-pair-major order.  Column block
+// q (16 columns) holds positions {2q, 2q + 1} of all eight samples; MFMA row i of a block (the lane's low four bits
+// for the A operand, 4 * (lane / 16) + r for accumulator register r) is:
+DAD_HD inline int halo8_sample(int i) { return ((i >> 1) & 1) * 4 + (i >> 2); }
+DAD_HD inline int halo8_pos(int i, int q) { return 2 * q + (i & 1); }
+// Wave tile tn of the two along N owns blocks {0, 1} / {3, 2} in this order: its block 0 is the tile's outer one, and
+// it walks the taps from its outer side (tap index t is conv tap t for tn = 0, 4 - t for tn = 1), so that for every
+// wave (tap index 0, block 0) is the product that reads halo rows only.
+DAD_HD inline int halo8_block(int tn, int nb) { return tn ? 3 - nb : nb; }
+DAD_HD inline int halo8_tap(int tn, int t) { return tn ? 4 - t : t; }
+
 // conv_wgrad (train_bwd.hpp)
-constexpr int WG_THREADS = 512;              // 8 waves: TM x TN wave tiles of 32 x 32 (x TAPS), the rest split K
+constexpr int WG_THREADS = 512;             // 8 waves: TM x TN wave tiles of 32 x 32 (x TAPS), the rest split K
 constexpr int WG_ROWS = 64;                  // G rows per staged chunk: spc = max(1, 64 / Lg) whole samples
 constexpr int WG_MAX_GROWS = 128, WG_MAX_ZROWS = 160;      // rows one chunk may stage (registers of chunk_load)
 

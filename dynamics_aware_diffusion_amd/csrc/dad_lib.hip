@@ -22,6 +22,7 @@
 #include "../../include/dad.h"
 #include "host_plan.hpp"
 #include "conv_gemm.hpp"
+#include "conv_halo8.hpp"
 #include "conv_gn_pass.hpp"
 #include "pointwise.hpp"
 #include "conv_cc.hpp"
@@ -259,6 +260,22 @@ const void* ccw_kernel(int taps, bool res, bool ride_in, int rows) {
     return find_kernel(ccw_kernels(), taps, res, ride_in, rows);
 }
 
+// conv_halo8.hpp instantiations by (tile cfg, this launch carries a riding 1x1 conv): the block tiles of kTiles[0 / 1]
+const FamilyList& halo8_kernels() {
+    static const FamilyList list = [] {
+        FamilyList v;
+        static_assert(kTiles[0].BM == 32 && kTiles[0].SK == 4 && kTiles[1].BM == 64 && kTiles[1].SK == 2 && halo8_kernel_exists(0) &&
+                      halo8_kernel_exists(1) && !halo8_kernel_exists(2), "conv_halo8_f32 covers tiles 0 and 1");
+        v.push_back({{0, 0}, (const void*)dad::conv_halo8_f32<32, 4, false>});
+        v.push_back({{0, 1}, (const void*)dad::conv_halo8_f32<32, 4, true>});
+        v.push_back({{1, 0}, (const void*)dad::conv_halo8_f32<64, 2, false>});
+        v.push_back({{1, 1}, (const void*)dad::conv_halo8_f32<64, 2, true>});
+        return v;
+    }();
+    return list;
+}
+const void* halo8_kernel(int cfg, bool res) { return find_kernel(halo8_kernels(), cfg, res, 0); }
+
 // conv_wgrad instantiations by (taps of kWgradTaps, block tile, windowed: layers longer than a chunk stages):
 // tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32 (eight); tile 3 = 32 x 32 with the general
 // staging path (operands that are not whole aligned float4 rows)
@@ -296,7 +313,7 @@ int configure_kernels() {
     std::vector<const void*> fns = {(const void*)dad::final_posterior_kernel, (const void*)dad::final_cc_kernel,
                                     (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>};
     for (const auto& kv : kernel_table()) fns.push_back((const void*)kv.second);
-    for (const FamilyList* list : {&cc_kernels(), &ccw_kernels(), &wgrad_kernels()})
+    for (const FamilyList* list : {&cc_kernels(), &ccw_kernels(), &wgrad_kernels(), &halo8_kernels()})
         for (const FamilyKernel& k : *list) fns.push_back(k.fn);
     for (const void* fn : fns)
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
@@ -424,6 +441,15 @@ int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, 
     p.stamps = (g_stamps && &op >= &m->plan.convs[0] && &op < &m->plan.convs[0] + m->plan.convs.size())
                    ? g_stamps + (size_t)(&op - &m->plan.convs[0]) * 4096 * 8 : nullptr;
 #endif
+    if (g.halo8) {                     // conv_halo8.hpp: same tile, grid, LDS and operands, its own slot shifts
+        const void* fn = halo8_kernel(g.cfg, g.fused);
+        if (fn == nullptr || gn_pass || p.pre != nullptr || p.stats != nullptr || p.kslices != 1)
+            return fail(DAD_E_INVALID, "no halo-skipping kernel for %s (tile %d res=%d)", op.name.c_str(), g.cfg, (int)g.fused);
+        p.xswz = g.xswz8;
+        void* hargs[] = {&p};
+        HIP_TRY(hipLaunchKernel(fn, dim3(g.gx, g.gy, g.gz), dim3(g.threads), hargs, g.lds_bytes, st));
+        return DAD_OK;
+    }
     const auto& table = kernel_table();
     const auto it = table.find(KernKey(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded, g.windowed));
     if (it == table.end())
@@ -1670,6 +1696,7 @@ int dad_debug_set_option(dad_model* m, const char* name, int32_t value) {
     else if (key == "ccw_min_blocks") m->ccw_min_blocks = std::max(1, (int)value);
     else if (key == "ccw_prefer16") m->ccw_prefer16 = value != 0;
     else if (key == "wgrad_blocks") m->wgrad_blocks = std::max(1, (int)value);
+    else if (key == "halo8") m->halo8_enabled = value != 0;
     else return fail(DAD_E_INVALID, "unknown option '%s'", name);
     // every option changes which launches a captured loop holds, and not all of them are part of the
     // graph key: drop the cache (a replay may still be in flight: wait for the device first)

@@ -220,6 +220,8 @@ struct HostModel {
     bool ccw_prefer16 = true;                                  //   two 16-row tiles instead of an LDS-short 32-row one
                                                                //   (measured crossover: batch 16 at H = 32)
     mutable std::map<std::array<int, 5>, uint64_t> xswz_cache; // find_xswz memo: the cache of a pure function, filled by const planning
+    bool halo8_enabled = true;                                 // 8-position 5-tap layers at full-chip batches take conv_halo8.hpp
+    mutable std::map<std::array<int, 3>, uint64_t> xswz8_cache; // find_xswz_pairs memo
     // ---- backward pass (dad_model_set_training): data-gradient launches + the layout of the gradients
     bool training = false;
     struct BwdConv {
@@ -997,8 +999,55 @@ inline uint64_t find_xswz(const HostModel& m, int L, int stride, int pad, int kp
     return packed;
 }
 
+// The same for conv_halo8.hpp: a tile of eight 8-position samples read in position-pair-major column blocks with
+// ds_read_b64 (lane map: conv_shapes.hpp halo8_*).  A ds_read_b64 is served in two groups of 32 lanes — 16 MFMA rows
+// x two channel pairs kq — and is conflict-free when the group's 32 eight-byte slots are distinct mod 32.  Every
+// block holds all eight samples, so one set of shifts serves every (wave tile, block, tap).  kp2: eight-byte slots
+// per LDS row.  Returns 0 when nothing is found (plain layout: correct, slower).
+inline bool xswz8_prefix_ok(const int* d, int upto, int seg, int kp2) {
+    for (int q = 0; q < 4; ++q) {
+        uint32_t seen = 0;
+        for (int i = 0; i < 16; ++i) {
+            const int sm = dad::halo8_sample(i);
+            if (sm >= upto) continue;
+            for (int kq = 0; kq < 2; ++kq) {
+                const uint32_t bit = 1u << (((sm * seg + dad::halo8_pos(i, q)) * kp2 + 2 * d[sm] + kq) & 31);
+                if (seen & bit) return false;
+                seen |= bit;
+            }
+        }
+    }
+    return true;
+}
+inline uint64_t find_xswz_pairs(const HostModel& m, int L, int pad, int kp4) {
+    if (L != 8 || pad == 0) return 0;
+    const std::array<int, 3> key{L, pad, kp4};
+    auto it = m.xswz8_cache.find(key);
+    if (it != m.xswz8_cache.end()) return it->second;
+    const int S = 8, seg = L + 2 * pad;
+    int d[8] = {0};
+    long budget = 300000;
+    std::function<bool(int)> place = [&](int sm) -> bool {
+        if (sm == S) return true;
+        for (int v = 0; v < 16; ++v) {
+            if (--budget < 0) return false;
+            if (sm > 0 && d[sm - 1] - v > pad * kp4) continue;     // never onto the neighbour's real rows
+            d[sm] = v;
+            if (xswz8_prefix_ok(d, sm + 1, seg, 2 * kp4) && place(sm + 1)) return true;
+        }
+        d[sm] = 0;
+        return false;
+    };
+    uint64_t packed = 0;
+    if (place(0))
+        for (int sm = 0; sm < S; ++sm) packed |= (uint64_t)d[sm] << (4 * sm);
+    m.xswz8_cache[key] = packed;
+    return packed;
+}
+
 // Grid-level split-K: when a layer has too few output tiles to cover the chip (small batches;
 // the deepest levels of the wide nets), several blocks share a tile and split its K chunks.
+constexpr int kSplitMaxTiles = 160;      // from this many output tiles on a launch is never split
 struct SplitPlan { int kslices, chunks_per_slice; long slab_floats; };
 inline SplitPlan plan_split(const HostModel& m, const ConvOp& op, int cfg, int batch) {
     const TileCfg& t = kTiles[cfg];
@@ -1007,7 +1056,7 @@ inline SplitPlan plan_split(const HostModel& m, const ConvOp& op, int cfg, int b
     const int nchunks = (op.cin0 + op.cin1 + kc - 1) / kc;      // chunks holding real channels
     SplitPlan sp{1, nchunks, 0};
     if (!m.split_enabled) return sp;
-    if (tiles >= 160 || nchunks < 2 || tiles > kMaxSplitTiles) return sp;
+    if (tiles >= kSplitMaxTiles || nchunks < 2 || tiles > kMaxSplitTiles) return sp;
     // blocks = tiles * slices should not spill a few blocks into a second wave of the 256 CUs (24 tiles x
     // 11 slices = 264 blocks took 1.4x the time of 24 x 10): round the slice count DOWN while that still
     // splits, up only for tile counts above half the chip
@@ -1038,6 +1087,8 @@ struct LaunchGeom {
     int gn_npt = 0;          // > 0: a windowed GroupNorm'd layer, finished by gn_pass_kernel<gn_npt> after the conv
     SplitPlan split{1, 0, 0};
     uint64_t xswz = 0;
+    bool halo8 = false;      // launched as conv_halo8_f32<BM, SK, fused> (choose_halo8), not as the conv-GEMM kernel above
+    uint64_t xswz8 = 0;      //   its slot shifts (find_xswz_pairs)
 };
 
 // The general staging path (RAGGED kernels): a K chunk may straddle the concat's seam or the end of the channels, or
@@ -1187,6 +1238,26 @@ inline int plan_launch(const HostModel& m, const ConvOp& op, int batch, LaunchGe
     }
     g.xswz = m.xswz_enabled ? find_xswz(m, op.Lout, op.stride, op.taps / 2, (g.kc + 4) / 4, t.BN) : 0;
     return DAD_OK;
+}
+
+// conv_halo8.hpp: which launches of a forward evaluation take the halo-skipping kernel instead of the conv-GEMM
+// kernel plan_launch chose.  It exists for the 5-tap stride-1 fp32 convs of 8-position layers on tiles 0 and 1,
+// with whole aligned K chunks and no grid split-K, and is taken only in the full-chip regime (kSplitMaxTiles output
+// tiles or more) of the heuristic: a forced tile (dad_debug_set_tile, split-K switched off included) pins the
+// conv-GEMM kernels and their summation order.  Not for the training forward (plan_forward applies it to m.plan
+// only).  The ride is decided by fused_at as before.
+constexpr bool halo8_kernel_exists(int cfg) { return cfg == 0 || cfg == 1; }      // each with and without the ride
+inline bool halo8_layer(const ConvOp& op) {
+    return op.kind == CONV_K5 && op.taps == 5 && op.stride == 1 && op.Lin == 8 && op.Lout == 8 && !op.x3 && !op.bdir &&
+           !op.net_padded && !op.padded() && op.pre < 0 && op.stats < 0;
+}
+inline void choose_halo8(const HostModel& m, const ConvOp& op, LaunchGeom& g) {
+    g.halo8 = false; g.xswz8 = 0;
+    if (!m.halo8_enabled || m.force_tile >= 0 || !m.split_enabled || g.cfg < 0 || !halo8_layer(op)) return;
+    if (!halo8_kernel_exists(g.cfg) || g.kc != 32 || g.ragged || g.padded || g.windowed || g.split.kslices != 1) return;
+    if ((long)g.mtiles * g.ntiles_n < kSplitMaxTiles) return;
+    g.halo8 = true;
+    g.xswz8 = m.xswz_enabled ? find_xswz_pairs(m, op.Lout, op.taps / 2, (g.kc + 4) / 4) : 0;
 }
 
 // ------------------------------------------------------------------ small-batch (CC) plan
@@ -1455,6 +1526,7 @@ inline int plan_forward(const HostModel& m, bool train, int batch, bool small_ok
         const bool listed = !f.cc.ok && !(op.rider_of >= 0 && carries[op.rider_of]);
         if (listed) { const int rc = plan_launch(m, op, batch, l.g); l.ok = rc == DAD_OK; first.note(rc); }
         else choose_launch(m, op, batch, l.g);         // (its split-K slab still counts: sizes are one rule for all calls)
+        if (listed && l.ok && !train) choose_halo8(m, op, l.g);
         carries[i] = l.g.fused;
         scratch = std::max(scratch, l.g.split.slab_floats);
         if (listed) f.launches.push_back(l);
@@ -1758,7 +1830,7 @@ inline void forward_plan_encode(const HostModel& m, int mode, int batch, const F
         const int bn = g.cfg >= 0 ? kTiles[g.cfg].BN : 0;
         const bool part = g.cfg >= 0 && op.Lout <= bn && batch % (bn / op.Lout) != 0;
         const int32_t rec[DAD_FP_REC_INTS] = {index, sub, g.cfg, op.taps, op.stride, launch_flags(op, g), g.kc, g.split.kslices,
-                                              g.gn_npt, g.ntiles_n, g.mtiles, part};
+                                              g.gn_npt, g.ntiles_n, g.mtiles, part, g.halo8 ? DAD_FP_FAMILY_HALO8 : DAD_FP_FAMILY_GEMM};
         r.insert(r.end(), rec, rec + DAD_FP_REC_INTS);
         ++r[DAD_FP_RECORDS];
     };

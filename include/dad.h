@@ -337,7 +337,8 @@ int dad_profile_read(dad_model* m, double* conv_ms, int64_t* conv_launches, doub
  * needs the streamed-weight kernels of csrc/conv_ccw.hpp: GroupNorm groups wider than 64 channels),
  * "ccw_min_blocks" (blocks a wide layer keeps when its K slices are fattened), "ccw_prefer16" (two
  * 16-row tiles instead of a 32-row tile whose K slice LDS would halve), "wgrad_blocks" (blocks a
- * weight-gradient launch of the backward pass aims for: tiles x batch splits).
+ * weight-gradient launch of the backward pass aims for: tiles x batch splits), "halo8" (5-tap convs of
+ * 8-position layers at full-chip batches under the heuristic take csrc/conv_halo8.hpp; 0 = the conv-GEMM kernels).
  * Results do not depend on these choices beyond fp32 summation order. */
 int dad_debug_set_tile(dad_model* m, int32_t cfg);
 int dad_debug_set_option(dad_model* m, const char* name, int32_t value);
@@ -483,7 +484,9 @@ int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t 
  *   which of that conv's data-gradient launches), tile cfg, taps, stride, flags (bit 0 x3, 1 bdir, 2 ragged, 3 res —
  *   the ride —, 4 padded, 5 windowed: the flag word of kernel_registered_f, so (cfg, taps, stride, flags) names the
  *   instantiation), K chunk, grid-level K slices, npt of the gn_pass_kernel<npt> launch that follows (0: none),
- *   N tiles, M tiles, 1 when the last N tile holds fewer samples than it has room for.
+ *   N tiles, M tiles, 1 when the last N tile holds fewer samples than it has room for, kernel family:
+ *   DAD_FP_FAMILY_GEMM (conv_gemm_f32, the instantiation named above) or DAD_FP_FAMILY_HALO8 (conv_halo8_f32 of
+ *   csrc/conv_halo8.hpp on the same tile, grid and ride: cfg 0 / 1 and flag bit 3 name its instantiation).
  * With [DAD_FP_SMALL] one record per launched small-batch conv instead:
  *   conv index, taps, stride, wide (conv_ccw), ride, big, ride_in, rows per tile (16 / 32), windowed, channels per K
  *   slice, K slices, N tiles, res_kind (how the output's residual reaches its consumer: 0 none, 1 the trajectory,
@@ -512,7 +515,10 @@ int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t 
 #define DAD_FP_REC_NTILES_N 9
 #define DAD_FP_REC_MTILES 10
 #define DAD_FP_REC_PART_TILE 11
-#define DAD_FP_REC_INTS 12
+#define DAD_FP_REC_FAMILY 12
+#define DAD_FP_REC_INTS 13
+#define DAD_FP_FAMILY_GEMM 0
+#define DAD_FP_FAMILY_HALO8 1
 #define DAD_FP_CC_CONV 0
 #define DAD_FP_CC_TAPS 1
 #define DAD_FP_CC_STRIDE 2

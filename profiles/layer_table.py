@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer efficiency table of one denoise step from a rocprofv3 --kernel-trace CSV of
-profiles/pmc_target.py (batch-256 kernels: dad::conv_gemm_f32<...>):
+profiles/pmc_target.py (batch-256 kernels: dad::conv_gemm_f32<...>, dad::conv_halo8_f32<...>):
 
     python3 profiles/layer_table.py <kernel_trace.csv> <arch> <batch>  >  profiles/rNN_layers_<arch>_b<batch>.md
 
@@ -61,7 +61,7 @@ def main():
     raw, cur = [], []
     for r in rows:
         us = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-        if "conv_gemm_f32" in r["Kernel_Name"]:
+        if "conv_gemm_f32" in r["Kernel_Name"] or "conv_halo8_f32" in r["Kernel_Name"]:
             cur.append((us, r["Kernel_Name"]))
         elif "final_posterior_kernel" in r["Kernel_Name"]:
             raw.append(cur)
@@ -82,7 +82,10 @@ def main():
             if i >= len(step):
                 return None
             a = targs(step[i][1])
-            pending_ride = len(a) >= 10 and a[9] in ("true", "1") and a[4] == "5"
+            if "conv_halo8_f32" in step[i][1]:           # <BM, SK, RES> (csrc/conv_halo8.hpp)
+                pending_ride = a[2] in ("true", "1")
+            else:
+                pending_ride = len(a) >= 10 and a[9] in ("true", "1") and a[4] == "5"
             names.append((name, f))
             i += 1
         return names if i == len(step) else None
@@ -104,6 +107,8 @@ def main():
         us = sum(s[i][0] for s in steps) / len(steps)
         kn = steps[0][i][1]
         tile = kn[kn.index("<") + 1:kn.index(">")] if "<" in kn else kn
+        if "conv_halo8_f32" in kn:
+            tile = "halo8 " + tile
         fl = f * batch
         tot_us += us
         tot_fl += fl
