@@ -146,6 +146,7 @@ ABI = {
                                            C.POINTER(C.c_int32)]),
     "dad_debug_forward_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(C.c_int32)]),
+    "dad_debug_project_plan": (C.c_int, [C.c_int32] * 5 + [C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
     "dad_debug_kernel_registered": (C.c_int, [C.c_int32] * 4),
     "dad_debug_small_kernel_exists": (C.c_int, [C.c_int32] * 8),
     "dad_optim_create": (C.c_int, [C.POINTER(C.c_void_p)]),
@@ -222,6 +223,9 @@ FP_CC_FIELDS = ("conv", "taps", "stride", "wide", "ride", "big", "ride_in", "til
                 "ntiles", "res_kind")
 FP_FINAL_KERNELS = (None, "final_posterior_kernel", "final_cc_kernel")
 FP_FLAGS = ("x3", "bdir", "ragged", "res", "padded", "windowed")      # bits 0..5 of a record's flag word
+# DAD_PP_* of include/dad.h: the fields and forms of dad_debug_project_plan
+PP_FIELDS = ("form", "rows_per_block", "gx", "gy", "lds_bytes", "refused")
+PP_FORMS = ("row1", "row4", "gemm")       # project_kernel<1,16>, project_kernel<4,16>, project_gemm_kernel
 
 
 def registered_kernels():
@@ -243,6 +247,22 @@ def registered_kernels():
                         if lib.dad_debug_small_kernel_exists(taps, stride, ride, 1, 0, a, rows, 0):
                             ccw.add(("ccw", taps, stride, ride, a, rows))
     return gemm, cc, ccw
+
+
+def projection_plan(state_dim: int, observation_dim: int, action_dim: int, batch: int, horizon: int, *,
+                    scratch_bytes: int = 0, violation: bool = False) -> dict:
+    """Which kernel one dad_project (or, ``violation``, dad_projection_violation) call launches at this shape with a
+    scratch copy of ``scratch_bytes`` (0: none), and on which grid (dad_debug_project_plan: the plan the entry points
+    launch from; host logic only).  Returns ``form`` ("row1", "row4" or "gemm"), ``rows_per_block``, ``grid`` (x, y),
+    ``lds_bytes`` and ``refused`` (the call fails: the row does not fit LDS and the GEMM form is not to be had)."""
+    lib = load_library()
+    out = (C.c_int32 * len(PP_FIELDS))()
+    _check(lib, lib.dad_debug_project_plan(int(state_dim), int(observation_dim), int(action_dim), int(batch), int(horizon),
+                                           int(scratch_bytes), int(bool(violation)), out))
+    q = dict(zip(PP_FIELDS, out))
+    q["form"], q["refused"] = PP_FORMS[q["form"]], bool(q["refused"])
+    q["grid"] = (q.pop("gx"), q.pop("gy"))
+    return q
 
 
 def optim_plan(numel: Sequence[int]) -> dict:
@@ -919,6 +939,15 @@ class ProjectionState:
                 or self.act_mean.numel() != action_dim or self.act_std.numel() != action_dim:
             raise ValueError("normaliser statistics do not match observation_dim / action_dim")
 
+    @classmethod
+    def host(cls, state_dim: int, observation_dim: int, action_dim: int, gemm: bool = True) -> "ProjectionState":
+        """A state without a projector or a device: enough for :meth:`plan` (as an engine without weights plans)."""
+        self = cls.__new__(cls)
+        self.args = DadProjectArgs()
+        self.args.state_dim, self.args.observation_dim, self.args.action_dim = state_dim, observation_dim, action_dim
+        self.device, self._scratch, self.gemm, self.D = None, None, gemm, None
+        return self
+
     def _check_x(self, x: torch.Tensor) -> None:
         """The kernel derives D = (H+1) n + H m from x's horizon and indexes P[D, D] with it: a batch
         with another horizon or transition width would read P out of bounds (the reference raises a
@@ -939,6 +968,17 @@ class ProjectionState:
             self._scratch = torch.empty(x.numel(), dtype=torch.float32, device=self.device)
             self.args.scratch = self._scratch.data_ptr()
             self.args.scratch_bytes = self._scratch.numel() * 4
+
+    def plan(self, batch: int, horizon: int, violation: bool = False) -> dict:
+        """What :meth:`apply` (or, ``violation``, :meth:`violation`) launches for ``batch`` trajectories of ``horizon``
+        steps, with the scratch copy this state would hold for them (:func:`projection_plan`; no device call)."""
+        a = self.args
+        x_bytes = int(batch) * int(horizon) * (a.observation_dim + a.action_dim) * 4
+        scratch = int(a.scratch_bytes) if a.scratch else 0
+        if self.gemm:
+            scratch = max(scratch, x_bytes)
+        return projection_plan(a.state_dim, a.observation_dim, a.action_dim, batch, horizon, scratch_bytes=scratch,
+                               violation=violation)
 
     def violation(self, x: torch.Tensor) -> torch.Tensor:
         """Per-row squared distance from the dynamics-consistent subspace, physical units

@@ -112,4 +112,13 @@ DAD_HD inline size_t ccw_lds_floats(int slice_ch, int taps, int Lin, int Lout, i
     return k > e ? k : e;
 }
 
+// project_kernel<RB, KP> (pointwise.hpp): KP = 16 waves split k; a block keeps RB rows and their KP partial sets
+constexpr int PROJ_KP = 16;
+DAD_HD inline size_t project_row_lds_bytes(int D) { return (size_t)(1 + PROJ_KP) * D * sizeof(float); }
+// project_gemm_kernel (pointwise.hpp)
+constexpr int PG_THREADS = 256;
+constexpr int PG_KC = 64;                     // k values per staged chunk
+constexpr int PG_AS = 33;                     // LDS row stride of the staged v chunk [k][32 rows]
+DAD_HD inline size_t project_gemm_lds_floats() { return (size_t)4 * PG_KC * PG_AS + 64; }
+
 }  // namespace dad

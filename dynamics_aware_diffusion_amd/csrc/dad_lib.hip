@@ -667,35 +667,24 @@ int run_project(const dad_project_args* pa, float alpha, float* x, int batch, in
     p.alpha = alpha;
     p.one_minus_alpha = (float)(1.0 - (double)alpha);
     p.violation = violation;
-    // batches of 32+ trajectories with scratch for the projected copy: v @ P as an MFMA GEMM (P read once
-    // per 32 trajectories, not once per trajectory)
     const size_t x_bytes = (size_t)batch * horizon * (pa->observation_dim + pa->action_dim) * sizeof(float);
-    // (at PointMaze size, D = 196, the per-trajectory kernel is the faster one: 10 us against 16.6 us for
-    // 256 plans — 56 GEMM blocks leave most of the chip idle; the GEMM takes over from D = 512)
-    const size_t row_lds_probe = (size_t)(1 + 16) * p.D * sizeof(float);
-    const bool gemm_pays = p.D >= 512 || row_lds_probe > dad::kLdsBytes;
-    if (!violation && gemm_pays && batch >= 32 && pa->scratch != nullptr && pa->scratch_bytes >= x_bytes) {
+    const ProjectPlan q = plan_project(p.D, batch, x_bytes, pa->scratch ? pa->scratch_bytes : 0, violation != nullptr);
+    if (q.refused)
+        return fail(DAD_E_INVALID, "projection dimension D=%d: one trajectory's partial sums exceed LDS; pass "
+                    "dad_project_args.scratch and a batch of at least 32 for the GEMM form", p.D);
+    const dim3 grid(q.gx, q.gy);
+    if (q.form == DAD_PP_GEMM) {
         p.xout = pa->scratch;
-        const dim3 grid((unsigned)((batch + 31) / 32), (unsigned)((p.D + 31) / 32));
-        hipLaunchKernelGGL(dad::project_gemm_kernel, grid, dim3(dad::PG_THREADS),
-                           dad::project_gemm_lds_floats() * sizeof(float), st, p);
+        hipLaunchKernelGGL(dad::project_gemm_kernel, grid, dim3(dad::PG_THREADS), q.lds_bytes, st, p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(x, pa->scratch, x_bytes, hipMemcpyDeviceToDevice, st));
         return DAD_OK;
     }
     p.xout = x;
-    // rows per block: one while the batch fits one wave of blocks (every CU streams P once),
-    // four beyond that (P is then re-used by four rows per pass) if four rows fit LDS
-    const size_t row_lds = (size_t)(1 + 16) * p.D * sizeof(float);    // a row + its 16 partial sets
-    const int rb = (batch > 512 && 4 * row_lds <= dad::kLdsBytes) ? 4 : 1;
-    const size_t lds = rb * row_lds;
-    if (lds > dad::kLdsBytes)
-        return fail(DAD_E_INVALID, "projection dimension D=%d: one trajectory's partial sums exceed LDS; pass "
-                    "dad_project_args.scratch and a batch of at least 32 for the GEMM form", p.D);
-    if (rb == 1)
-        hipLaunchKernelGGL((dad::project_kernel<1, 16>), dim3(batch), dim3(1024), lds, st, p);
+    if (q.form == DAD_PP_ROW1)
+        hipLaunchKernelGGL((dad::project_kernel<1, dad::PROJ_KP>), grid, dim3(64 * dad::PROJ_KP), q.lds_bytes, st, p);
     else
-        hipLaunchKernelGGL((dad::project_kernel<4, 16>), dim3((batch + 3) / 4), dim3(1024), lds, st, p);
+        hipLaunchKernelGGL((dad::project_kernel<4, dad::PROJ_KP>), grid, dim3(64 * dad::PROJ_KP), q.lds_bytes, st, p);
     HIP_TRY(hipGetLastError());
     return DAD_OK;
 }
@@ -1788,6 +1777,23 @@ int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* o
     if (rc != DAD_OK) return rc;
     if (needed_out) *needed_out = (int32_t)r.size();
     std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
+}
+
+int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
+                           size_t scratch_bytes, int32_t violation, int32_t* out) {
+    if (!out || state_dim <= 0 || observation_dim < state_dim || action_dim <= 0 || batch <= 0 || horizon <= 0)
+        return fail(DAD_E_INVALID, "bad argument");
+    const long D = (long)(horizon + 1) * state_dim + (long)horizon * action_dim;
+    if (D > INT32_MAX / 64) return fail(DAD_E_INVALID, "projection dimension D=%ld too large", D);
+    const size_t x_bytes = (size_t)batch * horizon * (observation_dim + action_dim) * sizeof(float);
+    const ProjectPlan q = plan_project((int)D, batch, x_bytes, scratch_bytes, violation != 0);
+    out[DAD_PP_FORM] = q.form;
+    out[DAD_PP_ROWS_PER_BLOCK] = q.rows_per_block;
+    out[DAD_PP_GX] = (int32_t)q.gx;
+    out[DAD_PP_GY] = (int32_t)q.gy;
+    out[DAD_PP_LDS_BYTES] = (int32_t)std::min<size_t>(q.lds_bytes, INT32_MAX);
+    out[DAD_PP_REFUSED] = q.refused;
     return DAD_OK;
 }
 

@@ -1559,6 +1559,42 @@ inline size_t workspace_bytes(const HostModel& m, int batch) {
     return f.bytes;
 }
 
+// ------------------------------------------------------------------ projection: which kernel, on which grid
+// One call of dad_project / dad_projection_violation (run_project launches from this; dad_debug_project_plan reports
+// it).  D = (H+1) n + H m, x_bytes: the batch of trajectories, scratch_bytes: dad_project_args.scratch (0 without one).
+struct ProjectPlan {
+    int form = DAD_PP_ROW1;  // DAD_PP_ROW1 project_kernel<1,16>, DAD_PP_ROW4 project_kernel<4,16>, DAD_PP_GEMM project_gemm_kernel
+    int rows_per_block = 1;
+    unsigned gx = 1, gy = 1;
+    size_t lds_bytes = 0;
+    bool refused = false;    // one trajectory's partial sums exceed LDS and the GEMM form is not to be had
+};
+inline ProjectPlan plan_project(int D, int batch, size_t x_bytes, size_t scratch_bytes, bool violation) {
+    ProjectPlan q;
+    // batches of 32+ trajectories with scratch for the projected copy: v @ P as an MFMA GEMM (P read once
+    // per 32 trajectories, not once per trajectory)
+    // (at PointMaze size, D = 196, the per-trajectory kernel is the faster one: 10 us against 16.6 us for
+    // 256 plans — 56 GEMM blocks leave most of the chip idle; the GEMM takes over from D = 512)
+    const size_t row_lds = dad::project_row_lds_bytes(D);             // a row + its 16 partial sets
+    const bool gemm_pays = D >= 512 || row_lds > dad::kLdsBytes;
+    if (!violation && gemm_pays && batch >= 32 && scratch_bytes > 0 && scratch_bytes >= x_bytes) {
+        q.form = DAD_PP_GEMM;
+        q.rows_per_block = 32;
+        q.gx = (unsigned)((batch + 31) / 32); q.gy = (unsigned)((D + 31) / 32);
+        q.lds_bytes = dad::project_gemm_lds_floats() * sizeof(float);
+        return q;
+    }
+    // rows per block: one while the batch fits one wave of blocks (every CU streams P once),
+    // four beyond that (P is then re-used by four rows per pass) if four rows fit LDS
+    const int rb = (batch > 512 && 4 * row_lds <= dad::kLdsBytes) ? 4 : 1;
+    q.form = rb == 4 ? DAD_PP_ROW4 : DAD_PP_ROW1;
+    q.rows_per_block = rb;
+    q.gx = (unsigned)((batch + rb - 1) / rb);
+    q.lds_bytes = rb * row_lds;
+    q.refused = q.lds_bytes > dad::kLdsBytes;
+    return q;
+}
+
 // ------------------------------------------------------------------ backward pass: per-batch geometry
 // conv_wgrad instantiations exist for these tap counts (the list of dad_lib.hip, wgrad_kernels, is built from them)
 constexpr int kWgradTaps[] = {1, 3, 4, 5, 7};

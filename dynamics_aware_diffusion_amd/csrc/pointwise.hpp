@@ -329,10 +329,7 @@ __global__ __launch_bounds__(64 * KP) void project_kernel(const ProjParams p) {
 // a wave-private LDS tile.  The epilogue blends and scatters its 32 x 32 outputs
 // (guides/policies.py:451-483) into a scratch copy of the batch (other blocks are still gathering from
 // x); the host copies it back.  No atomics: bit-reproducible.
-constexpr int PG_THREADS = 256;
-constexpr int PG_KC = 64;                     // k values per staged chunk
-constexpr int PG_AS = 33;                     // LDS row stride of the staged v chunk [k][32 rows]
-__host__ __device__ inline size_t project_gemm_lds_floats() { return (size_t)4 * PG_KC * PG_AS + 64; }
+// (PG_THREADS, PG_KC, PG_AS, project_gemm_lds_floats: conv_shapes.hpp)
 
 // element d of trajectory row `xb` in physical units (policies.py:434-448)
 __device__ __forceinline__ float proj_gather(const ProjParams& p, const float* xb, int d, int nstate, int td) {

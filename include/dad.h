@@ -534,6 +534,30 @@ int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t 
 #define DAD_FP_CC_RES_KIND 12
 #define DAD_FP_CC_INTS 13
 int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out);
+/* Which kernel one dad_project (violation == 0) or dad_projection_violation (violation != 0) call launches for
+ * trajectories (batch, horizon, observation_dim + action_dim) and a dad_project_args.scratch of scratch_bytes (0: none),
+ * and on which grid: the plan the two entry points launch from.  Host logic only, no device call.  out[DAD_PP_INTS]:
+ *   [DAD_PP_FORM]            DAD_PP_ROW1 (project_kernel<1,16>: one trajectory per block), DAD_PP_ROW4 (project_kernel<4,16>:
+ *                            four per block, batches beyond 512 whose four rows fit LDS) or DAD_PP_GEMM (project_gemm_kernel:
+ *                            32 trajectories x 32 columns of P per block; never for the violation)
+ *   [DAD_PP_ROWS_PER_BLOCK]  1, 4 or 32
+ *   [DAD_PP_GX] [DAD_PP_GY]  the grid
+ *   [DAD_PP_LDS_BYTES]       dynamic LDS of one block
+ *   [DAD_PP_REFUSED]         1: the call fails with DAD_E_INVALID (one trajectory's partial sums exceed LDS and there is
+ *                            no scratch, or fewer than 32 trajectories, for the GEMM form); the other fields then describe
+ *                            the launch that does not fit */
+#define DAD_PP_FORM 0
+#define DAD_PP_ROWS_PER_BLOCK 1
+#define DAD_PP_GX 2
+#define DAD_PP_GY 3
+#define DAD_PP_LDS_BYTES 4
+#define DAD_PP_REFUSED 5
+#define DAD_PP_INTS 6
+#define DAD_PP_ROW1 0
+#define DAD_PP_ROW4 1
+#define DAD_PP_GEMM 2
+int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
+                           size_t scratch_bytes, int32_t violation, int32_t* out);
 /* 1 where the conv-GEMM instantiation (tile cfg, taps, stride, flag word as above) exists: the planner's one statement of
  * it (kernel_registered_f), whose domain is cfg 0..9, taps 1..7, stride 1..2, flags 0..63.  No device call. */
 int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32_t flags);

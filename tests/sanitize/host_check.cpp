@@ -841,6 +841,39 @@ int main(int argc, char** argv) {
         CHECK(e.size() == 320 && e[0] == 0.0f && e[16] == 1.0f, "sinusoid table t=0");
         CHECK(std::fabs(e[32] - std::sin(1.0f)) < 1e-7, "sinusoid table t=1");
     }
+    // projection plan: every (D, batch), with and without scratch, for dad_project and the violation, either fits
+    // LDS on a grid that covers the batch (and, as a GEMM, the columns of P) or is refused; the GEMM form needs
+    // scratch for the whole batch and 32 trajectories, and never serves the violation
+    {
+        long plans = 0, refused = 0, forms[3] = {0, 0, 0};
+        for (int D : {1, 7, 33, 63, 64, 65, 196, 511, 512, 524, 602, 603, 753, 2183, 2409, 2410, 4096, 100000})
+            for (int batch : {1, 3, 4, 31, 32, 33, 256, 512, 513, 515, 4096})
+                for (int with_scratch : {0, 1, 2})
+                    for (int violation : {0, 1}) {
+                        const size_t x_bytes = (size_t)batch * 96 * sizeof(float);
+                        const size_t scratch = with_scratch == 0 ? 0 : with_scratch == 1 ? x_bytes - 4 : x_bytes;
+                        const ProjectPlan q = plan_project(D, batch, x_bytes, scratch, violation != 0);
+                        ++plans; refused += q.refused;
+                        CHECK(q.form >= DAD_PP_ROW1 && q.form <= DAD_PP_GEMM, "D=%d B=%d: form %d", D, batch, q.form);
+                        ++forms[q.form];
+                        CHECK(q.refused || q.lds_bytes <= dad::kLdsBytes, "D=%d B=%d: %zu bytes of LDS accepted", D, batch, q.lds_bytes);
+                        CHECK((long)q.gx * q.rows_per_block >= batch && (long)(q.gx - 1) * q.rows_per_block < batch,
+                              "D=%d B=%d: grid x %u of %d rows", D, batch, q.gx, q.rows_per_block);
+                        if (q.form == DAD_PP_GEMM) {
+                            CHECK(!q.refused && !violation && batch >= 32 && scratch >= x_bytes, "D=%d B=%d: GEMM form", D, batch);
+                            CHECK(q.rows_per_block == 32 && (long)q.gy * 32 >= D && (long)(q.gy - 1) * 32 < D, "D=%d: grid y %u", D, q.gy);
+                            CHECK(q.lds_bytes >= (size_t)4 * 32 * dad::PG_AS * sizeof(float), "GEMM exchange tile");
+                        } else {
+                            CHECK(q.gy == 1 && q.rows_per_block == (q.form == DAD_PP_ROW4 ? 4 : 1), "D=%d B=%d: rows", D, batch);
+                            CHECK(q.lds_bytes == (size_t)q.rows_per_block * (1 + dad::PROJ_KP) * D * sizeof(float), "D=%d: row LDS", D);
+                            CHECK(q.form == DAD_PP_ROW1 || batch > 512, "D=%d B=%d: four rows per block within one wave of blocks", D, batch);
+                        }
+                        CHECK(q.refused == (q.form != DAD_PP_GEMM && (size_t)(1 + dad::PROJ_KP) * D * sizeof(float) > dad::kLdsBytes),
+                              "D=%d B=%d: refusal", D, batch);
+                    }
+        CHECK(forms[0] && forms[1] && forms[2] && refused, "the projection sweep misses a form or the refusal");
+        printf("  projection plan: %ld plans (%ld row1, %ld row4, %ld gemm), %ld refused\n", plans, forms[0], forms[1], forms[2], refused);
+    }
     CHECK(g_reports > 0, "no forward-plan report was compared");
     if (g_failures) { fprintf(stderr, "%d host-logic checks FAILED\n", g_failures); return 1; }
     printf("host logic ok (%ld forward-plan reports equal the descriptions they were read from)\n", g_reports);
