@@ -117,6 +117,9 @@ ABI = {
                                              C.POINTER(C.c_int32)]),
     "dad_debug_backward_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                           C.POINTER(C.c_int32)]),
+    "dad_debug_backward_steps": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                           C.POINTER(C.c_int32)]),
+    "dad_debug_wgrad_kernel_exists": (C.c_int, [C.c_int32] * 3),
     "dad_model_set_training": (C.c_int, [C.c_void_p, C.c_int32]),
     "dad_model_refresh_weights": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                             C.c_void_p]),
@@ -247,6 +250,28 @@ def registered_kernels():
                         if lib.dad_debug_small_kernel_exists(taps, stride, ride, 1, 0, a, rows, 0):
                             ccw.add(("ccw", taps, stride, ride, a, rows))
     return gemm, cc, ccw
+
+
+# DAD_BS_* of include/dad.h: the records of dad_debug_backward_steps, by kind (field 0 is the kind itself)
+BS_KINDS = ("bias", "wgrad", "dgrad", "gn", "resid", "cols")
+BS_FIELDS = {
+    "bias": ("rows", "C"),
+    "wgrad": ("taps", "tile", "windowed", "M", "C0", "C1", "stride", "pad", "Lg", "Lz", "gx", "gy", "ragged", "concat_inside",
+              "edge_m", "edge_c", "swapped", "ksplit", "slab_n4", "samples", "spc", "sps", "chunks", "last_chunks"),
+    "dgrad": ("conv", "sub", "write"),
+    "gn": ("nv", "cpg", "L", "lreal", "cpg_real", "dtemb", "short_pair", "C"),
+    "resid": ("write", "n", "to_x"),
+    "cols": ("C", "off", "ld", "rows", "write"),
+}
+BS_WRITES = ("set", "add", "stage")       # BwdWrite of csrc/host_plan.hpp
+
+
+def wgrad_kernels():
+    """Every (taps, tile, windowed) of the library's conv_wgrad registry (dad_debug_wgrad_kernel_exists over taps 1..8,
+    tiles 0..3); host logic only."""
+    lib = load_library()
+    return {(taps, tile, win) for taps in range(1, 9) for tile in range(4) for win in (0, 1)
+            if lib.dad_debug_wgrad_kernel_exists(taps, tile, win)}
 
 
 def projection_plan(state_dim: int, observation_dim: int, action_dim: int, batch: int, horizon: int, *,
@@ -834,6 +859,29 @@ class HipEngine:
             "fwd": hist(31), "dgrad": hist(51),
             "launches": [dict(zip(fields, r[at:at + len(fields)])) for at in range(72, len(r), len(fields))],
         }
+
+    def backward_steps(self, batch: int) -> dict:
+        """Everything dad_unet_backward replays at `batch` under the current debug options (dad_debug_backward_steps:
+        host logic only, as :meth:`backward_plan`).  Returns ``batch``, ``colsums`` (launches, entries, widest),
+        ``padcopy`` (the zero-padded horizon's copies run), ``horizon`` / ``real_horizon``, ``dx`` and ``steps``: one
+        dict per step in launch order with ``kind`` (a name of BS_KINDS) and the fields of BS_FIELDS for that kind
+        (DAD_BS_* of include/dad.h); ``write`` is a name of BS_WRITES."""
+        need = C.c_int32()
+        _check(self.lib, self.lib.dad_debug_backward_steps(self._h, int(batch), None, 0, C.byref(need)))
+        buf = (C.c_int32 * need.value)()
+        _check(self.lib, self.lib.dad_debug_backward_steps(self._h, int(batch), buf, need.value, C.byref(need)))
+        r = list(buf)
+        ints = r[1]
+        assert ints == 25 and len(r) - 12 == r[0] * ints
+        steps = []
+        for at in range(12, len(r), ints):
+            kind = BS_KINDS[r[at]]
+            q = dict(zip(BS_FIELDS[kind], r[at + 1:at + ints]), kind=kind)
+            if "write" in q:
+                q["write"] = BS_WRITES[q["write"]]
+            steps.append(q)
+        return {"batch": r[2], "colsums": (r[3], r[4], r[5]), "padcopy": bool(r[6]), "horizon": r[7], "real_horizon": r[8],
+                "dx": bool(r[9]), "steps": steps}
 
     def objective_plan(self, batch: int) -> dict:
         """The time chain of one fused objective step at `batch` (host logic only, as :meth:`backward_plan`).  Keys as

@@ -49,6 +49,8 @@ constexpr int WG_THREADS = 512;             // 8 waves: TM x TN wave tiles of 32
 constexpr int WG_ROWS = 64;                  // G rows per staged chunk: spc = max(1, 64 / Lg) whole samples
 constexpr int WG_MAX_GROWS = 128, WG_MAX_ZROWS = 160;      // rows one chunk may stage (registers of chunk_load)
 
+constexpr int COLS_MAX = 120;                // col_sums_many_kernel: arrays per launch (descriptors travel as kernel arguments)
+
 DAD_HD inline int wgrad_segz(int Lz, int taps, int pad) { return Lz + pad + (taps - 1 - pad); }
 DAD_HD inline int wgrad_round64(int v) { return (v + 63) / 64 * 64; }
 // LDS floats: two stages of a chunk (G rows [spc * Lg][32 TM], Z rows with halo [spc * SEGZ][32 TN], each part

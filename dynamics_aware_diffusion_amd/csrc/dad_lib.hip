@@ -1345,9 +1345,10 @@ static int unet_backward(dad_model* m, const float* x, const float* d_out, float
                 gp.gamma = f.d_gamma; gp.beta = f.d_beta;
                 gp.dH = ptr(s.out);
                 gp.part_dgamma = part + s.part * B; gp.part_dbeta = gp.part_dgamma + c4 * B; gp.part_dbias = gp.part_dbeta + c4 * B;
-                gp.dtemb = f.temb_off >= 0 ? d_temb_rows + f.temb_off : nullptr;
+                const GnBwdShape q = gn_bwd_shape(f);
+                gp.dtemb = q.dtemb ? d_temb_rows + f.temb_off : nullptr;
                 gp.temb_stride = P.temb_width;
-                gp.C = f.cout; gp.L = f.Lout; gp.cpg = f.cout / 8; gp.lreal = f.lreal; gp.cpg_real = f.gn_real;
+                gp.C = q.C; gp.L = q.L; gp.cpg = q.cpg; gp.lreal = q.lreal; gp.cpg_real = q.cpg_real;
                 gp.B = B;
                 const dim3 wgrid((unsigned)((B * 8 + 3) / 4));
                 switch (s.nv) {
@@ -1754,6 +1755,22 @@ int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t c
     if (needed_out) *needed_out = (int32_t)r.size();
     std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
     return DAD_OK;
+}
+
+int dad_debug_backward_steps(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
+    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
+    std::vector<int32_t> r;
+    const int rc = backward_steps_report(*m, batch, r);     // (a batch the backward pass refuses is refused here too)
+    if (rc != DAD_OK) return rc;
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
+}
+
+int dad_debug_wgrad_kernel_exists(int32_t taps, int32_t tile, int32_t windowed) {
+    return wgrad_kernel(taps, tile, windowed != 0) != nullptr ? 1 : 0;
 }
 
 int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {

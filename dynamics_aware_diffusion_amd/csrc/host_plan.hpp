@@ -1816,6 +1816,88 @@ inline int backward_plan_report(const HostModel& m, int B, std::vector<int32_t>&
     return rc;
 }
 
+// What a BK_GN step hands gn_mish_bwd_kernel / gn_mish_bwd_wave_kernel besides its pointers: read from the forward conv
+// the step belongs to.  dad_unet_backward fills GnBwdParams from it, backward_steps_encode writes it down.
+struct GnBwdShape { int C, L, cpg, lreal, cpg_real; bool dtemb; };
+inline GnBwdShape gn_bwd_shape(const ConvOp& f) { return {f.cout, f.Lout, f.cout / 8, f.lreal, f.gn_real, f.temb_off >= 0}; }
+// The col_sums_many_kernel launches that end a pass: bsums in order, at most dad::COLS_MAX per launch.
+inline int col_sums_launches(const HostModel& m) { return (int)((m.bsums.size() + dad::COLS_MAX - 1) / dad::COLS_MAX); }
+
+// dad_debug_backward_steps: everything dad_unet_backward replays at batch B, step by step (layout: include/dad.h,
+// DAD_BS_*).  backward_steps_encode writes down m.bsteps / m.bsums with the geometry `ts` (train_scratch) the entry
+// point launches from and decides nothing; backward_steps_report plans the pass as the entry point does and encodes it.
+inline void backward_steps_encode(const HostModel& m, int B, const TrainScratch& ts, std::vector<int32_t>& r) {
+    const int H = m.cfg.horizon, Hr = traj_horizon(m);
+    r.assign(DAD_BS_HEADER, 0);
+    r[DAD_BS_RECORD_INTS] = DAD_BS_REC_INTS;
+    r[DAD_BS_BATCH] = B;
+    r[DAD_BS_COLSUMS_LAUNCHES] = col_sums_launches(m);
+    r[DAD_BS_COLSUMS_ENTRIES] = (int32_t)m.bsums.size();
+    for (const BwdSum& q : m.bsums) r[DAD_BS_COLSUMS_WIDEST] = std::max(r[DAD_BS_COLSUMS_WIDEST], (int32_t)q.C);
+    r[DAD_BS_PADCOPY] = Hr != H;
+    r[DAD_BS_HORIZON] = H;
+    r[DAD_BS_REAL_HORIZON] = Hr;
+    r[DAD_BS_DX] = m.bdx;
+    size_t nw = 0;
+    for (const BwdStep& s : m.bsteps) {
+        int32_t rec[DAD_BS_REC_INTS] = {0};
+        rec[DAD_BS_KIND] = (int32_t)s.kind;
+        switch (s.kind) {
+            case BK_BIAS:
+                rec[DAD_BS_BIAS_ROWS] = s.rows; rec[DAD_BS_BIAS_C] = s.C;
+                break;
+            case BK_WGRAD: {
+                if (nw >= ts.wgrads.size()) break;
+                const WgradShape& sh = ts.wgrads[nw].sh;
+                const WgradGeom& g = ts.wgrads[nw++].g;
+                const int Ctot = s.C0 + s.C1, wm = 32 * g.tm, wn = 32 * g.tn;
+                const long numel = (long)s.M * Ctot * s.taps;
+                rec[DAD_BS_WG_TAPS] = s.taps; rec[DAD_BS_WG_TILE] = g.tile; rec[DAD_BS_WG_WINDOWED] = sh.wshift > 0;
+                rec[DAD_BS_WG_M] = s.M; rec[DAD_BS_WG_C0] = s.C0; rec[DAD_BS_WG_C1] = s.C1;
+                rec[DAD_BS_WG_STRIDE] = s.stride; rec[DAD_BS_WG_PAD] = s.pad; rec[DAD_BS_WG_LG] = sh.Lg; rec[DAD_BS_WG_LZ] = sh.Lz;
+                rec[DAD_BS_WG_GX] = (int32_t)g.gx; rec[DAD_BS_WG_GY] = (int32_t)g.gy;
+                rec[DAD_BS_WG_RAGGED] = g.tile == 3;
+                rec[DAD_BS_WG_CONCAT_INSIDE] = s.C1 > 0 && s.C0 % wn != 0;
+                rec[DAD_BS_WG_EDGE_M] = s.M % wm != 0;
+                rec[DAD_BS_WG_EDGE_C] = Ctot % wn != 0;
+                rec[DAD_BS_WG_SWAPPED] = s.in.sp == BSP_ACT || s.in.sp == BSP_X;
+                rec[DAD_BS_WG_KSPLIT] = g.ksplit;
+                rec[DAD_BS_WG_SLAB_N4] = g.ksplit > 1 ? (int32_t)(numel / 4) : 0;
+                rec[DAD_BS_WG_SAMPLES] = sh.B; rec[DAD_BS_WG_SPC] = g.spc; rec[DAD_BS_WG_SPS] = g.sps;
+                rec[DAD_BS_WG_CHUNKS] = (std::min(g.sps, sh.B) + g.spc - 1) / g.spc;
+                rec[DAD_BS_WG_LAST_CHUNKS] = (sh.B - (g.ksplit - 1) * g.sps + g.spc - 1) / g.spc;
+                break;
+            }
+            case BK_DGRAD:
+                rec[DAD_BS_DG_CONV] = s.conv; rec[DAD_BS_DG_SUB] = s.sub; rec[DAD_BS_DG_WRITE] = (int32_t)s.write;
+                break;
+            case BK_GN: {
+                const GnBwdShape q = gn_bwd_shape(m.tplan.convs[s.conv]);
+                rec[DAD_BS_GN_NV] = s.nv; rec[DAD_BS_GN_CPG] = q.cpg; rec[DAD_BS_GN_L] = q.L; rec[DAD_BS_GN_LREAL] = q.lreal;
+                rec[DAD_BS_GN_CPG_REAL] = q.cpg_real; rec[DAD_BS_GN_DTEMB] = q.dtemb; rec[DAD_BS_GN_C] = q.C;
+                rec[DAD_BS_GN_SHORT_PAIR] = q.cpg / 4 * q.L < 64;
+                break;
+            }
+            case BK_RESID:
+                rec[DAD_BS_RS_WRITE] = (int32_t)s.write; rec[DAD_BS_RS_N] = (int32_t)std::min<long>(s.n, INT32_MAX);
+                rec[DAD_BS_RS_TO_X] = s.out.sp == BSP_DX;
+                break;
+            case BK_COLS:
+                rec[DAD_BS_CL_C] = s.C; rec[DAD_BS_CL_OFF] = s.off; rec[DAD_BS_CL_LD] = s.ld; rec[DAD_BS_CL_ROWS] = s.rows;
+                rec[DAD_BS_CL_WRITE] = (int32_t)s.write;
+                break;
+        }
+        r.insert(r.end(), rec, rec + DAD_BS_REC_INTS);
+        ++r[DAD_BS_STEPS];
+    }
+}
+inline int backward_steps_report(const HostModel& m, int B, std::vector<int32_t>& r) {
+    TrainScratch ts;
+    const int rc = train_scratch(m, B, ts);
+    backward_steps_encode(m, B, ts, r);
+    return rc;
+}
+
 // dad_debug_objective_plan: the time chain of one fused objective step at batch B (layout: include/dad.h, DAD_OP_*),
 // read from the list dad_train_objective_forward / _backward replay (ObjectivePlan::time).
 inline int objective_plan_report(const HostModel& m, int B, std::vector<int32_t>& r) {

@@ -430,8 +430,7 @@ __global__ __launch_bounds__(256) void col_sums_kernel(float* out, const float* 
 // The same for MANY [B][C] arrays in one launch (blockIdx.y picks the array): every layer of a backward pass parks
 // its per-sample partial sums (d gamma, d beta, d bias) in a region of its own and ONE launch at the end of the pass
 // reduces them all — 45 launches of ~5 us each on a PointMaze step become one.  The descriptors travel as kernel
-// arguments (no upload): at most COLS_MAX per launch.
-constexpr int COLS_MAX = 120;
+// arguments (no upload): at most COLS_MAX (conv_shapes.hpp) per launch.
 struct ColSumsMany { float* out[COLS_MAX]; const float* part[COLS_MAX]; int32_t C[COLS_MAX]; };
 __global__ __launch_bounds__(256) void col_sums_many_kernel(const ColSumsMany a, int B) {
     __shared__ float red[8][33];

@@ -415,6 +415,101 @@ int dad_debug_small_batch_plan(dad_model* m, int32_t batch, int32_t* launches_ou
 #define DAD_BP_REC_INTS 9
 int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
 
+/* Everything dad_unet_backward replays at a batch, step by step, read from the list of steps and the per-batch geometry
+ * the entry point launches from (host-side query, no device work; the conditions of dad_debug_backward_plan).  Writes
+ * min(capacity, *needed_out) int32 values to `out`:
+ *   [DAD_BS_STEPS]             records that follow from DAD_BS_HEADER on, [DAD_BS_RECORD_INTS] ints each, in launch order
+ *   [DAD_BS_BATCH]             the batch
+ *   [DAD_BS_COLSUMS_LAUNCHES]  col_sums_many_kernel launches that end the pass ([DAD_BS_COLSUMS_ENTRIES] arrays of
+ *                              `batch` rows in all, the widest of [DAD_BS_COLSUMS_WIDEST] columns)
+ *   [DAD_BS_PADCOPY]           1: the horizon is zero padded ([DAD_BS_REAL_HORIZON] of [DAD_BS_HORIZON] positions exist):
+ *                              pad_rows_kernel copies the trajectory and d out in, slice_rows_cols_kernel copies d x out
+ *   [DAD_BS_DX]                1: a gradient reaches the trajectory
+ * A record starts with its kind, [DAD_BS_KIND] = DAD_BS_K_*; fields a kind does not name are 0.
+ *   DAD_BS_K_BIAS   row_partial_sums_kernel: rows per sample, columns
+ *   DAD_BS_K_WGRAD  conv_wgrad<taps, tile, windowed>: M, C0, C1 (the Z operand is the concat [C0 | C1]), stride, pad, Lg and
+ *                   Lz (rows per sample of G and Z as the kernel counts them: per window when windowed), grid x / y,
+ *                   ragged (rows that are not whole aligned float4s), concat_inside (the boundary C0 falls inside one
+ *                   block's staged columns), edge_m / edge_c (the last M / C tile is partly filled), swapped (G is the
+ *                   conv's input, Z the gradient: the transposed conv), ksplit, slab_n4 (float4s per slab
+ *                   sum_slabs_kernel adds; 0 when ksplit == 1), and samples, spc, sps, chunks, last_chunks as
+ *                   DAD_BP_REC_* of dad_debug_backward_plan
+ *   DAD_BS_K_DGRAD  a data-gradient conv (its launch: mode 3 of dad_debug_forward_plan): forward conv, sub, write (0 set,
+ *                   1 add through the residual operand, 2 staged and added by add_inplace_kernel)
+ *   DAD_BS_K_GN     gn_mish_bwd_wave_kernel<nv> (nv = 0: gn_mish_bwd_kernel): channels per group, L, lreal (> 0: positions
+ *                   that exist), cpg_real (> 0: channels per group that exist), dtemb (d time projection is written),
+ *                   short_pair (a pair has fewer than 64 float4), C
+ *   DAD_BS_K_RESID  identity residual: write (0: a copy, 1: add_inplace_kernel), floats per sample, to_x (into d x)
+ *   DAD_BS_K_COLS   take_cols_kernel: C columns at `off` of rows of `ld`, rows per sample, write (1: accumulates) */
+#define DAD_BS_STEPS 0
+#define DAD_BS_RECORD_INTS 1
+#define DAD_BS_BATCH 2
+#define DAD_BS_COLSUMS_LAUNCHES 3
+#define DAD_BS_COLSUMS_ENTRIES 4
+#define DAD_BS_COLSUMS_WIDEST 5
+#define DAD_BS_PADCOPY 6
+#define DAD_BS_HORIZON 7
+#define DAD_BS_REAL_HORIZON 8
+#define DAD_BS_DX 9
+#define DAD_BS_HEADER 12
+#define DAD_BS_K_BIAS 0
+#define DAD_BS_K_WGRAD 1
+#define DAD_BS_K_DGRAD 2
+#define DAD_BS_K_GN 3
+#define DAD_BS_K_RESID 4
+#define DAD_BS_K_COLS 5
+#define DAD_BS_KIND 0
+#define DAD_BS_BIAS_ROWS 1
+#define DAD_BS_BIAS_C 2
+#define DAD_BS_WG_TAPS 1
+#define DAD_BS_WG_TILE 2
+#define DAD_BS_WG_WINDOWED 3
+#define DAD_BS_WG_M 4
+#define DAD_BS_WG_C0 5
+#define DAD_BS_WG_C1 6
+#define DAD_BS_WG_STRIDE 7
+#define DAD_BS_WG_PAD 8
+#define DAD_BS_WG_LG 9
+#define DAD_BS_WG_LZ 10
+#define DAD_BS_WG_GX 11
+#define DAD_BS_WG_GY 12
+#define DAD_BS_WG_RAGGED 13
+#define DAD_BS_WG_CONCAT_INSIDE 14
+#define DAD_BS_WG_EDGE_M 15
+#define DAD_BS_WG_EDGE_C 16
+#define DAD_BS_WG_SWAPPED 17
+#define DAD_BS_WG_KSPLIT 18
+#define DAD_BS_WG_SLAB_N4 19
+#define DAD_BS_WG_SAMPLES 20
+#define DAD_BS_WG_SPC 21
+#define DAD_BS_WG_SPS 22
+#define DAD_BS_WG_CHUNKS 23
+#define DAD_BS_WG_LAST_CHUNKS 24
+#define DAD_BS_DG_CONV 1
+#define DAD_BS_DG_SUB 2
+#define DAD_BS_DG_WRITE 3
+#define DAD_BS_GN_NV 1
+#define DAD_BS_GN_CPG 2
+#define DAD_BS_GN_L 3
+#define DAD_BS_GN_LREAL 4
+#define DAD_BS_GN_CPG_REAL 5
+#define DAD_BS_GN_DTEMB 6
+#define DAD_BS_GN_SHORT_PAIR 7
+#define DAD_BS_GN_C 8
+#define DAD_BS_RS_WRITE 1
+#define DAD_BS_RS_N 2
+#define DAD_BS_RS_TO_X 3
+#define DAD_BS_CL_C 1
+#define DAD_BS_CL_OFF 2
+#define DAD_BS_CL_LD 3
+#define DAD_BS_CL_ROWS 4
+#define DAD_BS_CL_WRITE 5
+#define DAD_BS_REC_INTS 25
+int dad_debug_backward_steps(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
+/* 1 when conv_wgrad<taps, tile, windowed> is in the library's registry of weight-gradient kernels (tile as
+ * DAD_BP_TILE; no device call): lets a test walk the whole domain */
+int dad_debug_wgrad_kernel_exists(int32_t taps, int32_t tile, int32_t windowed);
+
 /* The time chain of one fused objective step (dad_train_objective_forward + dad_train_objective_backward) at a batch:
  * the list of launches the two entry points replay (host-side query, no device work; needs
  * dad_model_set_training(m, 1) but neither weights nor dad_model_finalize; a batch the objective refuses is refused

@@ -223,6 +223,102 @@ static void check_forward_report(const HostModel& m, int mode, int B, const FwdP
     }
 }
 
+// dad_debug_backward_steps: one record per step of m.bsteps, in order, each field equal to what dad_unet_backward reads for
+// that step — the step itself, the forward conv a GroupNorm step belongs to, the geometry `ts` of train_scratch.  The
+// derived fields are recomputed here the way the kernels see them (block origins, staged widths), not the way the
+// report computes them.
+static long g_step_reports = 0;
+static void check_backward_steps(const HostModel& m, int B, const TrainScratch& ts, int rc_plan) {
+    std::vector<int32_t> r;
+    const int rc = backward_steps_report(m, B, r);
+    CHECK(rc == rc_plan, "B=%d: the step report returns %d, train_scratch %d", B, rc, rc_plan);
+    CHECK(r.size() >= DAD_BS_HEADER && r[DAD_BS_BATCH] == B && r[DAD_BS_RECORD_INTS] == DAD_BS_REC_INTS &&
+          r[DAD_BS_STEPS] == (int)m.bsteps.size() && r.size() == DAD_BS_HEADER + m.bsteps.size() * DAD_BS_REC_INTS,
+          "B=%d: step report of %zu ints for %zu steps", B, r.size(), m.bsteps.size());
+    if (r.size() != DAD_BS_HEADER + m.bsteps.size() * DAD_BS_REC_INTS) return;
+    ++g_step_reports;
+    const int H = m.cfg.horizon, Hr = m.real_horizon > 0 ? m.real_horizon : H;
+    int widest = 0;
+    for (const BwdSum& q : m.bsums) widest = std::max(widest, q.C);
+    int launches = 0;
+    for (size_t at = 0; at < m.bsums.size(); at += dad::COLS_MAX) ++launches;       // the loop of dad_unet_backward
+    CHECK(r[DAD_BS_COLSUMS_LAUNCHES] == launches && r[DAD_BS_COLSUMS_ENTRIES] == (int)m.bsums.size() && r[DAD_BS_COLSUMS_WIDEST] == widest,
+          "B=%d: column sums: %d launches, %d entries, widest %d", B, r[DAD_BS_COLSUMS_LAUNCHES], r[DAD_BS_COLSUMS_ENTRIES], r[DAD_BS_COLSUMS_WIDEST]);
+    CHECK((r[DAD_BS_PADCOPY] != 0) == (Hr != H) && r[DAD_BS_HORIZON] == H && r[DAD_BS_REAL_HORIZON] == Hr && (r[DAD_BS_DX] != 0) == m.bdx,
+          "B=%d: padded-horizon copies %d (%d of %d positions)", B, r[DAD_BS_PADCOPY], r[DAD_BS_REAL_HORIZON], r[DAD_BS_HORIZON]);
+    size_t nw = 0;
+    for (size_t i = 0; i < m.bsteps.size(); ++i) {
+        const BwdStep& s = m.bsteps[i];
+        const int32_t* q = &r[DAD_BS_HEADER + i * DAD_BS_REC_INTS];
+        CHECK(q[DAD_BS_KIND] == (int)s.kind, "B=%d step %zu: kind %d, the plan says %d", B, i, q[DAD_BS_KIND], (int)s.kind);
+        int used = 1;                          // fields the kind names; the rest must be 0
+        switch (s.kind) {
+            case BK_BIAS:
+                CHECK(q[DAD_BS_BIAS_ROWS] == s.rows && q[DAD_BS_BIAS_C] == s.C, "B=%d step %zu: bias record", B, i);
+                used = 3;
+                break;
+            case BK_WGRAD: {
+                if (nw >= ts.wgrads.size()) { CHECK(false, "B=%d step %zu: no geometry", B, i); break; }
+                const WgradShape& sh = ts.wgrads[nw].sh;
+                const WgradGeom& g = ts.wgrads[nw++].g;
+                const int Ctot = s.C0 + s.C1, WMW = 32 * g.tm, WNW = 32 * g.tn;
+                bool inside = false;           // a block whose staged columns [c0, c0 + WNW) hold both sides of the concat
+                for (unsigned by = 0; by < g.gy; ++by) inside = inside || (s.C1 > 0 && (int)by * WNW < s.C0 && s.C0 < (int)(by + 1) * WNW);
+                int at = 0, fullest = 0, last = 0;
+                for (int ks = 0; ks < g.ksplit; ++ks) {
+                    const int hi = std::min(sh.B, (ks + 1) * g.sps);
+                    last = (hi - at + g.spc - 1) / g.spc;
+                    fullest = std::max(fullest, last);
+                    at = hi;
+                }
+                CHECK(q[DAD_BS_WG_TAPS] == s.taps && q[DAD_BS_WG_TILE] == g.tile && (q[DAD_BS_WG_WINDOWED] != 0) == (sh.wshift > 0) &&
+                      q[DAD_BS_WG_M] == s.M && q[DAD_BS_WG_C0] == s.C0 && q[DAD_BS_WG_C1] == s.C1 && q[DAD_BS_WG_STRIDE] == s.stride &&
+                      q[DAD_BS_WG_PAD] == s.pad && q[DAD_BS_WG_LG] == sh.Lg && q[DAD_BS_WG_LZ] == sh.Lz && q[DAD_BS_WG_GX] == (int)g.gx &&
+                      q[DAD_BS_WG_GY] == (int)g.gy, "B=%d step %zu: weight-gradient record (operands)", B, i);
+                CHECK((q[DAD_BS_WG_RAGGED] != 0) == (((s.M | s.C0 | s.C1) & 3) != 0) && (q[DAD_BS_WG_CONCAT_INSIDE] != 0) == inside &&
+                      (q[DAD_BS_WG_EDGE_M] != 0) == ((int)g.gx * WMW != s.M) && (q[DAD_BS_WG_EDGE_C] != 0) == ((int)g.gy * WNW != Ctot) &&
+                      (q[DAD_BS_WG_SWAPPED] != 0) == (s.taps == 4), "B=%d step %zu: weight-gradient record (edges)", B, i);
+                CHECK(q[DAD_BS_WG_KSPLIT] == g.ksplit && q[DAD_BS_WG_SLAB_N4] == (g.ksplit > 1 ? (long)s.M * Ctot * s.taps / 4 : 0) &&
+                      q[DAD_BS_WG_SAMPLES] == sh.B && q[DAD_BS_WG_SPC] == g.spc && q[DAD_BS_WG_SPS] == g.sps && q[DAD_BS_WG_CHUNKS] == fullest &&
+                      q[DAD_BS_WG_LAST_CHUNKS] == last, "B=%d step %zu: weight-gradient record (batch split)", B, i);
+                CHECK(std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) != std::end(kWgradTaps) && g.tile >= 0 && g.tile < 4,
+                      "B=%d step %zu: conv_wgrad<%d, tile %d> does not exist", B, i, s.taps, g.tile);
+                used = DAD_BS_REC_INTS;
+                break;
+            }
+            case BK_DGRAD:
+                CHECK(q[DAD_BS_DG_CONV] == s.conv && q[DAD_BS_DG_SUB] == s.sub && q[DAD_BS_DG_WRITE] == (int)s.write, "B=%d step %zu: data-gradient record", B, i);
+                used = 4;
+                break;
+            case BK_GN: {
+                const ConvOp& f = m.tplan.convs[s.conv];
+                const int nq = f.cout / 8 / 4;
+                CHECK(q[DAD_BS_GN_NV] == s.nv && q[DAD_BS_GN_CPG] == f.cout / 8 && q[DAD_BS_GN_L] == f.Lout && q[DAD_BS_GN_LREAL] == f.lreal &&
+                      q[DAD_BS_GN_CPG_REAL] == f.gn_real && (q[DAD_BS_GN_DTEMB] != 0) == (f.temb_off >= 0) && q[DAD_BS_GN_C] == f.cout &&
+                      (q[DAD_BS_GN_SHORT_PAIR] != 0) == (nq * f.Lout < 64), "B=%d step %zu (%s): GroupNorm record", B, i, f.name.c_str());
+                // the wave form holds a pair in nv x 64 float4; the block form needs a power-of-two quad count <= 64
+                CHECK(s.nv == 0 ? (nq >= 1 && nq <= 64 && is_pow2(nq)) : (nq * f.Lout <= s.nv * 64 && is_pow2(nq) && nq <= 64),
+                      "B=%d step %zu (%s): a pair of %d float4 on gn_mish_bwd_wave_kernel<%d>", B, i, f.name.c_str(), nq * f.Lout, s.nv);
+                used = 9;
+                break;
+            }
+            case BK_RESID:
+                CHECK(q[DAD_BS_RS_WRITE] == (int)s.write && q[DAD_BS_RS_N] == std::min<long>(s.n, INT32_MAX) && (q[DAD_BS_RS_TO_X] != 0) == (s.out.sp == BSP_DX),
+                      "B=%d step %zu: residual record", B, i);
+                used = 4;
+                break;
+            case BK_COLS:
+                CHECK(q[DAD_BS_CL_C] == s.C && q[DAD_BS_CL_OFF] == s.off && q[DAD_BS_CL_LD] == s.ld && q[DAD_BS_CL_ROWS] == s.rows &&
+                      q[DAD_BS_CL_WRITE] == (int)s.write, "B=%d step %zu: column-take record", B, i);
+                CHECK(s.C % 4 == 0 && s.off % 4 == 0 && s.ld % 4 == 0 && s.off + s.C <= s.ld, "B=%d step %zu: take_cols of %d columns at %d of %d", B, i, s.C, s.off, s.ld);
+                used = 6;
+                break;
+        }
+        for (int k = used; k < DAD_BS_REC_INTS; ++k) CHECK(q[k] == 0, "B=%d step %zu: field %d of a kind-%d record is %d", B, i, k, (int)s.kind, q[k]);
+    }
+    CHECK(nw == ts.wgrads.size(), "B=%d: %zu weight-gradient geometries for %zu steps", B, ts.wgrads.size(), nw);
+}
+
 static void check_arch(const Arch& a, int precision) {
     HostModel m;
     dad_cfg& c = m.cfg;
@@ -671,6 +767,7 @@ static void check_arch(const Arch& a, int precision) {
             rc = train_scratch(m, B, ts);
             CHECK(rc == DAD_OK, "backward geometry B=%d: %s", B, g_err);
             check_forward_report(m, 3, B, nullptr, &ts, rc);
+            check_backward_steps(m, B, ts, rc);
             {
                 FwdPlan ft;
                 const int rct = plan_forward(m, true, B, false, ft);
@@ -875,7 +972,9 @@ int main(int argc, char** argv) {
         printf("  projection plan: %ld plans (%ld row1, %ld row4, %ld gemm), %ld refused\n", plans, forms[0], forms[1], forms[2], refused);
     }
     CHECK(g_reports > 0, "no forward-plan report was compared");
+    CHECK(g_step_reports > 0, "no backward-step report was compared");
     if (g_failures) { fprintf(stderr, "%d host-logic checks FAILED\n", g_failures); return 1; }
-    printf("host logic ok (%ld forward-plan reports equal the descriptions they were read from)\n", g_reports);
+    printf("host logic ok (%ld forward-plan and %ld backward-step reports equal the descriptions they were read from)\n", g_reports,
+           g_step_reports);
     return 0;
 }

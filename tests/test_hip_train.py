@@ -7,6 +7,8 @@ sum of squares and max |g| (tests/golden/make_golden.py::gen_grads); the oracle'
 restatement of the forward is pinned to the same fixtures on the CPU (test_oracle_golden.py) and gives
 the element-by-element comparison here.  Gate: |g_hip - g_ref| <= 2e-5 * max|g_ref| per tensor.
 """
+import copy
+
 import numpy as np
 import pytest
 import torch
@@ -304,3 +306,71 @@ def test_refresh_with_unchanged_weights_changes_nothing(net, dev):
     names = ["out B=1", "out B=3", "out B=256", "d x"] + list(diff.model._params())
     for name, a, b in zip(names, before, after):
         assert torch.equal(a, b), f"{name}: max|diff| = {float((a - b).abs().max()):.3e}"
+
+
+@pytest.mark.parametrize("net", [
+    "tiny4", "tiny_d48", (5, 256, (1, 8), 8, 5), (6, 64, (1, 2, 4), 32, 3),        # the nets of the test above
+    (6, 64, (1, 2, 4), 24, 5),         # horizon 24, zero-padded to 32
+    (7, 32, (1, 4), 16, 7),            # kernel_size 7
+], ids=lambda n: n if isinstance(n, str) else f"td{n[0]}_d{n[1]}_m{'x'.join(map(str, n[2]))}_H{n[3]}_k{n[4]}")
+def test_refresh_with_changed_weights_equals_a_fresh_engine(net, dev):
+    """The complement of the test above, which a refresh that skips an image passes (the stale image is then the right
+    one): every parameter moves by an optimiser-sized step (deterministic, from utils/synth), the engine rebuilds its images on the device
+    (dad_model_refresh_weights), and a second engine is built from the new weights on the host (dad_model_finalize).  The
+    two give the same bits: forward outputs at batches 1, 3 and 256, every parameter gradient, d loss / d x."""
+    from dynamics_aware_diffusion_amd import GaussianDiffusion, TemporalUnet
+    from dynamics_aware_diffusion_amd.utils import synth
+    T = 20
+    if isinstance(net, str):
+        od, ad, td, dim, mults = cases.net_dims(net)
+        H, ks, state = cases.H, 5, cases.net_weights(net)
+    else:
+        td, dim, mults, H, ks = net
+        od, ad = td - 1, 1
+        state = synth.synth_unet_state(td, dim, mults, seed=23, affine_jitter=0.3, kernel_size=ks)
+    # the step of a tensor: 4093 draws of 1e-3 x N(0, 1) repeated over it (a prime length: no two taps or rows of a conv
+    # weight move alike, and 160 M draws for the 2048-channel net would cost more than the rest of the test)
+    stepped = {k: (v + np.resize(1e-3 * synth.normal_like(25, f"refresh.step.{k}", (4093,)), v.shape)).astype(np.float32)
+               for k, v in state.items()}
+    assert all(np.any(stepped[k] != state[k]) for k in state)
+    xs = [torch.from_numpy(synth.normal_like(24, f"refresh.x{B}", (B, H, td))).to(dev) for B in (1, 3, 256)]
+    x5 = torch.from_numpy(synth.normal_like(24, "refresh.x5", (5, H, td))).to(dev)
+    t5 = torch.tensor([3, 0, 19, 7, 11], device=dev)
+    target = torch.from_numpy(synth.normal_like(24, "refresh.n5", (5, H, td))).to(dev)
+
+    def build(weights):
+        unet = TemporalUnet(td, dim=dim, dim_mults=mults, kernel_size=ks)
+        unet.load_state_dict({k: torch.from_numpy(v) for k, v in weights.items()})
+        return GaussianDiffusion(unet, H, od, ad, n_timesteps=T).to(dev)
+
+    def run(diff):
+        params = diff.model._params()
+        for p in params.values():
+            p.grad = None
+        with torch.enable_grad():              # (first: the engine is built with training on)
+            x = x5.clone().requires_grad_(True)
+            ((diff.model(x, t5) - target) ** 2).mean().backward()
+        with torch.no_grad():
+            outs = [diff.model(x, 7).clone() for x in xs]
+        torch.cuda.synchronize()
+        return outs + [x.grad.clone()] + [p.grad.clone() for p in params.values()]
+
+    refreshed = build(state)
+    before = run(refreshed)
+    eng = refreshed.model._engine
+    assert eng.training
+    with torch.no_grad():                      # in place: the version counters move, the next call refreshes the engine
+        for k, p in refreshed.model._params().items():
+            p.copy_(torch.from_numpy(stepped[k]).to(dev))
+    after = run(refreshed)
+    assert refreshed.model._engine is eng, "the engine was rebuilt instead of refreshed"
+    fresh = copy.deepcopy(refreshed)           # (the copy holds the parameters, not the engine: it builds its own)
+    assert fresh.model._engine is None
+    want = run(fresh)
+    assert fresh.model._engine is not eng
+    names = ["out B=1", "out B=3", "out B=256", "d x"] + list(fresh.model._params())
+    assert list(fresh.model._params()) == list(refreshed.model._params())
+    for name, a, b in zip(names, after, want):
+        assert torch.equal(a, b), f"{name}: refreshed and fresh engines differ by max|diff| = {float((a - b).abs().max()):.3e}"
+    # ... and the step was one the outputs can see: had the refresh done nothing, `after` would be `before`
+    assert all(not torch.equal(a, b) for a, b in zip(before[:4], after[:4]))
