@@ -150,6 +150,8 @@ ABI = {
     "dad_debug_forward_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(C.c_int32)]),
     "dad_debug_project_plan": (C.c_int, [C.c_int32] * 5 + [C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
+    "dad_debug_seam_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "dad_debug_seam_reason": (C.c_char_p, [C.c_int32]),
     "dad_debug_kernel_registered": (C.c_int, [C.c_int32] * 4),
     "dad_debug_small_kernel_exists": (C.c_int, [C.c_int32] * 8),
     "dad_optim_create": (C.c_int, [C.POINTER(C.c_void_p)]),
@@ -229,6 +231,8 @@ FP_FLAGS = ("x3", "bdir", "ragged", "res", "padded", "windowed")      # bits 0..
 # DAD_PP_* of include/dad.h: the fields and forms of dad_debug_project_plan
 PP_FIELDS = ("form", "rows_per_block", "gx", "gy", "lds_bytes", "refused")
 PP_FORMS = ("row1", "row4", "gemm")       # project_kernel<1,16>, project_kernel<4,16>, project_gemm_kernel
+# DAD_SEAM_* of include/dad.h: the fields of dad_debug_seam_plan
+SEAM_FIELDS = ("taken", "reason", "grid", "threads", "lds_bytes", "tile", "units")
 
 
 def registered_kernels():
@@ -829,6 +833,19 @@ class HipEngine:
             _check(self.lib, self.lib.dad_debug_read_table(self._h, TABLES[which], int(t),
                                                            out.data_ptr(), out.numel(), C.byref(width)))
         return out[:width.value].clone()
+
+    def seam_plan(self, batch: int, *, projection: bool = False) -> dict:
+        """Whether dad_sample_loop at `batch` (``projection``: with a projection argument) runs the seam between two
+        denoise steps as one launch (csrc/conv_seam.hpp) under the current debug options (dad_debug_seam_plan: the
+        statement the loop itself reads; host logic only).  Returns ``taken``, ``reason`` (the name of the first
+        condition that refuses it, "taken" otherwise), ``grid``, ``threads``, ``lds_bytes``, ``tile`` (the first conv's
+        tile, whose summation order the launch keeps) and ``units`` (8-channel units multiplied)."""
+        out = (C.c_int32 * len(SEAM_FIELDS))()
+        _check(self.lib, self.lib.dad_debug_seam_plan(self._h, int(batch), int(bool(projection)), out))
+        q = dict(zip(SEAM_FIELDS, out))
+        q["taken"] = bool(q["taken"])
+        q["reason"] = self.lib.dad_debug_seam_reason(q["reason"]).decode()
+        return q
 
     def small_batch_plan(self, batch: int):
         """(conv launches through the consumer-combine kernels, how many of them are the

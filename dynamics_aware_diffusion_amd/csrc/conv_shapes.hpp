@@ -97,6 +97,16 @@ DAD_HD inline size_t final_lds_floats(int td, int dim, int gy) {
     return (size_t)final_rows_local(td, gy) * dim + ((td + 3) & ~3) + (size_t)FINAL_COLS * (dim + 4);
 }
 
+// conv_seam.hpp: a block owns 32 rows (32 / H whole samples) and all `dim` output channels, 4 * dim threads.  Its X
+// stage holds one 16-channel granule per row (SEAM_KP floats: 16-byte aligned, an odd number of 16-byte slots).
+constexpr int SEAM_KP = 20;
+DAD_HD constexpr int seam_threads(int dim) { return 4 * dim; }
+DAD_HD inline int seam_xf(int H) { return (32 / H) * (H + 4) * SEAM_KP + kXSwzPad; }
+// [32][dim + 4] activation / exchange tile | [td][dim] final_conv[1] | bias | X stage | [32][dim + 4] the ride's tile
+DAD_HD inline size_t seam_lds_floats(int td, int dim, int H) {
+    return (size_t)2 * 32 * (dim + 4) + (size_t)td * dim + ((td + 3) & ~3) + (size_t)seam_xf(H);
+}
+
 // conv_gn_pass.hpp: one block of GNP_THREADS threads holds a (sample, group) pair in NPT float4 per thread,
 // NPT a power of two up to kGnPassMaxNpt: pairs of up to GNP_THREADS * 4 * kGnPassMaxNpt elements (cpg x L)
 constexpr int GNP_THREADS = 256;

@@ -25,6 +25,7 @@
 #include "conv_halo8.hpp"
 #include "conv_gn_pass.hpp"
 #include "pointwise.hpp"
+#include "conv_seam.hpp"
 #include "conv_cc.hpp"
 #include "conv_ccw.hpp"
 #include "train_bwd.hpp"
@@ -276,6 +277,22 @@ const FamilyList& halo8_kernels() {
 }
 const void* halo8_kernel(int cfg, bool res) { return find_kernel(halo8_kernels(), cfg, res, 0); }
 
+// conv_seam.hpp instantiations by (dim, the first conv's tile is 0): plan_seam takes them for tiles 0 and 1 (tile 1 needs
+// 64 output channels)
+const FamilyList& seam_kernels() {
+    static const FamilyList list = [] {
+        FamilyList v;
+        v.push_back({{32, 1}, (const void*)dad::conv_seam_f32<32, true>});
+        v.push_back({{64, 1}, (const void*)dad::conv_seam_f32<64, true>});
+        v.push_back({{64, 0}, (const void*)dad::conv_seam_f32<64, false>});
+        v.push_back({{128, 1}, (const void*)dad::conv_seam_f32<128, true>});
+        v.push_back({{128, 0}, (const void*)dad::conv_seam_f32<128, false>});
+        return v;
+    }();
+    return list;
+}
+const void* seam_kernel(int dim, bool tile0) { return find_kernel(seam_kernels(), dim, tile0, 0); }
+
 // conv_wgrad instantiations by (taps of kWgradTaps, block tile, windowed: layers longer than a chunk stages):
 // tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32 (eight); tile 3 = 32 x 32 with the general
 // staging path (operands that are not whole aligned float4 rows)
@@ -313,7 +330,7 @@ int configure_kernels() {
     std::vector<const void*> fns = {(const void*)dad::final_posterior_kernel, (const void*)dad::final_cc_kernel,
                                     (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>};
     for (const auto& kv : kernel_table()) fns.push_back((const void*)kv.second);
-    for (const FamilyList* list : {&cc_kernels(), &ccw_kernels(), &wgrad_kernels(), &halo8_kernels()})
+    for (const FamilyList* list : {&cc_kernels(), &ccw_kernels(), &wgrad_kernels(), &halo8_kernels(), &seam_kernels()})
         for (const FamilyKernel& k : *list) fns.push_back(k.fn);
     for (const void* fn : fns)
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
@@ -336,21 +353,14 @@ int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, 
 // (training: every tensor kept, plus the pre-activation / statistics buffers of the GroupNorm'd convs).
 // `temb_rows`: (B, temb_width) time projections of the training forward (indexed through trow), instead of the
 // per-timestep table.
-int run_conv(dad_model* m, const FwdPlan& f, const FwdLaunch& l, const float* xext, float* ws, int t, hipStream_t st,
-             const int32_t* trow, const float* temb_rows) {
+ConvIO conv_io(dad_model* m, const FwdPlan& f, const FwdLaunch& l, const float* xext, float* ws, int t,
+               const int32_t* trow, const float* temb_rows) {
     const Plan& plan = f.train ? m->tplan : m->plan;
     const ConvOp& op = plan.convs[l.conv];
     const int batch = f.batch;
     auto buf = [&](int id) -> float* {
         return id >= 0 ? ws + plan.bufs[id].offset * (long)batch : nullptr;
     };
-    if (op.cat0 >= 0) {     // rows of [cat0 | cat1] side by side into the residual buffer
-        const long rows = (long)batch * op.Lout;
-        const long n4 = rows * ((op.cat_c0 + op.cat_c1) / 4);
-        hipLaunchKernelGGL(dad::concat_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                           buf(op.res), buf(op.cat0), buf(op.cat1), rows, op.cat_c0, op.cat_c1);
-        HIP_TRY(hipGetLastError());
-    }
     ConvIO io;
     io.src0 = op.src0 == -2 ? xext : buf(op.src0);
     io.src1 = buf(op.src1);
@@ -366,7 +376,22 @@ int run_conv(dad_model* m, const FwdPlan& f, const FwdLaunch& l, const float* xe
     io.rdst = buf(op.rdst);
     io.pre = buf(op.pre); io.stats = buf(op.stats);
     io.slab = ws + plan.floats_per_sample * (long)batch;     // scratch behind the activations
-    return launch_conv(m, op, l.g, batch, io, st);
+    return io;
+}
+int run_conv(dad_model* m, const FwdPlan& f, const FwdLaunch& l, const float* xext, float* ws, int t, hipStream_t st,
+             const int32_t* trow, const float* temb_rows) {
+    const Plan& plan = f.train ? m->tplan : m->plan;
+    const ConvOp& op = plan.convs[l.conv];
+    const int batch = f.batch;
+    if (op.cat0 >= 0) {     // rows of [cat0 | cat1] side by side into the residual buffer
+        auto buf = [&](int id) -> float* { return ws + plan.bufs[id].offset * (long)batch; };
+        const long rows = (long)batch * op.Lout;
+        const long n4 = rows * ((op.cat_c0 + op.cat_c1) / 4);
+        hipLaunchKernelGGL(dad::concat_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
+                           buf(op.res), buf(op.cat0), buf(op.cat1), rows, op.cat_c0, op.cat_c1);
+        HIP_TRY(hipGetLastError());
+    }
+    return launch_conv(m, op, l.g, batch, conv_io(m, f, l, xext, ws, t, trow, temb_rows), st);
 }
 
 // GroupNorm -> Mish -> + time embedding -> + residual of a windowed layer (conv_gn_pass.hpp), after its conv:
@@ -394,7 +419,7 @@ int launch_gn_pass(dad_model* m, const ConvOp& op, int npt, int batch, const Con
 }
 
 // `g`: the launch as plan_launch accepted it (plan_forward, train_scratch); nothing is decided here
-int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, const ConvIO& io, hipStream_t st) {
+ConvParams conv_params(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, const ConvIO& io) {
     // windowed tiles of a GroupNorm'd layer: the conv stores conv + bias (into the pre-activation buffer when
     // the training forward keeps one), the pass over whole (sample, group) pairs finishes the block
     const bool gn_pass = g.gn_npt > 0;
@@ -430,6 +455,11 @@ int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, 
     p.wtaps = op.wtaps();
     p.rbias = g.fused ? op.d_rbias : nullptr;
     p.rdst = g.fused ? io.rdst : nullptr;
+    return p;
+}
+int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, const ConvIO& io, hipStream_t st) {
+    const bool gn_pass = g.gn_npt > 0;
+    ConvParams p = conv_params(m, op, g, batch, io);
     if (g.split.kslices > 1 && io.slab == nullptr)
         return fail(DAD_E_WORKSPACE, "%s: split-K launch without scratch", op.name.c_str());
     static const bool trace = getenv("DAD_TRACE_TILES") != nullptr;     // tuning aid
@@ -567,9 +597,61 @@ int run_conv_cc(dad_model* m, const CcPlan& cc, int i, const float* xext, float*
     return DAD_OK;
 }
 
-// One denoiser evaluation up to final_conv[0]: the launches of `f`, nothing else
+// final_conv[1] and the posterior update of step t on the trajectories x (dad_step_args `a`), as kernel parameters
+void posterior_params(dad_model* m, const FwdPlan& f, float* x, int t, const dad_step_args* a, int x_out_disabled,
+                      bool seed_from_device, float* ws, dad::FinalParams& p) {
+    const dad_cfg& c = m->cfg;
+    const Plan& plan = f.train ? m->tplan : m->plan;
+    p.act = ws + plan.bufs[plan.final_act].offset * (long)f.batch;
+    p.w = m->d_final_w; p.bias = m->d_final_b;
+    p.dim = c.dim; p.td = c.transition_dim; p.B = f.batch; p.H = traj_horizon(*m); p.Hact = c.horizon;
+    p.predict_epsilon = c.predict_epsilon; p.clip_denoised = c.clip_denoised;
+    p.x = x;
+    p.noise = a->noise; p.cond0 = a->cond0; p.cond_per_row = a->cond_per_row;
+    p.guide = (a->guide_grad && a->guide_weight > 0.0f) ? a->guide_grad : nullptr;
+    p.mean_out = a->mean_out; p.eps_out = a->eps_out;
+    p.x_out_disabled = x_out_disabled;
+    const float lv = m->sched[4][t];
+    p.c_recip = m->sched[0][t]; p.c_recipm1 = m->sched[1][t];
+    p.coef1 = m->sched[2][t]; p.coef2 = m->sched[3][t];
+    p.sigma = t == 0 ? 0.0f : expf(0.5f * lv);
+    p.guide_scale = a->guide_weight * expf(lv);
+    p.seed = a->seed;
+    p.elem_offset = a->row_offset * (uint64_t)traj_horizon(*m) * (uint64_t)c.transition_dim;
+    p.draw = a->draw;
+    p.seed_dev = seed_from_device ? (const unsigned long long*)m->d_rng : nullptr;
+}
+
+// The seam of dad_sample_loop (conv_seam.hpp, plan_seam): the posterior update of step `t` and, on the new x, the
+// first launch of the evaluation at t - 1.
+struct SeamCall {
+    const SeamPlan* plan;
+    float* x;
+    int t;                       // the step whose posterior update the launch carries
+    const dad_step_args* a;      //   and its arguments
+    bool seed_from_device;
+};
+int launch_seam(dad_model* m, const FwdPlan& f, const SeamCall& sc, int t_conv, float* ws, hipStream_t st) {
+    const FwdLaunch& l = f.launches[0];
+    const ConvOp& op = m->plan.convs[l.conv];
+    dad::SeamParams q{};
+    posterior_params(m, f, sc.x, sc.t, sc.a, 0, sc.seed_from_device, ws, q.f);
+    q.c = conv_params(m, op, l.g, f.batch, conv_io(m, f, l, sc.x, ws, t_conv, nullptr, nullptr));
+    q.c.xswz = sc.plan->xswz;
+    q.units = sc.plan->units;
+    q.hshift = ilog2(m->cfg.horizon);
+    const void* fn = seam_kernel(m->cfg.dim, sc.plan->tile0);
+    if (fn == nullptr || q.c.rdst == nullptr || q.c.rbias == nullptr || q.c.gamma == nullptr)
+        return fail(DAD_E_INVALID, "no seam kernel for dim %d on tile %d", m->cfg.dim, sc.plan->cfg);
+    void* args[] = {&q};
+    HIP_TRY(hipLaunchKernel(fn, dim3(sc.plan->grid), dim3(sc.plan->threads), args, sc.plan->lds_bytes, st));
+    return DAD_OK;
+}
+
+// One denoiser evaluation up to final_conv[0]: the launches of `f`, nothing else.  `seam`: the first of them goes out
+// as the seam launch, which also carries the previous step's posterior update (counted as that first launch)
 int run_unet(dad_model* m, const FwdPlan& f, const float* x, int t, float* ws, hipStream_t st,
-             const int32_t* trow = nullptr, const float* temb_rows = nullptr) {
+             const int32_t* trow = nullptr, const float* temb_rows = nullptr, const SeamCall* seam = nullptr) {
     // Profiling brackets the whole run of conv-GEMM launches of one denoiser evaluation with
     // ONE pair of HIP events on the launch stream (events between individual launches would
     // break the back-to-back dispatch they are meant to time).
@@ -592,7 +674,8 @@ int run_unet(dad_model* m, const FwdPlan& f, const float* x, int t, float* ws, h
         if (rc != DAD_OK) return rc;
     }
     for (const FwdLaunch& l : f.launches) {
-        const int rc = run_conv(m, f, l, x, ws, t, st, trow, temb_rows);
+        const int rc = (seam != nullptr && &l == &f.launches[0]) ? launch_seam(m, f, *seam, t, ws, st)
+                                                                 : run_conv(m, f, l, x, ws, t, st, trow, temb_rows);
         if (rc != DAD_OK) return rc;
     }
     if (m->profile) {                 // (a riding 1x1 residual conv counts its flops, not a launch)
@@ -620,20 +703,7 @@ int run_final(dad_model* m, const FwdPlan& f, float* x, const float* x_ro, int t
         p.eps_out = eps_only;
         p.x_out_disabled = 1;
     } else {
-        p.x = x;
-        p.noise = a->noise; p.cond0 = a->cond0; p.cond_per_row = a->cond_per_row;
-        p.guide = (a->guide_grad && a->guide_weight > 0.0f) ? a->guide_grad : nullptr;
-        p.mean_out = a->mean_out; p.eps_out = a->eps_out;
-        p.x_out_disabled = x_out_disabled;
-        const float lv = m->sched[4][t];
-        p.c_recip = m->sched[0][t]; p.c_recipm1 = m->sched[1][t];
-        p.coef1 = m->sched[2][t]; p.coef2 = m->sched[3][t];
-        p.sigma = t == 0 ? 0.0f : expf(0.5f * lv);
-        p.guide_scale = a->guide_weight * expf(lv);
-        p.seed = a->seed;
-        p.elem_offset = a->row_offset * (uint64_t)traj_horizon(*m) * (uint64_t)c.transition_dim;
-        p.draw = a->draw;
-        p.seed_dev = seed_from_device ? (const unsigned long long*)m->d_rng : nullptr;
+        posterior_params(m, f, x, t, a, x_out_disabled, seed_from_device, ws, p);
     }
     const dim3 grid(f.final_gx, f.final_gy);
     if (f.cc.ok) {
@@ -987,15 +1057,24 @@ int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
     const long step_elems = (long)batch * traj_horizon(*m) * m->cfg.transition_dim;
 
     const bool seed_dev = use_graph && !m->profile && noise_stack == nullptr;
+    // The seam between two steps as one launch (plan_seam): step 0 runs the whole evaluation, every later one starts
+    // with the seam launch — the previous step's posterior update and this evaluation's first conv — and the last
+    // step ends with the posterior launch.
+    const SeamPlan seam = plan_seam(*m, f, proj != nullptr);
+    const bool seamed = seam.taken() && n_steps > 1;
     auto enqueue_all = [&](hipStream_t st) -> int {
+        dad_step_args prev{};
         for (int j = 0; j < n_steps; ++j) {
             const int t = n_steps - 1 - j;
             dad_step_args a{};
             a.noise = noise_stack ? noise_stack + (long)j * step_elems : nullptr;
             a.seed = seed; a.row_offset = row_offset; a.draw = (uint64_t)(j + 1);
             a.cond0 = cond0; a.cond_per_row = cond_per_row;
-            int r = run_unet(m, f, x, t, (float*)workspace, st);
+            const SeamCall sc{&seam, x, t + 1, &prev, seed_dev};
+            int r = run_unet(m, f, x, t, (float*)workspace, st, nullptr, nullptr, seamed && j > 0 ? &sc : nullptr);
             if (r != DAD_OK) return r;
+            prev = a;
+            if (seamed && j + 1 < n_steps) continue;
             if ((r = run_final(m, f, x, nullptr, t, &a, 0, nullptr, (float*)workspace, st, seed_dev)) != DAD_OK) return r;
             if (proj && (r = run_project(proj, proj_alphas_host[t], x, batch, traj_horizon(*m), st)) != DAD_OK)
                 return r;
@@ -1025,7 +1104,7 @@ int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
     key.n_steps = n_steps; key.batch = batch; key.cond_per_row = cond_per_row;
     key.force_tile = m->force_tile;
     key.flags = (m->split_enabled ? 1 : 0) | (m->fuse_residual ? 2 : 0) | (m->xswz_enabled ? 4 : 0) |
-                (m->xcd_order ? 8 : 0) | (f.cc.ok ? 16 : 0) | (m->split_target << 8);
+                (m->xcd_order ? 8 : 0) | (f.cc.ok ? 16 : 0) | (m->step_seam ? 32 : 0) | (m->split_target << 8);
     key.row_offset = row_offset;
     if (proj) {
         uint64_t hsh = 1469598103934665603ull;            // FNV-1a over the per-step alphas
@@ -1687,6 +1766,7 @@ int dad_debug_set_option(dad_model* m, const char* name, int32_t value) {
     else if (key == "ccw_prefer16") m->ccw_prefer16 = value != 0;
     else if (key == "wgrad_blocks") m->wgrad_blocks = std::max(1, (int)value);
     else if (key == "halo8") m->halo8_enabled = value != 0;
+    else if (key == "step_seam") m->step_seam = value != 0;
     else return fail(DAD_E_INVALID, "unknown option '%s'", name);
     // every option changes which launches a captured loop holds, and not all of them are part of the
     // graph key: drop the cache (a replay may still be in flight: wait for the device first)
@@ -1813,6 +1893,24 @@ int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t a
     out[DAD_PP_REFUSED] = q.refused;
     return DAD_OK;
 }
+
+int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out) {
+    if (!m || !out || batch <= 0) return fail(DAD_E_INVALID, "bad argument");
+    FwdPlan f;
+    const int rc = plan_forward(*m, false, batch, true, f);      // (a batch the loop refuses is refused here too)
+    if (rc != DAD_OK) return rc;
+    const SeamPlan s = plan_seam(*m, f, projection != 0);
+    out[DAD_SEAM_TAKEN] = s.taken();
+    out[DAD_SEAM_REASON] = s.why;
+    out[DAD_SEAM_GRID] = s.taken() ? (int32_t)s.grid : 0;
+    out[DAD_SEAM_THREADS] = s.taken() ? s.threads : 0;
+    out[DAD_SEAM_LDS_BYTES] = s.taken() ? (int32_t)s.lds_bytes : 0;
+    out[DAD_SEAM_TILE] = s.taken() ? s.cfg : -1;
+    out[DAD_SEAM_UNITS] = s.taken() ? s.units : 0;
+    return DAD_OK;
+}
+
+const char* dad_debug_seam_reason(int32_t reason) { return seam_reason(reason); }
 
 int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32_t flags) {
     if (taps < 1 || taps > kRegMaxTaps || stride < 1 || stride > 2 || flags < 0 || flags >= (1 << kRegFlags)) return 0;

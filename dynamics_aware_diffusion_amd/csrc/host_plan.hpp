@@ -222,6 +222,7 @@ struct HostModel {
     mutable std::map<std::array<int, 5>, uint64_t> xswz_cache; // find_xswz memo: the cache of a pure function, filled by const planning
     bool halo8_enabled = true;                                 // 8-position 5-tap layers at full-chip batches take conv_halo8.hpp
     mutable std::map<std::array<int, 3>, uint64_t> xswz8_cache; // find_xswz_pairs memo
+    bool step_seam = true;                                     // dad_sample_loop: posterior + next first conv as one launch (plan_seam)
     // ---- backward pass (dad_model_set_training): data-gradient launches + the layout of the gradients
     bool training = false;
     struct BwdConv {
@@ -1557,6 +1558,105 @@ inline size_t workspace_bytes(const HostModel& m, int batch) {
     FwdPlan f;
     plan_forward(m, false, batch, true, f);
     return f.bytes;
+}
+
+// ------------------------------------------------------------------ the seam between two steps of dad_sample_loop
+// conv_seam.hpp: final_conv[1] + the posterior update of step t and the first conv of the evaluation at t - 1 (with
+// its riding 1x1 residual conv) as one launch, in place of final_posterior_kernel and the evaluation's first listed
+// launch.  Decided once per dad_sample_loop call, from the call's FwdPlan and arguments; this is the one statement of
+// the rule (dad_debug_seam_plan reports it).  Everything it refuses runs the launches of the FwdPlan as they are.
+// The first condition that fails, in this order, is the reason:
+enum SeamWhy {
+    SEAM_TAKEN = 0,
+    SEAM_OPTION,          // dad_debug_set_option("step_seam", 0)
+    SEAM_SMALL_BATCH,     // the evaluation takes the small-batch kernels (conv_cc.hpp), not the batch kernels
+    SEAM_PRECISION,       // split-f16 arithmetic
+    SEAM_FORCED_TILE,     // dad_debug_set_tile pins the conv-GEMM kernels (split-K switched off included)
+    SEAM_PROJECTION,      // the projection sits between the posterior and the next evaluation
+    SEAM_PADDED,          // zero-padded horizon or GroupNorm groups
+    SEAM_HORIZON,         // a 32-row tile holds whole samples: 8, 16 or 32 positions
+    SEAM_TRANSITION_DIM,  // one 16-channel granule
+    SEAM_DIM,             // instantiations: 32, 64, 128
+    SEAM_FIRST_CONV,      // the first launch is not the 5-tap transition_dim -> dim Conv1dBlock of one K chunk
+    SEAM_NO_RIDE,         // the 1x1 residual conv does not ride in it (fused_at)
+    SEAM_TILE,            // its tile is neither 0 nor 1: the launch keeps the tile's summation and reduction order,
+                          //   and has them for these two (tile 2, from 512 N tiles on, owns eight float4 per thread)
+    SEAM_LDS,
+    SEAM_BUFFERS,         // final_act against the buffers the conv and the ride write (seam_buffers_ok)
+    SEAM_WHYS
+};
+inline const char* seam_reason(int why) {
+    static const char* const names[SEAM_WHYS] = {"taken", "option off", "small-batch kernels", "split-f16 arithmetic", "forced tile",
+                                                 "projection", "zero-padded net", "horizon", "transition_dim", "dim", "first conv",
+                                                 "no riding residual conv", "tile", "LDS", "buffers"};
+    return why >= 0 && why < SEAM_WHYS ? names[why] : "?";
+}
+struct SeamPlan {
+    int why = SEAM_OPTION;
+    bool tile0 = false;      // the first conv's tile is 0 (else 1): conv_seam_f32<dim, tile0>
+    int cfg = -1;
+    int units = 0;           // 8-channel units with real channels
+    unsigned grid = 0;
+    int threads = 0;
+    size_t lds_bytes = 0;
+    uint64_t xswz = 0;       // slot shifts of its X stage
+    bool taken() const { return why == SEAM_TAKEN; }
+};
+// The launch reads final_act and writes the first conv's dst and rdst.  The activation allocator reuses buffer ids:
+// final_conv[0] is handed the first free level-0 buffer, which on every net so far is the first conv's own.  Allowed:
+// three buffers whose floats do not overlap — or final_act being the very buffer (same id, so same offset) the conv
+// or the ride writes: both sides are then [B * H][dim] row-major, and a workgroup reads its 32 rows in full before it
+// writes those 32 rows and no others (conv_seam.hpp).  Any other overlap is refused.
+inline bool seam_buffers_ok(const Plan& plan, const ConvOp& op) {
+    const int n = (int)plan.bufs.size();
+    const int fa = plan.final_act;
+    if (fa < 0 || fa >= n || op.dst < 0 || op.dst >= n || op.rdst < 0 || op.rdst >= n || op.dst == op.rdst) return false;
+    const long rows = (long)op.Lout * op.M;         // floats per sample the launch reads / writes of each
+    auto apart = [&](int a, int b) {
+        const long a0 = plan.bufs[a].offset, b0 = plan.bufs[b].offset;
+        return a0 + rows <= b0 || b0 + rows <= a0;
+    };
+    for (int id : {fa, op.dst, op.rdst})
+        if (plan.bufs[id].per_sample < rows) return false;
+    if (!apart(op.dst, op.rdst)) return false;
+    for (int id : {op.dst, op.rdst})
+        if (id != fa && !apart(fa, id)) return false;
+    return true;
+}
+inline SeamPlan plan_seam(const HostModel& m, const FwdPlan& f, bool projection) {
+    SeamPlan s;
+    const dad_cfg& c = m.cfg;
+    const int H = c.horizon, td = c.transition_dim, dim = c.dim;
+    auto no = [&](int why) { s.why = why; return s; };
+    if (!m.step_seam) return no(SEAM_OPTION);
+    if (f.train || f.cc.ok || f.launches.empty()) return no(SEAM_SMALL_BATCH);
+    if (m.precision != DAD_PREC_FP32) return no(SEAM_PRECISION);
+    if (m.force_tile >= 0 || !m.split_enabled) return no(SEAM_FORCED_TILE);
+    if (projection) return no(SEAM_PROJECTION);
+    const FwdLaunch& l = f.launches[0];
+    const ConvOp& op = m.plan.convs[l.conv];
+    if (traj_horizon(m) != H || op.net_padded || op.padded()) return no(SEAM_PADDED);
+    if (H != 8 && H != 16 && H != 32) return no(SEAM_HORIZON);
+    if (td > 16) return no(SEAM_TRANSITION_DIM);
+    if (dim != 32 && dim != 64 && dim != 128) return no(SEAM_DIM);
+    const LaunchGeom& g = l.g;
+    if (l.conv != 0 || !l.ok || op.kind != CONV_K5 || op.taps != 5 || op.stride != 1 || op.src0 != -2 || op.src1 >= 0 || op.cin0 != td ||
+        op.cin1 != 0 || op.cout != dim || op.M != dim || op.Lin != H || op.Lout != H || op.norm.empty() || op.res != -1 || op.cat0 >= 0 ||
+        op.x3 || op.bdir || op.kc != 16 || op.cin_pad < 16 || g.halo8 || g.padded || g.windowed || g.split.kslices != 1)
+        return no(SEAM_FIRST_CONV);
+    if (!g.fused || op.rdst < 0) return no(SEAM_NO_RIDE);
+    if ((g.cfg != 0 && g.cfg != 1) || g.kc != 32) return no(SEAM_TILE);
+    s.lds_bytes = dad::seam_lds_floats(td, dim, H) * sizeof(float);
+    if (s.lds_bytes > dad::kLdsBytes) return no(SEAM_LDS);
+    if (!seam_buffers_ok(m.plan, op)) return no(SEAM_BUFFERS);
+    s.cfg = g.cfg;
+    s.tile0 = g.cfg == 0;
+    s.units = td > 8 ? 2 : 1;
+    s.grid = (unsigned)(((long)f.batch * H + 31) / 32);
+    s.threads = dad::seam_threads(dim);
+    s.xswz = m.xswz_enabled ? find_xswz(m, H, 1, 2, dad::SEAM_KP / 4, 32) : 0;
+    s.why = SEAM_TAKEN;
+    return s;
 }
 
 // ------------------------------------------------------------------ projection: which kernel, on which grid

@@ -338,7 +338,9 @@ int dad_profile_read(dad_model* m, double* conv_ms, int64_t* conv_launches, doub
  * "ccw_min_blocks" (blocks a wide layer keeps when its K slices are fattened), "ccw_prefer16" (two
  * 16-row tiles instead of a 32-row tile whose K slice LDS would halve), "wgrad_blocks" (blocks a
  * weight-gradient launch of the backward pass aims for: tiles x batch splits), "halo8" (5-tap convs of
- * 8-position layers at full-chip batches under the heuristic take csrc/conv_halo8.hpp; 0 = the conv-GEMM kernels).
+ * 8-position layers at full-chip batches under the heuristic take csrc/conv_halo8.hpp; 0 = the conv-GEMM kernels),
+ * "step_seam" (dad_sample_loop runs the posterior update of a step and the first conv of the next evaluation as one
+ * launch, csrc/conv_seam.hpp, where dad_debug_seam_plan says so; 0 = the two launches; same bits either way).
  * Results do not depend on these choices beyond fp32 summation order. */
 int dad_debug_set_tile(dad_model* m, int32_t cfg);
 int dad_debug_set_option(dad_model* m, const char* name, int32_t value);
@@ -653,6 +655,24 @@ int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* o
 #define DAD_PP_GEMM 2
 int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
                            size_t scratch_bytes, int32_t violation, int32_t* out);
+/* Whether dad_sample_loop at `batch` (projection != 0: called with a projection argument) takes the seam between two
+ * denoise steps as one launch (csrc/conv_seam.hpp; the rule: plan_seam in csrc/host_plan.hpp), under the model's current
+ * options.  Host logic only, no device call; the model needs no weights.  out[DAD_SEAM_INTS]:
+ *   [DAD_SEAM_TAKEN]      1 / 0
+ *   [DAD_SEAM_REASON]     0 = taken, else the first condition that refuses it; dad_debug_seam_reason names it
+ *   [DAD_SEAM_GRID] [DAD_SEAM_THREADS] [DAD_SEAM_LDS_BYTES]   the launch (0 when refused)
+ *   [DAD_SEAM_TILE]       the first conv's tile (0 or 1), whose summation order the launch keeps; -1 when refused
+ *   [DAD_SEAM_UNITS]      8-channel units it multiplies (1: transition_dim <= 8, 2) */
+#define DAD_SEAM_TAKEN 0
+#define DAD_SEAM_REASON 1
+#define DAD_SEAM_GRID 2
+#define DAD_SEAM_THREADS 3
+#define DAD_SEAM_LDS_BYTES 4
+#define DAD_SEAM_TILE 5
+#define DAD_SEAM_UNITS 6
+#define DAD_SEAM_INTS 7
+int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out);
+const char* dad_debug_seam_reason(int32_t reason);
 /* 1 where the conv-GEMM instantiation (tile cfg, taps, stride, flag word as above) exists: the planner's one statement of
  * it (kernel_registered_f), whose domain is cfg 0..9, taps 1..7, stride 1..2, flags 0..63.  No device call. */
 int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32_t flags);
