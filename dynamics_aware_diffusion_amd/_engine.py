@@ -149,11 +149,14 @@ ABI = {
                                            C.POINTER(C.c_int32)]),
     "dad_debug_forward_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(C.c_int32)]),
+    "dad_debug_halo8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                       C.POINTER(C.c_int32)]),
     "dad_debug_project_plan": (C.c_int, [C.c_int32] * 5 + [C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
     "dad_debug_seam_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "dad_debug_seam_reason": (C.c_char_p, [C.c_int32]),
     "dad_debug_kernel_registered": (C.c_int, [C.c_int32] * 4),
     "dad_debug_small_kernel_exists": (C.c_int, [C.c_int32] * 8),
+    "dad_debug_fullchip_kernel_exists": (C.c_int, [C.c_int32] * 3),
     "dad_optim_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "dad_optim_destroy": (None, [C.c_void_p]),
     "dad_optim_step": (C.c_int, [C.c_void_p, C.POINTER(DadOptimTensor), C.c_int32, C.POINTER(DadOptimArgs), C.c_void_p]),
@@ -232,7 +235,12 @@ FP_FLAGS = ("x3", "bdir", "ragged", "res", "padded", "windowed")      # bits 0..
 PP_FIELDS = ("form", "rows_per_block", "gx", "gy", "lds_bytes", "refused")
 PP_FORMS = ("row1", "row4", "gemm")       # project_kernel<1,16>, project_kernel<4,16>, project_gemm_kernel
 # DAD_SEAM_* of include/dad.h: the fields of dad_debug_seam_plan
-SEAM_FIELDS = ("taken", "reason", "grid", "threads", "lds_bytes", "tile", "units")
+SEAM_FIELDS = ("taken", "reason", "grid", "threads", "lds_bytes", "tile", "units", "spt", "last", "buffers", "dim", "tile0")
+SEAM_DETAIL_FIELDS = SEAM_FIELDS[7:]        # reported by HipEngine.seam_plan(detail=True) only
+SEAM_BUFFERS = ("apart", "dst", "rdst")   # DAD_SEAM_BUF_* of include/dad.h
+# DAD_H8_* of include/dad.h: the records of dad_debug_halo8_plan
+H8_FIELDS = ("conv", "cfg", "ride", "chunks", "src1_chunk", "res", "temb", "per_row", "gn", "wpp", "xcd_gn", "mtiles", "ntiles_n",
+             "part_tile")
 
 
 def registered_kernels():
@@ -254,6 +262,16 @@ def registered_kernels():
                         if lib.dad_debug_small_kernel_exists(taps, stride, ride, 1, 0, a, rows, 0):
                             ccw.add(("ccw", taps, stride, ride, a, rows))
     return gemm, cc, ccw
+
+
+def fullchip_kernels():
+    """Every instantiation of the two full-chip families in the library's own lists (dad_debug_fullchip_kernel_exists over
+    tiles 0..9 x ride and dims 16..512 x tile0): ({("halo8", cfg, ride)}, {("seam", dim, tile0)}); host logic only."""
+    lib = load_library()
+    halo8 = {("halo8", cfg, ride) for cfg in range(10) for ride in (0, 1) if lib.dad_debug_fullchip_kernel_exists(0, cfg, ride)}
+    seam = {("seam", dim, t0) for dim in (16, 32, 48, 64, 96, 128, 256, 512) for t0 in (0, 1)
+            if lib.dad_debug_fullchip_kernel_exists(1, dim, t0)}
+    return halo8, seam
 
 
 # DAD_BS_* of include/dad.h: the records of dad_debug_backward_steps, by kind (field 0 is the kind itself)
@@ -834,18 +852,38 @@ class HipEngine:
                                                            out.data_ptr(), out.numel(), C.byref(width)))
         return out[:width.value].clone()
 
-    def seam_plan(self, batch: int, *, projection: bool = False) -> dict:
+    def seam_plan(self, batch: int, *, projection: bool = False, detail: bool = False) -> dict:
         """Whether dad_sample_loop at `batch` (``projection``: with a projection argument) runs the seam between two
         denoise steps as one launch (csrc/conv_seam.hpp) under the current debug options (dad_debug_seam_plan: the
         statement the loop itself reads; host logic only).  Returns ``taken``, ``reason`` (the name of the first
         condition that refuses it, "taken" otherwise), ``grid``, ``threads``, ``lds_bytes``, ``tile`` (the first conv's
-        tile, whose summation order the launch keeps) and ``units`` (8-channel units multiplied)."""
+        tile, whose summation order the launch keeps) and ``units`` (8-channel units multiplied).  With ``detail`` also
+        the fields that name the path inside the kernel: ``spt`` (samples of a 32-row tile), ``last`` (samples in the
+        last tile), ``buffers`` (which allowed relation final_act has to the buffers the launch writes: "apart", "dst"
+        or "rdst"; None when refused) and ``dim`` / ``tile0``: the instantiation conv_seam_f32<dim, tile0>."""
         out = (C.c_int32 * len(SEAM_FIELDS))()
         _check(self.lib, self.lib.dad_debug_seam_plan(self._h, int(batch), int(bool(projection)), out))
         q = dict(zip(SEAM_FIELDS, out))
         q["taken"] = bool(q["taken"])
         q["reason"] = self.lib.dad_debug_seam_reason(q["reason"]).decode()
+        q["buffers"] = SEAM_BUFFERS[q["buffers"]] if q["buffers"] >= 0 else None
+        if not detail:
+            for k in SEAM_DETAIL_FIELDS:
+                del q[k]
         return q
+
+    def halo8_plan(self, batch: int, mode: int = 0) -> list:
+        """The conv_halo8_f32 launches (csrc/conv_halo8.hpp) of one evaluation at `batch` under the current debug
+        options (dad_debug_halo8_plan: host logic only; ``mode`` 0 / 1 as :meth:`forward_plan`): one dict per launch in
+        launch order with the fields of DAD_H8_* — what the kernel makes of the operands the launch hands it."""
+        need = C.c_int32()
+        _check(self.lib, self.lib.dad_debug_halo8_plan(self._h, int(batch), int(mode), None, 0, C.byref(need)))
+        buf = (C.c_int32 * need.value)()
+        _check(self.lib, self.lib.dad_debug_halo8_plan(self._h, int(batch), int(mode), buf, need.value, C.byref(need)))
+        r = list(buf)
+        k = len(H8_FIELDS)
+        assert r[1] == k and len(r) - 2 == r[0] * k
+        return [dict(zip(H8_FIELDS, r[at:at + k])) for at in range(2, len(r), k)]
 
     def small_batch_plan(self, batch: int):
         """(conv launches through the consumer-combine kernels, how many of them are the

@@ -43,6 +43,10 @@ DAD_HD inline int halo8_pos(int i, int q) { return 2 * q + (i & 1); }
 // wave (tap index 0, block 0) is the product that reads halo rows only.
 DAD_HD inline int halo8_block(int tn, int nb) { return tn ? 3 - nb : nb; }
 DAD_HD inline int halo8_tap(int tn, int t) { return tn ? 4 - t : t; }
+// Lanes that own one (sample, group) pair in that kernel's epilogue — its `lpp`: a pair is 8 positions x cpg channels
+// in float4, a thread owns (64 * BM / 4) / threads of them.  A pair of more than 64 lanes spans lpp / 64 waves, whose
+// partial sums meet through LDS.
+DAD_HD inline int halo8_lanes_per_pair(int BM, int threads, int cpg) { return (8 * (cpg / 4)) / ((64 * BM / 4) / threads); }
 
 // conv_wgrad (train_bwd.hpp)
 constexpr int WG_THREADS = 512;             // 8 waves: TM x TN wave tiles of 32 x 32 (x TAPS), the rest split K

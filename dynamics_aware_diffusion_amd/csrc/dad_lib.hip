@@ -1877,6 +1877,18 @@ int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* o
     return DAD_OK;
 }
 
+int dad_debug_halo8_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (!m || batch <= 0 || mode < 0 || mode > 1 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    FwdPlan f;
+    const int rc = plan_forward(*m, false, batch, mode == 0, f);     // (as dad_debug_forward_plan plans modes 0 / 1)
+    if (rc != DAD_OK) return rc;
+    std::vector<int32_t> r;
+    halo8_plan_encode(*m, f, mode == 1, r);
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
+}
+
 int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
                            size_t scratch_bytes, int32_t violation, int32_t* out) {
     if (!out || state_dim <= 0 || observation_dim < state_dim || action_dim <= 0 || batch <= 0 || horizon <= 0)
@@ -1907,6 +1919,11 @@ int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t
     out[DAD_SEAM_LDS_BYTES] = s.taken() ? (int32_t)s.lds_bytes : 0;
     out[DAD_SEAM_TILE] = s.taken() ? s.cfg : -1;
     out[DAD_SEAM_UNITS] = s.taken() ? s.units : 0;
+    out[DAD_SEAM_SPT] = s.taken() ? s.spt : 0;
+    out[DAD_SEAM_LAST] = s.taken() ? s.last : 0;
+    out[DAD_SEAM_BUFFERS] = s.taken() ? s.buffers : -1;
+    out[DAD_SEAM_DIM] = s.taken() ? s.dim : 0;
+    out[DAD_SEAM_TILE0] = s.taken() ? (int32_t)s.tile0 : -1;
     return DAD_OK;
 }
 
@@ -1920,6 +1937,12 @@ int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32
 int dad_debug_small_kernel_exists(int32_t taps, int32_t stride, int32_t ride, int32_t wide, int32_t big, int32_t ride_in,
                                   int32_t rows, int32_t windowed) {
     return small_kernel_exists(taps, stride, ride != 0, wide != 0, big != 0, ride_in != 0, rows, windowed != 0) ? 1 : 0;
+}
+
+int dad_debug_fullchip_kernel_exists(int32_t family, int32_t a, int32_t b) {
+    if (family == DAD_FAMILY_HALO8) return halo8_kernel(a, b != 0) != nullptr ? 1 : 0;
+    if (family == DAD_FAMILY_SEAM) return seam_kernel(a, b != 0) != nullptr ? 1 : 0;
+    return 0;
 }
 
 int dad_profile_enable(dad_model* m, int32_t on) {

@@ -1600,6 +1600,11 @@ struct SeamPlan {
     int threads = 0;
     size_t lds_bytes = 0;
     uint64_t xswz = 0;       // slot shifts of its X stage
+    // what the report adds (dad_debug_seam_plan); the launch reads none of them
+    int dim = 0;             // conv_seam_f32<dim, tile0>
+    int spt = 0;             // samples of one 32-row tile
+    int last = 0;            // samples in the last tile, 1 .. spt
+    int buffers = -1;        // seam_buffer_relation
     bool taken() const { return why == SEAM_TAKEN; }
 };
 // The launch reads final_act and writes the first conv's dst and rdst.  The activation allocator reuses buffer ids:
@@ -1622,6 +1627,11 @@ inline bool seam_buffers_ok(const Plan& plan, const ConvOp& op) {
     for (int id : {op.dst, op.rdst})
         if (id != fa && !apart(fa, id)) return false;
     return true;
+}
+// Which of the relations seam_buffers_ok allows holds (DAD_SEAM_BUF_* of include/dad.h), -1 where it allows none.
+inline int seam_buffer_relation(const Plan& plan, const ConvOp& op) {
+    if (!seam_buffers_ok(plan, op)) return -1;
+    return plan.final_act == op.dst ? DAD_SEAM_BUF_DST : plan.final_act == op.rdst ? DAD_SEAM_BUF_RDST : DAD_SEAM_BUF_APART;
 }
 inline SeamPlan plan_seam(const HostModel& m, const FwdPlan& f, bool projection) {
     SeamPlan s;
@@ -1655,6 +1665,10 @@ inline SeamPlan plan_seam(const HostModel& m, const FwdPlan& f, bool projection)
     s.grid = (unsigned)(((long)f.batch * H + 31) / 32);
     s.threads = dad::seam_threads(dim);
     s.xswz = m.xswz_enabled ? find_xswz(m, H, 1, 2, dad::SEAM_KP / 4, 32) : 0;
+    s.dim = dim;
+    s.spt = 32 / H;
+    s.last = f.batch - ((int)s.grid - 1) * s.spt;
+    s.buffers = seam_buffer_relation(m.plan, op);
     s.why = SEAM_TAKEN;
     return s;
 }
@@ -2085,6 +2099,29 @@ inline int forward_plan_report(const HostModel& m, int batch, int mode, std::vec
     const int rc = mode == 3 ? train_scratch(m, batch, ts) : plan_forward(m, mode == 2, batch, mode == 0, f);
     forward_plan_encode(m, mode, batch, &f, &ts, r);
     return rc;
+}
+// dad_debug_halo8_plan: the conv_halo8_f32 launches of `f` (plan_forward on m.plan, modes 0 / 1) with what the kernel
+// makes of the ConvParams that conv_params / conv_io of dad_lib.hip fill from the same ConvOp and LaunchGeom (layout:
+// include/dad.h, DAD_H8_*).  `rows`: the evaluation indexes its time embedding per sample (dad_unet_forward_rows).
+inline void halo8_plan_encode(const HostModel& m, const FwdPlan& f, bool rows, std::vector<int32_t>& r) {
+    r.assign(DAD_H8_HEADER, 0);
+    r[1] = DAD_H8_INTS;
+    if (f.train || f.cc.ok) return;
+    for (const FwdLaunch& l : f.launches) {
+        if (!l.g.halo8) continue;
+        const ConvOp& op = m.plan.convs[l.conv];
+        const LaunchGeom& g = l.g;
+        const TileCfg& t = kTiles[g.cfg];
+        const bool gn = !op.norm.empty() && g.gn_npt == 0;
+        const bool temb = op.temb_off >= 0;
+        // waves per pair: the kernel's own `wpp` is lpp >> 6, 0 for a pair inside one wave; the report says 1 there
+        const int lpp = gn ? dad::halo8_lanes_per_pair(t.BM, g.threads, op.cout / 8) : 0;
+        const int32_t rec[DAD_H8_INTS] = {l.conv, g.cfg, g.fused, (op.cin0 + op.cin1) / 32, op.src1 >= 0 ? op.cin0 / 32 : -1,
+                                          op.res == -2 || op.res >= 0, temb, rows && temb, gn, gn ? std::max(1, lpp >> 6) : 0,
+                                          g.xcd_gn, g.mtiles, g.ntiles_n, f.batch % (t.BN / op.Lout) != 0};
+        r.insert(r.end(), rec, rec + DAD_H8_INTS);
+        ++r[0];
+    }
 }
 
 // Bytes the parameter arena must hold: the parameter copies, the per-timestep tables, the zero row of the

@@ -631,6 +631,36 @@ int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t 
 #define DAD_FP_CC_RES_KIND 12
 #define DAD_FP_CC_INTS 13
 int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out);
+/* The conv_halo8_f32 launches (csrc/conv_halo8.hpp) of the same description, modes 0 and 1 only, with what the kernel
+ * makes of its ConvParams: read from the ConvOp / LaunchGeom the launch fills them from (csrc/host_plan.hpp,
+ * halo8_plan_encode), nothing decided.  Writes min(capacity, *needed_out) int32 values: [0] the records, [1]
+ * DAD_H8_INTS, then per launch in launch order
+ *   [DAD_H8_CONV] [DAD_H8_CFG] [DAD_H8_RIDE]   conv index, tile (0 / 1), the riding 1x1 conv: the instantiation
+ *   [DAD_H8_CHUNKS]       32-channel K chunks, (cin0 + cin1) / 32
+ *   [DAD_H8_SRC1_CHUNK]   the chunk from which the second source is read, -1 without one
+ *   [DAD_H8_RES] [DAD_H8_TEMB]   a residual operand / a time embedding is present
+ *   [DAD_H8_PER_ROW]      the time embedding is indexed per sample (mode 1, where there is one)
+ *   [DAD_H8_GN]           GroupNorm runs in the kernel
+ *   [DAD_H8_WPP]          waves one (sample, group) pair spans (0 without GroupNorm; > 1: the cross-wave sum through LDS)
+ *   [DAD_H8_XCD_GN]       0: the plain grid (y = M tile, z = N tile), else the XCD-aware tile order
+ *   [DAD_H8_MTILES] [DAD_H8_NTILES_N] [DAD_H8_PART_TILE]   as the DAD_FP_REC_* fields of those names */
+#define DAD_H8_HEADER 2
+#define DAD_H8_CONV 0
+#define DAD_H8_CFG 1
+#define DAD_H8_RIDE 2
+#define DAD_H8_CHUNKS 3
+#define DAD_H8_SRC1_CHUNK 4
+#define DAD_H8_RES 5
+#define DAD_H8_TEMB 6
+#define DAD_H8_PER_ROW 7
+#define DAD_H8_GN 8
+#define DAD_H8_WPP 9
+#define DAD_H8_XCD_GN 10
+#define DAD_H8_MTILES 11
+#define DAD_H8_NTILES_N 12
+#define DAD_H8_PART_TILE 13
+#define DAD_H8_INTS 14
+int dad_debug_halo8_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out);
 /* Which kernel one dad_project (violation == 0) or dad_projection_violation (violation != 0) call launches for
  * trajectories (batch, horizon, observation_dim + action_dim) and a dad_project_args.scratch of scratch_bytes (0: none),
  * and on which grid: the plan the two entry points launch from.  Host logic only, no device call.  out[DAD_PP_INTS]:
@@ -662,7 +692,13 @@ int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t a
  *   [DAD_SEAM_REASON]     0 = taken, else the first condition that refuses it; dad_debug_seam_reason names it
  *   [DAD_SEAM_GRID] [DAD_SEAM_THREADS] [DAD_SEAM_LDS_BYTES]   the launch (0 when refused)
  *   [DAD_SEAM_TILE]       the first conv's tile (0 or 1), whose summation order the launch keeps; -1 when refused
- *   [DAD_SEAM_UNITS]      8-channel units it multiplies (1: transition_dim <= 8, 2) */
+ *   [DAD_SEAM_UNITS]      8-channel units it multiplies (1: transition_dim <= 8, 2)
+ *   [DAD_SEAM_SPT]        samples of one 32-row tile (32 / horizon); 0 when refused
+ *   [DAD_SEAM_LAST]       samples in the last tile (1 .. DAD_SEAM_SPT); 0 when refused
+ *   [DAD_SEAM_BUFFERS]    which allowed relation of seam_buffers_ok holds: DAD_SEAM_BUF_APART (final_act overlaps neither
+ *                         buffer the launch writes), DAD_SEAM_BUF_DST (it is the conv's dst), DAD_SEAM_BUF_RDST (it is the
+ *                         ride's); -1 when refused
+ *   [DAD_SEAM_DIM] [DAD_SEAM_TILE0]   the instantiation conv_seam_f32<dim, tile0>; 0 / -1 when refused */
 #define DAD_SEAM_TAKEN 0
 #define DAD_SEAM_REASON 1
 #define DAD_SEAM_GRID 2
@@ -670,7 +706,15 @@ int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t a
 #define DAD_SEAM_LDS_BYTES 4
 #define DAD_SEAM_TILE 5
 #define DAD_SEAM_UNITS 6
-#define DAD_SEAM_INTS 7
+#define DAD_SEAM_SPT 7
+#define DAD_SEAM_LAST 8
+#define DAD_SEAM_BUFFERS 9
+#define DAD_SEAM_DIM 10
+#define DAD_SEAM_TILE0 11
+#define DAD_SEAM_INTS 12
+#define DAD_SEAM_BUF_APART 0
+#define DAD_SEAM_BUF_DST 1
+#define DAD_SEAM_BUF_RDST 2
 int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out);
 const char* dad_debug_seam_reason(int32_t reason);
 /* 1 where the conv-GEMM instantiation (tile cfg, taps, stride, flag word as above) exists: the planner's one statement of
@@ -680,6 +724,12 @@ int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32
  * windowed) with wide = ride_in = 0, conv_ccw by (taps, stride, ride, ride_in, rows) with wide = 1, big = windowed = 0. */
 int dad_debug_small_kernel_exists(int32_t taps, int32_t stride, int32_t ride, int32_t wide, int32_t big, int32_t ride_in,
                                   int32_t rows, int32_t windowed);
+/* 1 where the instantiation is in the library's list of its family (the lists the launches look their kernel up in):
+ * DAD_FAMILY_HALO8 conv_halo8_f32 by (a = tile cfg, b = riding 1x1 conv), DAD_FAMILY_SEAM conv_seam_f32 by (a = dim,
+ * b = the first conv's tile is 0).  No device call. */
+#define DAD_FAMILY_HALO8 0
+#define DAD_FAMILY_SEAM 1
+int dad_debug_fullchip_kernel_exists(int32_t family, int32_t a, int32_t b);
 
 /* ------------------------------------------------------------------------------------------------
  * The optimiser step.  Replaces what Trainer.train_step does after loss.backward() (utils/training.py:158-189):

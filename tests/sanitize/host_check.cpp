@@ -223,6 +223,62 @@ static void check_forward_report(const HostModel& m, int mode, int B, const FwdP
     }
 }
 
+// dad_debug_halo8_plan: one record per conv_halo8_f32 launch of the description, in order, every field recomputed here
+// the way the kernel derives it from its ConvParams (conv_halo8.hpp: nchunks, `second`, has_res / has_temb / has_gn,
+// lpp and wpp, the tile decode, nvalid of the last tile) — from the ConvOp and LaunchGeom those parameters are filled from.
+static long g_halo8_reports = 0, g_halo8_records = 0;
+static void check_halo8_report(const HostModel& m, int B, const FwdPlan& f, bool rows) {
+    std::vector<int32_t> r;
+    halo8_plan_encode(m, f, rows, r);
+    CHECK(r.size() >= DAD_H8_HEADER && r[1] == DAD_H8_INTS && r.size() == (size_t)DAD_H8_HEADER + (size_t)r[0] * DAD_H8_INTS, "B=%d: halo8 report of %zu ints",
+          B, r.size());
+    if (r.size() < DAD_H8_HEADER || r.size() != (size_t)DAD_H8_HEADER + (size_t)r[0] * DAD_H8_INTS) return;
+    ++g_halo8_reports;
+    int k = 0;
+    if (!f.cc.ok && !f.train)
+        for (const FwdLaunch& l : f.launches) {
+            if (!l.g.halo8) continue;
+            CHECK(k < r[0], "B=%d: more halo8 launches than records", B);
+            if (k >= r[0]) break;
+            const int32_t* q = &r[DAD_H8_HEADER + (size_t)k++ * DAD_H8_INTS];
+            const ConvOp& op = m.plan.convs[l.conv];
+            const LaunchGeom& g = l.g;
+            ++g_halo8_records;
+            CHECK(q[DAD_H8_CONV] == l.conv && q[DAD_H8_CFG] == g.cfg && halo8_kernel_exists(g.cfg) && (q[DAD_H8_RIDE] != 0) == g.fused, "%s B=%d: instantiation",
+                  op.name.c_str(), B);
+            const int cin0 = op.cin0, cin1 = op.cin1, KC = 32;
+            CHECK((cin0 + cin1) % KC == 0 && cin0 % KC == 0 && q[DAD_H8_CHUNKS] == (cin0 + cin1) / KC, "%s B=%d: %d chunks for %d + %d channels", op.name.c_str(), B,
+                  q[DAD_H8_CHUNKS], cin0, cin1);
+            int first_second = -1;                          // the first chunk the kernel's `second` is true for
+            for (int ch = 0; ch < (cin0 + cin1) / KC; ++ch)
+                if (ch * KC >= cin0 && first_second < 0) first_second = ch;
+            CHECK((op.src1 >= 0) == (cin1 > 0) && q[DAD_H8_SRC1_CHUNK] == first_second, "%s B=%d: second source from chunk %d, the kernel's %d", op.name.c_str(), B,
+                  q[DAD_H8_SRC1_CHUNK], first_second);
+            // (the operands as conv_io of dad_lib.hip hands them over: io.res is the trajectory for op.res == -2, a plan buffer for
+            // an id >= 0, else null; io.temb exists where op.temb_off >= 0, and io.trow only beside it.  The same expressions as the
+            // encoder's: this holds the slots, not the reading of conv_io — keep the two in step with it.)
+            CHECK((q[DAD_H8_RES] != 0) == (op.res == -2 || op.res >= 0) && (q[DAD_H8_TEMB] != 0) == (op.temb_off >= 0) &&
+                  (q[DAD_H8_PER_ROW] != 0) == (rows && op.temb_off >= 0), "%s B=%d: residual / time embedding", op.name.c_str(), B);
+            const bool gn = !op.norm.empty();
+            CHECK(g.gn_npt == 0 && (q[DAD_H8_GN] != 0) == gn, "%s B=%d: GroupNorm", op.name.c_str(), B);
+            const TileCfg& t = kTiles[g.cfg];
+            int wpp = 0;
+            if (gn) {
+                const int NT = 64 * (t.BM / 32) * 2 * t.SK, F4PL = (64 * t.BM / 4) / NT, cpg = op.cout / 8, cnt4 = 8 * (cpg >> 2);
+                const int lpp = cnt4 >> (F4PL == 1 ? 0 : F4PL == 2 ? 1 : F4PL == 4 ? 2 : 3);
+                CHECK(NT == g.threads && lpp >= 1 && is_pow2(lpp) && lpp * F4PL == cnt4, "%s B=%d: %d lanes per pair", op.name.c_str(), B, lpp);
+                wpp = std::max(1, lpp >> 6);
+                CHECK(wpp <= NT / 64 && (NT / 64) % wpp == 0, "%s B=%d: a pair of %d waves in a block of %d", op.name.c_str(), B, wpp, NT / 64);
+            }
+            CHECK(q[DAD_H8_WPP] == wpp, "%s B=%d: %d waves per pair, the kernel's %d", op.name.c_str(), B, q[DAD_H8_WPP], wpp);
+            CHECK(q[DAD_H8_XCD_GN] == g.xcd_gn && q[DAD_H8_MTILES] == g.mtiles && q[DAD_H8_NTILES_N] == g.ntiles_n && g.mtiles * t.BM == op.M, "%s B=%d: grid",
+                  op.name.c_str(), B);
+            const int last = B - (g.ntiles_n - 1) * 8;      // nvalid of the last N tile
+            CHECK(last >= 1 && last <= 8 && (q[DAD_H8_PART_TILE] != 0) == (last < 8), "%s B=%d: last tile holds %d samples", op.name.c_str(), B, last);
+        }
+    CHECK(k == r[0], "B=%d: %d halo8 launches, %d records", B, k, r[0]);
+}
+
 // dad_debug_backward_steps: one record per step of m.bsteps, in order, each field equal to what dad_unet_backward reads for
 // that step — the step itself, the forward conv a GroupNorm step belongs to, the geometry `ts` of train_scratch.  The
 // derived fields are recomputed here the way the kernels see them (block origins, staged widths), not the way the
@@ -532,10 +588,12 @@ static void check_arch(const Arch& a, int precision) {
                 CHECK(rc == DAD_OK || force >= 0, "B=%d: %s", B, g_err);
                 CHECK(f.bytes == ws && !f.cc.ok && !f.train && f.batch == B, "B=%d: description of another call (%zu bytes, the query says %zu)", B, f.bytes, ws);
                 check_forward_report(m, 1, B, &f, nullptr, rc);
+                if (rc == DAD_OK) check_halo8_report(m, B, f, true);
                 {   // ... and of the shared-timestep call, which may take the small-batch kernels
                     FwdPlan f0;
                     const int rc0 = plan_forward(m, false, B, true, f0);
                     check_forward_report(m, 0, B, &f0, nullptr, rc0);
+                    if (rc0 == DAD_OK) check_halo8_report(m, B, f0, false);
                 }
                 CHECK(workspace_bytes(m, B) == ws, "B=%d: the size query depends on who asks", B);
                 std::vector<int> at(P.convs.size(), -1);         // conv -> its place in the list
@@ -973,6 +1031,8 @@ int main(int argc, char** argv) {
     }
     CHECK(g_reports > 0, "no forward-plan report was compared");
     CHECK(g_step_reports > 0, "no backward-step report was compared");
+    CHECK(g_halo8_reports > 0 && g_halo8_records > 0, "no conv_halo8_f32 launch report was compared (%ld reports, %ld records)", g_halo8_reports, g_halo8_records);
+    printf("  halo8 plan: %ld reports, %ld launch records\n", g_halo8_reports, g_halo8_records);
     if (g_failures) { fprintf(stderr, "%d host-logic checks FAILED\n", g_failures); return 1; }
     printf("host logic ok (%ld forward-plan and %ld backward-step reports equal the descriptions they were read from)\n", g_reports,
            g_step_reports);

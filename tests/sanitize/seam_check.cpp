@@ -228,6 +228,23 @@ static void check_rule() {
                             CHECK(s.grid == (unsigned)(((long)B * H + 31) / 32) && s.threads == dad::seam_threads(dim), "grid %u, %d threads", s.grid, s.threads);
                             CHECK(s.lds_bytes == dad::seam_lds_floats(td, dim, H) * sizeof(float) && s.lds_bytes <= dad::kLdsBytes, "LDS %zu", s.lds_bytes);
                             CHECK(s.xswz == find_xswz(q, H, 1, 2, dad::SEAM_KP / 4, 32), "slot shifts");
+                            // what the report adds, against the description it was read from
+                            CHECK(s.dim == q.cfg.dim && s.spt * H == 32, "instantiation dim %d, %d samples per tile at H %d", s.dim, s.spt, H);
+                            CHECK(s.last >= 1 && s.last <= s.spt && ((long)s.grid - 1) * s.spt + s.last == B, "B %d: %u tiles of %d, last %d", B,
+                                  s.grid, s.spt, s.last);
+                            {
+                                const ConvOp& fop = q.plan.convs[f.launches[0].conv];
+                                const int fa = q.plan.final_act;
+                                const int want_rel = fa == fop.dst ? DAD_SEAM_BUF_DST : fa == fop.rdst ? DAD_SEAM_BUF_RDST : DAD_SEAM_BUF_APART;
+                                CHECK(s.buffers == want_rel && seam_buffers_ok(q.plan, fop), "buffer relation %d, the plan's %d", s.buffers, want_rel);
+                                if (want_rel == DAD_SEAM_BUF_APART) {
+                                    const long rows = (long)fop.Lout * fop.M, a0 = q.plan.bufs[fa].offset;
+                                    for (int id : {fop.dst, fop.rdst}) {
+                                        const long b0 = q.plan.bufs[id].offset;
+                                        CHECK(a0 + rows <= b0 || b0 + rows <= a0, "'apart' with overlapping floats");
+                                    }
+                                }
+                            }
                             // the launch it replaces is the ragged first conv with the ride, in one K chunk
                             const ConvOp& op = q.plan.convs[f.launches[0].conv];
                             CHECK(g.ragged && g.fused && g.kc == 32 && g.split.kslices == 1 && op.cin0 == td && op.wtaps() == 6 && op.kc == 16, "first conv");
@@ -272,6 +289,9 @@ static void check_rule() {
         CHECK(!ok(2, 0, 1) && !ok(1, 0, 2), "overlapping buffers");
         P.bufs[1].offset = 4096;
         CHECK(!ok(3, 0, 1), "final_act shorter than the tile rows");
+        auto rel = [&](int fin, int dst, int rdst) { P.final_act = fin; op.dst = dst; op.rdst = rdst; return seam_buffer_relation(P, op); };
+        CHECK(rel(2, 0, 1) == DAD_SEAM_BUF_APART && rel(0, 0, 1) == DAD_SEAM_BUF_DST && rel(1, 0, 1) == DAD_SEAM_BUF_RDST, "the three relations");
+        CHECK(rel(0, 0, 0) == -1 && rel(3, 0, 1) == -1 && rel(2, 0, 7) == -1, "a refused plan has no relation");
     }
 }
 

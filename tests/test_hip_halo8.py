@@ -8,8 +8,10 @@ GPU: the kernel with the "halo8" option on, and the conv-GEMM kernels with it of
 forward tests' gate (tests/test_hip_long_horizon.py: <= TOL_STEP from the fp32 oracle and no farther from float64 than
 twice the fp32 oracle, + 5e-7), at the smallest batches the planner takes the kernel at:
   d32_m124_H32        the first batch whose plan holds the family (313: 40 N tiles x 4 M tiles of tile 0 = 160 tiles, no
-                      grid split-K), 128 channels at 8 positions; 64 -> 128 carries the riding 1x1 conv
-  d32_m124_H32_part   the same + 3: a partly empty last N tile
+                      grid split-K), 128 channels at 8 positions; 64 -> 128 carries the riding 1x1 conv; the last N tile
+                      holds one sample of eight
+  d32_m124_H32_part   the same + 3: four samples in the last N tile (both are partly empty: neither 313 nor 316 is a
+                      multiple of 8; a full last tile runs in tests/test_hip_halo8_paths.py)
   d32_m14_H16_tile1   the first batch that takes it on tile 1 (889: 112 N tiles x 2 M tiles = 224 blocks), 32 -> 128 with
                       the ride in one K chunk, 128 -> 128 in four
   d32_m1_H8           horizon 8, one level: the first level is the 8-position one (32 -> 32, one K chunk, GroupNorm with

@@ -73,11 +73,15 @@ def test_report_says_taken_under_the_rule_and_names_every_refusal():
     head = _host().seam_plan(256)
     assert head == {"taken": True, "reason": "taken", "grid": 256, "threads": 512, "tile": 1, "units": 1,
                     "lds_bytes": 4 * (2 * 32 * 132 + 6 * 128 + 8 + 36 * 20 + 64)}, head
+    assert _host().seam_plan(256, detail=True) == dict(head, spt=1, last=1, buffers="dst", dim=128, tile0=0)
     for name, dim, mults, H, B, tile in NETS:
         for td in TDS:
             q = _host(td, dim, mults, H).seam_plan(B)
             assert q["taken"] and q["tile"] == tile and q["units"] == (1 if td <= 8 else 2), (name, td, q)
             assert q["grid"] == (B * H + 31) // 32 and q["threads"] == 4 * dim and q["lds_bytes"] <= 160 * 1024
+            q = _host(td, dim, mults, H).seam_plan(B, detail=True)
+            assert q["spt"] == 32 // H and (q["grid"] - 1) * q["spt"] + q["last"] == B and 1 <= q["last"] <= q["spt"]
+            assert q["dim"] == dim and q["tile0"] == (tile == 0) and q["buffers"] in ("dst", "rdst", "apart")
     # the first tile-1 batches are what NETS says
     assert _host(6, 64, (1,), 16).seam_plan(892)["tile"] == 0 and _host(6, 128, (1,), 32).seam_plan(222)["tile"] == 0
     refusals = [
@@ -100,6 +104,7 @@ def test_report_says_taken_under_the_rule_and_names_every_refusal():
             _check(eng.lib, eng.lib.dad_debug_set_option(eng._h, off.encode(), 0))
         q = eng.seam_plan(B, projection=proj)
         assert q == {"taken": False, "reason": reason, "grid": 0, "threads": 0, "lds_bytes": 0, "tile": -1, "units": 0}, (reason, q)
+        assert eng.seam_plan(B, projection=proj, detail=True) == dict(q, spt=0, last=0, buffers=None, dim=0, tile0=-1), reason
     # each of them alone decides: the same engines are taken once the condition is lifted
     assert _host(td=16).seam_plan(256)["taken"] and _host(H=16).seam_plan(256)["taken"] and _host(dim=64).seam_plan(256)["taken"]
     assert _host(cc=1).seam_plan(256)["taken"], "batch 256 takes the batch kernels whatever the option"
