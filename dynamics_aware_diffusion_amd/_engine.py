@@ -119,7 +119,6 @@ ABI = {
                                           C.POINTER(C.c_int32)]),
     "dad_debug_backward_steps": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                            C.POINTER(C.c_int32)]),
-    "dad_debug_wgrad_kernel_exists": (C.c_int, [C.c_int32] * 3),
     "dad_model_set_training": (C.c_int, [C.c_void_p, C.c_int32]),
     "dad_model_refresh_weights": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                             C.c_void_p]),
@@ -154,9 +153,7 @@ ABI = {
     "dad_debug_project_plan": (C.c_int, [C.c_int32] * 5 + [C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
     "dad_debug_seam_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "dad_debug_seam_reason": (C.c_char_p, [C.c_int32]),
-    "dad_debug_kernel_registered": (C.c_int, [C.c_int32] * 4),
-    "dad_debug_small_kernel_exists": (C.c_int, [C.c_int32] * 8),
-    "dad_debug_fullchip_kernel_exists": (C.c_int, [C.c_int32] * 3),
+    "dad_debug_kernel_list": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "dad_optim_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "dad_optim_destroy": (None, [C.c_void_p]),
     "dad_optim_step": (C.c_int, [C.c_void_p, C.POINTER(DadOptimTensor), C.c_int32, C.POINTER(DadOptimArgs), C.c_void_p]),
@@ -243,35 +240,33 @@ H8_FIELDS = ("conv", "cfg", "ride", "chunks", "src1_chunk", "res", "temb", "per_
              "part_tile")
 
 
-def registered_kernels():
-    """Every kernel key the planner says exists, in the form HipEngine.forward_plan reports them: the conv-GEMM
-    instantiations (dad_debug_kernel_registered over its whole domain) and the small-batch ones
-    (dad_debug_small_kernel_exists).  Returns (gemm keys, cc keys, ccw keys) as sets; host logic only."""
+KERNEL_FAMILIES = ("gemm", "cc", "ccw", "halo8", "seam", "wgrad")      # DAD_FAMILY_* of include/dad.h
+
+
+def kernel_list(family: str):
+    """The keys of one family of instantiated kernels in the library's own registry, the table every launch looks its
+    kernel up in (dad_debug_kernel_list), as a set of tuples; host logic only."""
     lib = load_library()
-    gemm = {("gemm", cfg, taps, stride, f) for cfg in range(10) for taps in range(1, 8) for stride in (1, 2) for f in range(64)
-            if lib.dad_debug_kernel_registered(cfg, taps, stride, f)}
-    cc, ccw = set(), set()
-    for taps in range(1, 8):
-        for stride in (1, 2):
-            for ride in (0, 1):
-                for rows in (8, 16, 32, 64):
-                    for a in (0, 1):
-                        for win in (0, 1):
-                            if lib.dad_debug_small_kernel_exists(taps, stride, ride, 0, a, 0, rows, win):
-                                cc.add(("cc", taps, stride, ride, a, rows, win))
-                        if lib.dad_debug_small_kernel_exists(taps, stride, ride, 1, 0, a, rows, 0):
-                            ccw.add(("ccw", taps, stride, ride, a, rows))
-    return gemm, cc, ccw
+    fam = KERNEL_FAMILIES.index(family)
+    need = C.c_int32()
+    _check(lib, lib.dad_debug_kernel_list(fam, None, 0, C.byref(need)))
+    out = (C.c_int32 * need.value)()
+    _check(lib, lib.dad_debug_kernel_list(fam, out, need.value, C.byref(need)))
+    n, ints = out[0], out[1]
+    return {tuple(out[2 + i * ints:2 + (i + 1) * ints]) for i in range(n)}
+
+
+def registered_kernels():
+    """Every kernel key of the conv-GEMM and the small-batch families in the library's registry, in the form
+    HipEngine.forward_plan reports them: ("gemm", cfg, taps, stride, flags), ("cc", taps, stride, ride, big, rows, windowed),
+    ("ccw", taps, stride, ride, ride_in, rows).  Returns (gemm keys, cc keys, ccw keys) as sets; host logic only."""
+    return tuple({(family,) + k for k in kernel_list(family)} for family in ("gemm", "cc", "ccw"))
 
 
 def fullchip_kernels():
-    """Every instantiation of the two full-chip families in the library's own lists (dad_debug_fullchip_kernel_exists over
-    tiles 0..9 x ride and dims 16..512 x tile0): ({("halo8", cfg, ride)}, {("seam", dim, tile0)}); host logic only."""
-    lib = load_library()
-    halo8 = {("halo8", cfg, ride) for cfg in range(10) for ride in (0, 1) if lib.dad_debug_fullchip_kernel_exists(0, cfg, ride)}
-    seam = {("seam", dim, t0) for dim in (16, 32, 48, 64, 96, 128, 256, 512) for t0 in (0, 1)
-            if lib.dad_debug_fullchip_kernel_exists(1, dim, t0)}
-    return halo8, seam
+    """Every instantiation of the two full-chip families in the library's registry: ({("halo8", cfg, ride)},
+    {("seam", dim, tile0)}); host logic only."""
+    return tuple({(family,) + k for k in kernel_list(family)} for family in ("halo8", "seam"))
 
 
 # DAD_BS_* of include/dad.h: the records of dad_debug_backward_steps, by kind (field 0 is the kind itself)
@@ -289,11 +284,8 @@ BS_WRITES = ("set", "add", "stage")       # BwdWrite of csrc/host_plan.hpp
 
 
 def wgrad_kernels():
-    """Every (taps, tile, windowed) of the library's conv_wgrad registry (dad_debug_wgrad_kernel_exists over taps 1..8,
-    tiles 0..3); host logic only."""
-    lib = load_library()
-    return {(taps, tile, win) for taps in range(1, 9) for tile in range(4) for win in (0, 1)
-            if lib.dad_debug_wgrad_kernel_exists(taps, tile, win)}
+    """Every (taps, tile, windowed) of the conv_wgrad family in the library's registry; host logic only."""
+    return kernel_list("wgrad")
 
 
 def projection_plan(state_dim: int, observation_dim: int, action_dim: int, batch: int, horizon: int, *,

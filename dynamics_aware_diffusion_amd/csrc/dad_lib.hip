@@ -167,155 +167,100 @@ void free_device(dad_model* m) {
 }
 
 // ---------------------------------------------------------------------- kernel registry
-// Every conv-GEMM instantiation the planner can ask for, keyed by what plan_launch decides.  Which ones exist is
-// decided by kernel_registered (host_plan.hpp) and nowhere else: the table is filled by a compile-time walk over
-// that predicate's whole domain.
-using KernFn = void (*)(const ConvParams);
-using KernKey = std::tuple<int, int, int, bool, bool, bool, bool, bool, bool>;   // cfg, taps, stride, x3, bdir, ragged, res, padded, windowed
-using KernTable = std::map<KernKey, KernFn>;
-
+// Every instantiated kernel a launch looks up, of every family of kFamilies (host_plan.hpp).  Which ones exist is
+// decided by the families' predicates and nowhere else: the table is filled by a compile-time walk over each
+// family's whole domain, which instantiates kernel_of<family, key...> where family_kernel_exists holds.
+//
+// The instantiation a key names, per family (the key's ints as kFamilies orders them):
 template <int CFG, int TAPS, int STRIDE, int F>
-void reg_kernel(KernTable& t) {
-    if constexpr (kernel_registered_f(CFG, TAPS, STRIDE, F)) {
-        constexpr TileCfg T = kTiles[CFG];
-        constexpr bool X3 = F & 1, BDIR = F & 2, RAGGED = F & 4, RES = F & 8, PADDED = F & 16, WIN = F & 32;
-        t[KernKey(CFG, TAPS, STRIDE, X3, BDIR, RAGGED, RES, PADDED, WIN)] =
-            dad::conv_gemm_f32<T.BM, T.BN, T.SK, tile_kc(CFG, TAPS, X3, BDIR), TAPS, STRIDE, RAGGED, X3, BDIR, RES, PADDED, WIN>;
+const void* gemm_kernel_of() {
+    constexpr TileCfg T = kTiles[CFG];
+    constexpr bool X3 = F & 1, BDIR = F & 2, RAGGED = F & 4, RES = F & 8, PADDED = F & 16, WIN = F & 32;
+    return (const void*)dad::conv_gemm_f32<T.BM, T.BN, T.SK, tile_kc(CFG, TAPS, X3, BDIR), TAPS, STRIDE, RAGGED, X3, BDIR, RES, PADDED, WIN>;
+}
+template <int TAPS, int STRIDE, int RIDE, int BIG, int ROWS, int WIN>
+const void* cc_kernel_of() { return (const void*)dad::conv_cc<TAPS, STRIDE, RIDE != 0, BIG != 0, ROWS, 6, WIN != 0>; }
+template <int TAPS, int STRIDE, int RIDE, int RIDE_IN, int ROWS>
+const void* ccw_kernel_of() { return (const void*)dad::conv_ccw<TAPS, STRIDE, RIDE != 0, RIDE_IN != 0, ROWS>; }
+template <int CFG, int RIDE>
+const void* halo8_kernel_of() {       // the block tile of kTiles[CFG]
+    static_assert(kTiles[CFG].BN == 64 && kTiles[CFG].KC == 32, "conv_halo8_f32 has 64-position tiles and 32-channel K chunks");
+    return (const void*)dad::conv_halo8_f32<kTiles[CFG].BM, kTiles[CFG].SK, RIDE != 0>;
+}
+template <int DIM, int TILE0>
+const void* seam_kernel_of() { return (const void*)dad::conv_seam_f32<DIM, TILE0 != 0>; }
+template <int TAPS, int TILE, int WIN>
+const void* wgrad_kernel_of() {       // tiles 0..2: 64 x 64, 64 x 32, 32 x 32; tile 3: 32 x 32 with the general staging path
+    return (const void*)dad::conv_wgrad<TAPS, TILE < 2 ? 2 : 1, TILE < 1 ? 2 : 1, TILE != 3, WIN != 0>;
+}
+template <int FAMILY, int... K>
+const void* kernel_of() {
+    if constexpr (FAMILY == FAM_GEMM) return gemm_kernel_of<K...>();
+    else if constexpr (FAMILY == FAM_CC) return cc_kernel_of<K...>();
+    else if constexpr (FAMILY == FAM_CCW) return ccw_kernel_of<K...>();
+    else if constexpr (FAMILY == FAM_HALO8) return halo8_kernel_of<K...>();
+    else if constexpr (FAMILY == FAM_SEAM) return seam_kernel_of<K...>();
+    else { static_assert(FAMILY == FAM_WGRAD, "a family without a template"); return wgrad_kernel_of<K...>(); }
+}
+
+// One table for all families, sorted by the packed (family, key): a byte per int, the family on top.
+struct KernelEntry { uint64_t key; const void* fn; };
+using KernelTable = std::vector<KernelEntry>;
+constexpr uint64_t kNoKey = ~0ull;            // what a key with an int outside 0..255 packs to: no entry has it
+constexpr uint64_t pack_key(int family, const int* k, int n) {
+    uint64_t key = (uint64_t)family;
+    for (int i = 0; i < kMaxKeyInts; ++i) {
+        const int v = i < n ? k[i] : 0;
+        if (v < 0 || v > 255) return kNoKey;
+        key = key << 8 | (uint64_t)v;
     }
+    return key;
 }
-// One fold per dimension (a single fold over all combinations would exceed the compiler's nesting limit).
-template <int CFG, int TAPS, size_t... F>
-void reg_flags(KernTable& t, std::index_sequence<F...>) {
-    (reg_kernel<CFG, TAPS, 1, (int)F>(t), ...);
-    (reg_kernel<CFG, TAPS, 2, (int)F>(t), ...);
+constexpr bool domains_pack() {               // every value of every domain fits its byte
+    for (int f = 0; f < kNumFamilies; ++f)
+        for (int a = 0; a < kFamilies[f].axes; ++a)
+            for (int i = 0; i < kFamilies[f].axis[a].n; ++i)
+                if (kFamilies[f].axis[a].at(i) < 0 || kFamilies[f].axis[a].at(i) > 255) return false;
+    return kNumFamilies <= 256 && kMaxKeyInts <= 7;
 }
-template <int CFG, size_t... TAPS>
-void reg_taps(KernTable& t, std::index_sequence<TAPS...>) {
-    (reg_flags<CFG, (int)TAPS + 1>(t, std::make_index_sequence<(1 << kRegFlags)>()), ...);
+static_assert(domains_pack(), "a kernel family's key does not pack into 64 bits");
+
+// The walk: RegWalk<FAMILY, K...> has fixed the first sizeof...(K) ints of a key and runs over the next axis.  One fold
+// per axis (a single fold over all combinations would exceed the compiler's nesting limit).
+template <int FAMILY, int... K>
+struct RegWalk {
+    static constexpr int kFixed = sizeof...(K);
+    static constexpr int kKey[kMaxKeyInts] = {K...};
+    template <size_t... I>
+    static void each(KernelTable& t, std::index_sequence<I...>) {
+        (RegWalk<FAMILY, K..., kFamilies[FAMILY].axis[kFixed].at((int)I)>::run(t), ...);
+    }
+    static void run(KernelTable& t) {
+        if constexpr (kFixed < kFamilies[FAMILY].axes) each(t, std::make_index_sequence<kFamilies[FAMILY].axis[kFixed].n>());
+        else if constexpr (family_kernel_exists(FAMILY, kKey)) t.push_back({pack_key(FAMILY, kKey, kFixed), kernel_of<FAMILY, K...>()});
+    }
+};
+template <size_t... FAMILY>
+void reg_families(KernelTable& t, std::index_sequence<FAMILY...>) {
+    (RegWalk<(int)FAMILY>::run(t), ...);
 }
-template <size_t... CFG>
-void reg_tiles(KernTable& t, std::index_sequence<CFG...>) {
-    (reg_taps<(int)CFG>(t, std::make_index_sequence<kRegMaxTaps>()), ...);
-}
-const KernTable& kernel_table() {
-    static const KernTable table = [] {
-        KernTable t;
-        reg_tiles(t, std::make_index_sequence<kNumTiles>());
+const KernelTable& kernel_table() {
+    static const KernelTable table = [] {
+        KernelTable t;
+        reg_families(t, std::make_index_sequence<kNumFamilies>());
+        std::sort(t.begin(), t.end(), [](const KernelEntry& a, const KernelEntry& b) { return a.key < b.key; });
         return t;
     }();
     return table;
 }
-
-// The other kernel families that stage through dynamic LDS: one list of instantiations each, searched by the
-// family's lookup and walked by configure_kernels.
-struct FamilyKernel { int key[5]; const void* fn; };
-using FamilyList = std::vector<FamilyKernel>;
-const void* find_kernel(const FamilyList& list, int k0, int k1, int k2, int k3 = 0, int k4 = 0) {
-    for (const FamilyKernel& k : list)
-        if (k.key[0] == k0 && k.key[1] == k1 && k.key[2] == k2 && k.key[3] == k3 && k.key[4] == k4) return k.fn;
-    return nullptr;
+// The kernel of a family's key (`n` ints), nullptr where the registry has none: every launch site refuses that.
+const void* find_kernel(int family, const int* k, int n) {
+    const uint64_t key = pack_key(family, k, n);
+    const KernelTable& t = kernel_table();
+    const auto it = std::lower_bound(t.begin(), t.end(), key, [](const KernelEntry& e, uint64_t v) { return e.key < v; });
+    return it != t.end() && it->key == key ? it->fn : nullptr;
 }
-
-// Small-batch conv kernels (conv_cc.hpp) by (taps, riding 1x1 conv, an input with 9..16 partial slabs, rows per
-// tile, windowed: layers longer than a tile).  The stride follows from the taps: 5 / 1, 3 / 2, 2 / 1.
-template <bool BIG, int NR>
-void add_cc(FamilyList& v) {
-    v.push_back({{5, 0, BIG, NR, 0}, (const void*)dad::conv_cc<5, 1, false, BIG, NR>});
-    v.push_back({{5, 1, BIG, NR, 0}, (const void*)dad::conv_cc<5, 1, true, BIG, NR>});
-    v.push_back({{3, 0, BIG, NR, 0}, (const void*)dad::conv_cc<3, 2, false, BIG, NR>});
-    v.push_back({{2, 0, BIG, NR, 0}, (const void*)dad::conv_cc<2, 1, false, BIG, NR>});
-}
-const FamilyList& cc_kernels() {
-    static const FamilyList list = [] {
-        FamilyList v;
-        add_cc<false, 16>(v); add_cc<false, 32>(v); add_cc<true, 16>(v); add_cc<true, 32>(v);
-        v.push_back({{5, 0, 0, 32, 1}, (const void*)dad::conv_cc<5, 1, false, false, 32, 6, true>});
-        v.push_back({{5, 1, 0, 32, 1}, (const void*)dad::conv_cc<5, 1, true, false, 32, 6, true>});
-        return v;
-    }();
-    return list;
-}
-const void* cc_kernel(int taps, bool ride, bool big, int rows, bool windowed) {
-    return find_kernel(cc_kernels(), taps, ride, big, rows, windowed);
-}
-
-// conv_ccw.hpp instantiations by (taps, this launch carries a riding 1x1 conv, an input has ride slabs, rows per
-// tile)
-template <bool RIDE, int NR>
-void add_ccw(FamilyList& v) {
-    v.push_back({{5, 0, RIDE, NR}, (const void*)dad::conv_ccw<5, 1, false, RIDE, NR>});
-    v.push_back({{5, 1, RIDE, NR}, (const void*)dad::conv_ccw<5, 1, true, RIDE, NR>});
-    v.push_back({{3, 0, RIDE, NR}, (const void*)dad::conv_ccw<3, 2, false, RIDE, NR>});
-    v.push_back({{2, 0, RIDE, NR}, (const void*)dad::conv_ccw<2, 1, false, RIDE, NR>});
-    v.push_back({{1, 0, RIDE, NR}, (const void*)dad::conv_ccw<1, 1, false, RIDE, NR>});
-}
-const FamilyList& ccw_kernels() {
-    static const FamilyList list = [] {
-        FamilyList v;
-        add_ccw<false, 16>(v); add_ccw<false, 32>(v); add_ccw<true, 16>(v); add_ccw<true, 32>(v);
-        return v;
-    }();
-    return list;
-}
-const void* ccw_kernel(int taps, bool res, bool ride_in, int rows) {
-    return find_kernel(ccw_kernels(), taps, res, ride_in, rows);
-}
-
-// conv_halo8.hpp instantiations by (tile cfg, this launch carries a riding 1x1 conv): the block tiles of kTiles[0 / 1]
-const FamilyList& halo8_kernels() {
-    static const FamilyList list = [] {
-        FamilyList v;
-        static_assert(kTiles[0].BM == 32 && kTiles[0].SK == 4 && kTiles[1].BM == 64 && kTiles[1].SK == 2 && halo8_kernel_exists(0) &&
-                      halo8_kernel_exists(1) && !halo8_kernel_exists(2), "conv_halo8_f32 covers tiles 0 and 1");
-        v.push_back({{0, 0}, (const void*)dad::conv_halo8_f32<32, 4, false>});
-        v.push_back({{0, 1}, (const void*)dad::conv_halo8_f32<32, 4, true>});
-        v.push_back({{1, 0}, (const void*)dad::conv_halo8_f32<64, 2, false>});
-        v.push_back({{1, 1}, (const void*)dad::conv_halo8_f32<64, 2, true>});
-        return v;
-    }();
-    return list;
-}
-const void* halo8_kernel(int cfg, bool res) { return find_kernel(halo8_kernels(), cfg, res, 0); }
-
-// conv_seam.hpp instantiations by (dim, the first conv's tile is 0): plan_seam takes them for tiles 0 and 1 (tile 1 needs
-// 64 output channels)
-const FamilyList& seam_kernels() {
-    static const FamilyList list = [] {
-        FamilyList v;
-        v.push_back({{32, 1}, (const void*)dad::conv_seam_f32<32, true>});
-        v.push_back({{64, 1}, (const void*)dad::conv_seam_f32<64, true>});
-        v.push_back({{64, 0}, (const void*)dad::conv_seam_f32<64, false>});
-        v.push_back({{128, 1}, (const void*)dad::conv_seam_f32<128, true>});
-        v.push_back({{128, 0}, (const void*)dad::conv_seam_f32<128, false>});
-        return v;
-    }();
-    return list;
-}
-const void* seam_kernel(int dim, bool tile0) { return find_kernel(seam_kernels(), dim, tile0, 0); }
-
-// conv_wgrad instantiations by (taps of kWgradTaps, block tile, windowed: layers longer than a chunk stages):
-// tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32 (eight); tile 3 = 32 x 32 with the general
-// staging path (operands that are not whole aligned float4 rows)
-template <int TAPS, bool WIN>
-void add_wgrad(FamilyList& v) {
-    v.push_back({{TAPS, 0, WIN}, (const void*)dad::conv_wgrad<TAPS, 2, 2, true, WIN>});
-    v.push_back({{TAPS, 1, WIN}, (const void*)dad::conv_wgrad<TAPS, 2, 1, true, WIN>});
-    v.push_back({{TAPS, 2, WIN}, (const void*)dad::conv_wgrad<TAPS, 1, 1, true, WIN>});
-    v.push_back({{TAPS, 3, WIN}, (const void*)dad::conv_wgrad<TAPS, 1, 1, false, WIN>});
-}
-template <size_t... I>
-void add_wgrad_taps(FamilyList& v, std::index_sequence<I...>) {
-    ((add_wgrad<kWgradTaps[I], false>(v), add_wgrad<kWgradTaps[I], true>(v)), ...);
-}
-const FamilyList& wgrad_kernels() {
-    static const FamilyList list = [] {
-        FamilyList v;
-        add_wgrad_taps(v, std::make_index_sequence<std::size(kWgradTaps)>());
-        return v;
-    }();
-    return list;
-}
-const void* wgrad_kernel(int taps, int tile, bool win) { return find_kernel(wgrad_kernels(), taps, tile, win); }
+const void* find_kernel(int family, std::initializer_list<int> k) { return find_kernel(family, k.begin(), (int)k.size()); }
 
 // Every kernel may use up to the full 160 KiB of LDS; the dynamic-LDS limit is a per-device
 // function attribute, raised once per device (not lazily per launch, so that nothing but launches
@@ -329,9 +274,7 @@ int configure_kernels() {
     if (done.count(dev)) return DAD_OK;
     std::vector<const void*> fns = {(const void*)dad::final_posterior_kernel, (const void*)dad::final_cc_kernel,
                                     (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>};
-    for (const auto& kv : kernel_table()) fns.push_back((const void*)kv.second);
-    for (const FamilyList* list : {&cc_kernels(), &ccw_kernels(), &wgrad_kernels(), &halo8_kernels(), &seam_kernels()})
-        for (const FamilyKernel& k : *list) fns.push_back(k.fn);
+    for (const KernelEntry& e : kernel_table()) fns.push_back(e.fn);      // every family
     for (const void* fn : fns)
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
     done.insert(dev);
@@ -472,7 +415,7 @@ int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, 
                    ? g_stamps + (size_t)(&op - &m->plan.convs[0]) * 4096 * 8 : nullptr;
 #endif
     if (g.halo8) {                     // conv_halo8.hpp: same tile, grid, LDS and operands, its own slot shifts
-        const void* fn = halo8_kernel(g.cfg, g.fused);
+        const void* fn = find_kernel(FAM_HALO8, {g.cfg, g.fused});
         if (fn == nullptr || gn_pass || p.pre != nullptr || p.stats != nullptr || p.kslices != 1)
             return fail(DAD_E_INVALID, "no halo-skipping kernel for %s (tile %d res=%d)", op.name.c_str(), g.cfg, (int)g.fused);
         p.xswz = g.xswz8;
@@ -480,14 +423,12 @@ int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, 
         HIP_TRY(hipLaunchKernel(fn, dim3(g.gx, g.gy, g.gz), dim3(g.threads), hargs, g.lds_bytes, st));
         return DAD_OK;
     }
-    const auto& table = kernel_table();
-    const auto it = table.find(KernKey(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded, g.windowed));
-    if (it == table.end())
+    const void* fn = find_kernel(FAM_GEMM, {g.cfg, op.taps, op.stride, launch_flags(op, g)});
+    if (fn == nullptr)
         return fail(DAD_E_INVALID, "no kernel for %s (tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d)",
                     op.name.c_str(), g.cfg, op.taps, op.stride, (int)op.x3, (int)op.bdir, (int)g.ragged, (int)g.fused);
     void* args[] = {&p};
-    HIP_TRY(hipLaunchKernel((const void*)it->second, dim3(g.gx, g.gy, g.gz), dim3(g.threads), args,
-                            g.lds_bytes, st));
+    HIP_TRY(hipLaunchKernel(fn, dim3(g.gx, g.gy, g.gz), dim3(g.threads), args, g.lds_bytes, st));
     if (gn_pass) return launch_gn_pass(m, op, g.gn_npt, batch, io, st);
     return DAD_OK;
 }
@@ -581,8 +522,8 @@ int run_conv_cc(dad_model* m, const CcPlan& cc, int i, const float* xext, float*
     p.oslab = slabs + o.oslab;
     p.orslab = o.orslab >= 0 ? slabs + o.orslab : nullptr;
     p.out_rows = o.out_rows;
-    const void* kern = o.wide ? ccw_kernel(op.taps, op.ride, o.ride_in, o.tile_rows)
-                              : cc_kernel(op.taps, op.ride, o.big, o.tile_rows, op.Lout > 32);
+    const void* kern = o.wide ? find_kernel(FAM_CCW, {op.taps, op.stride, op.ride, o.ride_in, o.tile_rows})
+                              : find_kernel(FAM_CC, {op.taps, op.stride, op.ride, o.big, o.tile_rows, op.Lout > 32});
     if (!kern) return fail(DAD_E_INVALID, "no small-batch kernel for %s (taps=%d stride=%d)", op.name.c_str(), op.taps, op.stride);
     static const bool trace = getenv("DAD_TRACE_TILES") != nullptr;
     if (trace)
@@ -640,7 +581,7 @@ int launch_seam(dad_model* m, const FwdPlan& f, const SeamCall& sc, int t_conv, 
     q.c.xswz = sc.plan->xswz;
     q.units = sc.plan->units;
     q.hshift = ilog2(m->cfg.horizon);
-    const void* fn = seam_kernel(m->cfg.dim, sc.plan->tile0);
+    const void* fn = find_kernel(FAM_SEAM, {m->cfg.dim, sc.plan->tile0});
     if (fn == nullptr || q.c.rdst == nullptr || q.c.rbias == nullptr || q.c.gamma == nullptr)
         return fail(DAD_E_INVALID, "no seam kernel for dim %d on tile %d", m->cfg.dim, sc.plan->cfg);
     void* args[] = {&q};
@@ -1266,9 +1207,10 @@ int launch_wgrad(const dad_model* m, const BwdStep& s, const TrainScratch::Wgrad
     p.wshift = w.sh.wshift;
     p.ksplit = g.ksplit; p.samples_per_split = g.sps; p.spc = g.spc;
     p.zero = m->d_zero;
+    const void* fn = find_kernel(FAM_WGRAD, {s.taps, g.tile, w.sh.wshift > 0});
+    if (fn == nullptr) return fail(DAD_E_INVALID, "no weight-gradient kernel for %d taps on tile %d (windowed=%d)", s.taps, g.tile, (int)(w.sh.wshift > 0));
     void* args[] = {&p};
-    HIP_TRY(hipLaunchKernel(wgrad_kernel(s.taps, g.tile, w.sh.wshift > 0), dim3(g.gx, g.gy, (unsigned)g.ksplit),
-                            dim3(dad::WG_THREADS), args, g.lds, st));
+    HIP_TRY(hipLaunchKernel(fn, dim3(g.gx, g.gy, (unsigned)g.ksplit), dim3(dad::WG_THREADS), args, g.lds, st));
     if (g.ksplit > 1) {
         const long n4 = p.out_numel / 4;
         hipLaunchKernelGGL(dad::sum_slabs_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, out, wslab, n4, g.ksplit);
@@ -1715,25 +1657,49 @@ int dad_fill_normal(float* x, int32_t batch, int32_t row_elems, uint64_t seed, u
 #ifdef DAD_STAMPS
 int dad_debug_stamps(void* buf) { g_stamps = (unsigned long long*)buf; return DAD_OK; }
 #endif
-// 1 when the generated registry covers the domain of kernel_registered (an entry wherever the predicate is true)
-// and holds nothing else
+// 1 when the generated registry holds, for every family, an entry wherever the family's predicate is true over its
+// domain, the family's count of them, and nothing else
 int dad_debug_kernel_table_consistent(void) {
-    const KernTable& t = kernel_table();
     size_t hits = 0;
-    for (int cfg = 0; cfg < kNumTiles; ++cfg)
-        for (int taps = 1; taps <= kRegMaxTaps; ++taps)
-            for (int stride = 1; stride <= 2; ++stride)
-                for (int f = 0; f < (1 << kRegFlags); ++f) {
-                    const bool x3 = f & 1, bdir = f & 2, ragged = f & 4, res = f & 8, padded = f & 16, win = f & 32;
-                    const bool have = t.count(KernKey(cfg, taps, stride, x3, bdir, ragged, res, padded, win)) != 0;
-                    if (have != kernel_registered_f(cfg, taps, stride, f)) {
-                        fail(DAD_E_INVALID, "kernel table mismatch at tile %d taps=%d stride=%d x3=%d bdir=%d ragged=%d res=%d padded=%d windowed=%d (registry %d)",
-                             cfg, taps, stride, (int)x3, (int)bdir, (int)ragged, (int)res, (int)padded, (int)win, (int)have);
-                        return 0;
-                    }
-                    hits += have;
-                }
-    return hits == t.size() ? 1 : 0;
+    for (int fam = 0; fam < kNumFamilies; ++fam) {
+        const FamilyDomain& d = kFamilies[fam];
+        int n = 0;
+        for (int i = 0; i < family_domain_size(fam); ++i) {
+            int k[kMaxKeyInts] = {};
+            family_key_at(fam, i, k);
+            const bool have = find_kernel(fam, k, d.axes) != nullptr;
+            if (have != family_kernel_exists(fam, k)) {
+                fail(DAD_E_INVALID, "kernel table mismatch: %s key (%d, %d, %d, %d, %d, %d)[:%d] (registry %d)", d.name, k[0], k[1], k[2], k[3],
+                     k[4], k[5], d.axes, (int)have);
+                return 0;
+            }
+            n += have;
+        }
+        if (n != d.count) {
+            fail(DAD_E_INVALID, "kernel table mismatch: %d %s kernels, expected %d", n, d.name, d.count);
+            return 0;
+        }
+        hits += (size_t)n;
+    }
+    if (hits != kernel_table().size()) {      // an entry outside every domain, or one key twice
+        fail(DAD_E_INVALID, "kernel table mismatch: %zu entries, %zu inside the families' domains", kernel_table().size(), hits);
+        return 0;
+    }
+    return 1;
+}
+
+int dad_debug_kernel_list(int32_t family, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (family < 0 || family >= kNumFamilies || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    const int axes = kFamilies[family].axes;
+    std::vector<int32_t> r = {0, axes};
+    for (const KernelEntry& e : kernel_table()) {
+        if ((int)(e.key >> (8 * kMaxKeyInts)) != family) continue;
+        for (int a = 0; a < axes; ++a) r.push_back((int32_t)(e.key >> (8 * (kMaxKeyInts - 1 - a)) & 0xff));
+        ++r[0];
+    }
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
 }
 
 #ifdef DAD_WG_STAMPS
@@ -1849,10 +1815,6 @@ int dad_debug_backward_steps(dad_model* m, int32_t batch, int32_t* out, int32_t 
     return DAD_OK;
 }
 
-int dad_debug_wgrad_kernel_exists(int32_t taps, int32_t tile, int32_t windowed) {
-    return wgrad_kernel(taps, tile, windowed != 0) != nullptr ? 1 : 0;
-}
-
 int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
     if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
     if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
@@ -1928,22 +1890,6 @@ int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t
 }
 
 const char* dad_debug_seam_reason(int32_t reason) { return seam_reason(reason); }
-
-int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32_t flags) {
-    if (taps < 1 || taps > kRegMaxTaps || stride < 1 || stride > 2 || flags < 0 || flags >= (1 << kRegFlags)) return 0;
-    return kernel_registered_f(cfg, taps, stride, flags) ? 1 : 0;
-}
-
-int dad_debug_small_kernel_exists(int32_t taps, int32_t stride, int32_t ride, int32_t wide, int32_t big, int32_t ride_in,
-                                  int32_t rows, int32_t windowed) {
-    return small_kernel_exists(taps, stride, ride != 0, wide != 0, big != 0, ride_in != 0, rows, windowed != 0) ? 1 : 0;
-}
-
-int dad_debug_fullchip_kernel_exists(int32_t family, int32_t a, int32_t b) {
-    if (family == DAD_FAMILY_HALO8) return halo8_kernel(a, b != 0) != nullptr ? 1 : 0;
-    if (family == DAD_FAMILY_SEAM) return seam_kernel(a, b != 0) != nullptr ? 1 : 0;
-    return 0;
-}
 
 int dad_profile_enable(dad_model* m, int32_t on) {
     if (!m) return fail(DAD_E_INVALID, "null model");

@@ -1126,7 +1126,8 @@ inline void choose_launch(const HostModel& m, const ConvOp& op, int batch, Launc
 // (kernel_table) is generated by walking this predicate's domain at compile time and instantiates a kernel where it
 // is true and nowhere else, and the planner — and the sanitizer harness, which has no device code — refuses a launch
 // it is false for.  dad_debug_kernel_table_consistent() checks that the generated table covers the domain and
-// holds nothing else.  The domain: tile 0..kNumTiles-1, taps 1..kRegMaxTaps, stride 1..2, kRegFlags flags.
+// holds nothing else.  The domain: tile 0..kNumTiles-1, taps 1..kRegMaxTaps, stride 1..2, kRegFlags flags (kFamilies,
+// at the end of this file, lists it with the other families' and holds the count).
 constexpr int kRegMaxTaps = 7;
 constexpr int kRegFlags = 6;      // x3, bdir, ragged, res, padded, windowed: bits 0..5 of a flag word
 constexpr bool kernel_registered(int cfg, int taps, int stride, bool x3, bool bdir, bool ragged, bool res, bool padded = false,
@@ -1153,16 +1154,6 @@ constexpr bool kernel_registered(int cfg, int taps, int stride, bool x3, bool bd
 constexpr bool kernel_registered_f(int cfg, int taps, int stride, int f) {
     return kernel_registered(cfg, taps, stride, f & 1, f & 2, f & 4, f & 8, f & 16, f & 32);
 }
-constexpr int count_registered() {
-    int n = 0;
-    for (int cfg = 0; cfg < kNumTiles; ++cfg)
-        for (int taps = 1; taps <= kRegMaxTaps; ++taps)
-            for (int stride = 1; stride <= 2; ++stride)
-                for (int f = 0; f < (1 << kRegFlags); ++f) n += kernel_registered_f(cfg, taps, stride, f);
-    return n;
-}
-// 223 plain + 79 PADDED + 33 windowed (125 of them RAGGED).  Adding or dropping a kernel form changes this line.
-static_assert(count_registered() == 335, "the set of conv-GEMM kernels changed: kernel_registered");
 
 inline int plan_launch(const HostModel& m, const ConvOp& op, int batch, LaunchGeom& g) {
     choose_launch(m, op, batch, g);
@@ -1247,7 +1238,11 @@ inline int plan_launch(const HostModel& m, const ConvOp& op, int batch, LaunchGe
 // tiles or more) of the heuristic: a forced tile (dad_debug_set_tile, split-K switched off included) pins the
 // conv-GEMM kernels and their summation order.  Not for the training forward (plan_forward applies it to m.plan
 // only).  The ride is decided by fused_at as before.
-constexpr bool halo8_kernel_exists(int cfg) { return cfg == 0 || cfg == 1; }      // each with and without the ride
+// Which conv_halo8_f32 instantiations exist, by (tile cfg, the launch carries a riding 1x1 conv): the block tiles of
+// kTiles[0 / 1], each with and without the ride.
+constexpr bool halo8_kernel_exists(int cfg, bool /*ride*/) { return cfg == 0 || cfg == 1; }
+// ... on this tile at all, with the ride or without
+constexpr bool halo8_kernel_exists(int cfg) { return halo8_kernel_exists(cfg, false) || halo8_kernel_exists(cfg, true); }
 inline bool halo8_layer(const ConvOp& op) {
     return op.kind == CONV_K5 && op.taps == 5 && op.stride == 1 && op.Lin == 8 && op.Lout == 8 && !op.x3 && !op.bdir &&
            !op.net_padded && !op.padded() && op.pre < 0 && op.stats < 0;
@@ -1255,7 +1250,7 @@ inline bool halo8_layer(const ConvOp& op) {
 inline void choose_halo8(const HostModel& m, const ConvOp& op, LaunchGeom& g) {
     g.halo8 = false; g.xswz8 = 0;
     if (!m.halo8_enabled || m.force_tile >= 0 || !m.split_enabled || g.cfg < 0 || !halo8_layer(op)) return;
-    if (!halo8_kernel_exists(g.cfg) || g.kc != 32 || g.ragged || g.padded || g.windowed || g.split.kslices != 1) return;
+    if (!halo8_kernel_exists(g.cfg, g.fused) || g.kc != 32 || g.ragged || g.padded || g.windowed || g.split.kslices != 1) return;
     if ((long)g.mtiles * g.ntiles_n < kSplitMaxTiles) return;
     g.halo8 = true;
     g.xswz8 = m.xswz_enabled ? find_xswz_pairs(m, op.Lout, op.taps / 2, (g.kc + 4) / 4) : 0;
@@ -1300,8 +1295,8 @@ struct CcPlan {
     std::string why;         // when !ok: which rule refused the plan (diagnostic)
 };
 inline CcPlan& refuse(CcPlan& P, const char* why) { P.why = why; return P; }
-// Which small-batch conv kernels exist: what add_cc / add_ccw of dad_lib.hip instantiate (`rows` per tile; `ride`: the
-// launch carries a riding 1x1 conv; conv_ccw has every form of `ride_in`).
+// Which small-batch conv kernels exist: conv_cc, and (`wide`) conv_ccw (`rows` per tile; `ride`: the launch carries a
+// riding 1x1 conv; conv_ccw has every form of `ride_in`).  The registry of dad_lib.hip is generated from it (kFamilies).
 constexpr bool cc_kernel_exists(int taps, int stride, bool ride, bool wide, bool big, int rows, bool windowed) {
     if ((rows != 16 && rows != 32) || (ride && !(taps == 5 && stride == 1))) return false;
     const bool shape_ok = (taps == 5 && stride == 1) || (taps == 3 && stride == 2) || (taps == 2 && stride == 1);
@@ -1576,11 +1571,12 @@ enum SeamWhy {
     SEAM_PADDED,          // zero-padded horizon or GroupNorm groups
     SEAM_HORIZON,         // a 32-row tile holds whole samples: 8, 16 or 32 positions
     SEAM_TRANSITION_DIM,  // one 16-channel granule
-    SEAM_DIM,             // instantiations: 32, 64, 128
+    SEAM_DIM,             // no instantiation for this dim on either tile (seam_kernel_exists)
     SEAM_FIRST_CONV,      // the first launch is not the 5-tap transition_dim -> dim Conv1dBlock of one K chunk
     SEAM_NO_RIDE,         // the 1x1 residual conv does not ride in it (fused_at)
-    SEAM_TILE,            // its tile is neither 0 nor 1: the launch keeps the tile's summation and reduction order,
-                          //   and has them for these two (tile 2, from 512 N tiles on, owns eight float4 per thread)
+    SEAM_TILE,            // no instantiation for its tile (neither 0 nor 1, or seam_kernel_exists): the launch keeps the tile's
+                          //   summation and reduction order, and has them for these two (tile 2, from 512 N tiles on, owns
+                          //   eight float4 per thread)
     SEAM_LDS,
     SEAM_BUFFERS,         // final_act against the buffers the conv and the ride write (seam_buffers_ok)
     SEAM_WHYS
@@ -1607,6 +1603,14 @@ struct SeamPlan {
     int buffers = -1;        // seam_buffer_relation
     bool taken() const { return why == SEAM_TAKEN; }
 };
+// Which conv_seam_f32 instantiations exist, by (dim, the first conv's tile is 0, else 1): tile 1 holds 64 output
+// channels, so it starts at dim 64.
+constexpr int kSeamDims[] = {32, 64, 128};
+constexpr bool seam_kernel_exists(int dim, bool tile0) {
+    for (int d : kSeamDims)
+        if (d == dim) return tile0 || dim >= 64;
+    return false;
+}
 // The launch reads final_act and writes the first conv's dst and rdst.  The activation allocator reuses buffer ids:
 // final_conv[0] is handed the first free level-0 buffer, which on every net so far is the first conv's own.  Allowed:
 // three buffers whose floats do not overlap — or final_act being the very buffer (same id, so same offset) the conv
@@ -1648,14 +1652,14 @@ inline SeamPlan plan_seam(const HostModel& m, const FwdPlan& f, bool projection)
     if (traj_horizon(m) != H || op.net_padded || op.padded()) return no(SEAM_PADDED);
     if (H != 8 && H != 16 && H != 32) return no(SEAM_HORIZON);
     if (td > 16) return no(SEAM_TRANSITION_DIM);
-    if (dim != 32 && dim != 64 && dim != 128) return no(SEAM_DIM);
+    if (!seam_kernel_exists(dim, true) && !seam_kernel_exists(dim, false)) return no(SEAM_DIM);
     const LaunchGeom& g = l.g;
     if (l.conv != 0 || !l.ok || op.kind != CONV_K5 || op.taps != 5 || op.stride != 1 || op.src0 != -2 || op.src1 >= 0 || op.cin0 != td ||
         op.cin1 != 0 || op.cout != dim || op.M != dim || op.Lin != H || op.Lout != H || op.norm.empty() || op.res != -1 || op.cat0 >= 0 ||
         op.x3 || op.bdir || op.kc != 16 || op.cin_pad < 16 || g.halo8 || g.padded || g.windowed || g.split.kslices != 1)
         return no(SEAM_FIRST_CONV);
     if (!g.fused || op.rdst < 0) return no(SEAM_NO_RIDE);
-    if ((g.cfg != 0 && g.cfg != 1) || g.kc != 32) return no(SEAM_TILE);
+    if ((g.cfg != 0 && g.cfg != 1) || g.kc != 32 || !seam_kernel_exists(dim, g.cfg == 0)) return no(SEAM_TILE);
     s.lds_bytes = dad::seam_lds_floats(td, dim, H) * sizeof(float);
     if (s.lds_bytes > dad::kLdsBytes) return no(SEAM_LDS);
     if (!seam_buffers_ok(m.plan, op)) return no(SEAM_BUFFERS);
@@ -1710,8 +1714,16 @@ inline ProjectPlan plan_project(int D, int batch, size_t x_bytes, size_t scratch
 }
 
 // ------------------------------------------------------------------ backward pass: per-batch geometry
-// conv_wgrad instantiations exist for these tap counts (the list of dad_lib.hip, wgrad_kernels, is built from them)
+// Which conv_wgrad instantiations exist, by (taps, block tile, windowed: layers longer than a chunk stages): these tap
+// counts, each on tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32 (eight) and 3 = 32 x 32 with the
+// general staging path (operands that are not whole aligned float4 rows), plain and windowed.
 constexpr int kWgradTaps[] = {1, 3, 4, 5, 7};
+constexpr int kWgradTiles = 4;
+constexpr bool wgrad_kernel_exists(int taps, int tile, bool /*windowed*/) {
+    for (int t : kWgradTaps)
+        if (t == taps) return tile >= 0 && tile < kWgradTiles;
+    return false;
+}
 struct WgradGeom { int spc, ksplit, sps, tile, tm, tn; unsigned gx, gy; size_t lds; };
 // Layers longer than a chunk stages (more than 128 rows of G or Z per sample: horizons 256 / 512) run the windowed
 // kernel over windows of kWgradWindow rows of G (and the matching rows of Z) as if they were samples.
@@ -1779,7 +1791,7 @@ inline int train_scratch(const HostModel& m, int B, TrainScratch& t) {
             if (g.lds > dad::kLdsBytes || g.spc * sh.Lg > dad::WG_MAX_GROWS ||
                 g.spc * dad::wgrad_segz(sh.Lz, s.taps, s.pad) > dad::WG_MAX_ZROWS || (g.spc * sh.Lg) % (4 * kgroups) != 0)
                 first.note(fail(DAD_E_INVALID, "wgrad: a chunk of %d samples x %d rows does not fit the kernel's staging", g.spc, sh.Lz));
-            if (std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) == std::end(kWgradTaps))
+            if (!wgrad_kernel_exists(s.taps, g.tile, sh.wshift > 0))
                 first.note(fail(DAD_E_INVALID, "wgrad: %d taps", s.taps));
             if (g.ksplit > 1 && numel % 4 != 0)
                 first.note(fail(DAD_E_INVALID, "wgrad: %ld gradient elements (not a multiple of 4)", numel));
@@ -2037,13 +2049,107 @@ inline int objective_plan_report(const HostModel& m, int B, std::vector<int32_t>
     return rc;
 }
 
-// The small-batch kernels as one domain for a walk (dad_debug_small_kernel_exists): conv_cc by (taps, stride, ride, big,
-// rows, windowed) — it has no `ride_in` form, a consumer of ride slabs runs the same instantiation — and conv_ccw
-// (`wide`) by (taps, stride, ride, ride_in, rows): 18 + 20 kernels.
+// The small-batch kernels of one launch, whichever of the two families it takes: conv_cc has no `ride_in` form (a
+// consumer of ride slabs runs the same instantiation), conv_ccw (`wide`) neither `big` nor `windowed`.
 constexpr bool small_kernel_exists(int taps, int stride, bool ride, bool wide, bool big, bool ride_in, int rows, bool windowed) {
     if (wide) return !big && cc_kernel_exists(taps, stride, ride, true, false, rows, windowed);
     return !ride_in && cc_kernel_exists(taps, stride, ride, false, big, rows, windowed);
 }
+
+// ------------------------------------------------------------------ the kernel families
+// Every family of instantiated kernels the library looks up at launch time: its key, the finite domain the key ranges
+// over, and — family_kernel_exists — the predicate above that says where in the domain a kernel exists.  The registry of
+// dad_lib.hip is generated from this table alone (one compile-time walk per family instantiates a kernel where the
+// predicate holds and nowhere else), the planner asks the same predicates, and dad_debug_kernel_table_consistent()
+// walks every domain against the generated table.  A new family is one predicate and one line here, plus the line of
+// dad_lib.hip (kernel_of) that names its template.
+enum KernelFamily {
+    FAM_GEMM = DAD_FAMILY_GEMM,       // conv_gemm_f32   (cfg, taps, stride, flags)                    kernel_registered_f
+    FAM_CC = DAD_FAMILY_CC,           // conv_cc         (taps, stride, ride, big, rows, windowed)     cc_kernel_exists
+    FAM_CCW = DAD_FAMILY_CCW,         // conv_ccw        (taps, stride, ride, ride_in, rows)           cc_kernel_exists, wide
+    FAM_HALO8 = DAD_FAMILY_HALO8,     // conv_halo8_f32  (cfg, ride)                                   halo8_kernel_exists
+    FAM_SEAM = DAD_FAMILY_SEAM,       // conv_seam_f32   (dim, tile0)                                  seam_kernel_exists
+    FAM_WGRAD = DAD_FAMILY_WGRAD,     // conv_wgrad      (taps, tile, windowed)                        wgrad_kernel_exists
+    kNumFamilies = DAD_FAMILIES
+};
+constexpr int kMaxKeyInts = DAD_KERNEL_KEY_MAX;
+// One axis of a domain: the `n` values lo, lo + 1, ..., or — with a list — values[0 .. n).
+struct KeyAxis {
+    int n, lo;
+    const int* values;
+    constexpr int at(int i) const { return values != nullptr ? values[i] : lo + i; }
+    constexpr bool has(int v) const {
+        if (values == nullptr) return v >= lo && v < lo + n;
+        for (int i = 0; i < n; ++i)
+            if (values[i] == v) return true;
+        return false;
+    }
+};
+struct FamilyDomain { const char* name; int count, axes; KeyAxis axis[kMaxKeyInts]; };
+constexpr int kCcRows[] = {16, 32};
+constexpr KeyAxis kTapsAxis = {kRegMaxTaps, 1, nullptr}, kStrideAxis = {2, 1, nullptr}, kBoolAxis = {2, 0, nullptr};
+// 335 conv-GEMM kernels: 223 plain + 79 PADDED + 33 windowed (125 of them RAGGED).  Adding or dropping a kernel form
+// changes a count here.
+constexpr FamilyDomain kFamilies[kNumFamilies] = {
+    {"conv_gemm_f32", 335, 4, {{kNumTiles, 0, nullptr}, kTapsAxis, kStrideAxis, {1 << kRegFlags, 0, nullptr}}},
+    {"conv_cc", 18, 6, {kTapsAxis, kStrideAxis, kBoolAxis, kBoolAxis, {2, 0, kCcRows}, kBoolAxis}},
+    {"conv_ccw", 20, 5, {kTapsAxis, kStrideAxis, kBoolAxis, kBoolAxis, {2, 0, kCcRows}}},
+    {"conv_halo8_f32", 4, 2, {{kNumTiles, 0, nullptr}, kBoolAxis}},
+    {"conv_seam_f32", 5, 2, {{(int)std::size(kSeamDims), 0, kSeamDims}, kBoolAxis}},
+    {"conv_wgrad", 40, 3, {kTapsAxis, {kWgradTiles, 0, nullptr}, kBoolAxis}},
+};
+constexpr bool family_key_in_domain(int family, const int* k) {
+    for (int a = 0; a < kFamilies[family].axes; ++a)
+        if (!kFamilies[family].axis[a].has(k[a])) return false;
+    return true;
+}
+// `k`: the family's key, kFamilies[family].axes ints
+constexpr bool family_kernel_exists(int family, const int* k) {
+    if (family < 0 || family >= kNumFamilies || !family_key_in_domain(family, k)) return false;
+    switch (family) {
+        case FAM_GEMM: return kernel_registered_f(k[0], k[1], k[2], k[3]);
+        case FAM_CC: return cc_kernel_exists(k[0], k[1], k[2] != 0, false, k[3] != 0, k[4], k[5] != 0);
+        case FAM_CCW: return cc_kernel_exists(k[0], k[1], k[2] != 0, true, false, k[4], false);     // every form of ride_in, k[3]
+        case FAM_HALO8: return halo8_kernel_exists(k[0], k[1] != 0);
+        case FAM_SEAM: return seam_kernel_exists(k[0], k[1] != 0);
+        case FAM_WGRAD: return wgrad_kernel_exists(k[0], k[1], k[2] != 0);
+    }
+    return false;
+}
+inline bool family_kernel_exists(int family, std::initializer_list<int> k) {
+    int key[kMaxKeyInts] = {};
+    if (family < 0 || family >= kNumFamilies || (int)k.size() != kFamilies[family].axes) return false;
+    std::copy(k.begin(), k.end(), key);
+    return family_kernel_exists(family, key);
+}
+// The domain as a sequence: key number `index` of family_domain_size(family), the last axis running fastest.
+constexpr int family_domain_size(int family) {
+    int n = 1;
+    for (int a = 0; a < kFamilies[family].axes; ++a) n *= kFamilies[family].axis[a].n;
+    return n;
+}
+constexpr void family_key_at(int family, int index, int* k) {
+    for (int a = kFamilies[family].axes - 1; a >= 0; --a) {
+        const KeyAxis& ax = kFamilies[family].axis[a];
+        k[a] = ax.at(index % ax.n);
+        index /= ax.n;
+    }
+}
+constexpr int count_family(int family) {
+    int n = 0;
+    for (int i = 0; i < family_domain_size(family); ++i) {
+        int k[kMaxKeyInts] = {};
+        family_key_at(family, i, k);
+        n += family_kernel_exists(family, k);
+    }
+    return n;
+}
+static_assert(count_family(FAM_GEMM) == 335 && kFamilies[FAM_GEMM].count == 335, "the set of conv-GEMM kernels changed: kernel_registered");
+static_assert(count_family(FAM_CC) == 18 && kFamilies[FAM_CC].count == 18, "the set of conv_cc kernels changed: cc_kernel_exists");
+static_assert(count_family(FAM_CCW) == 20 && kFamilies[FAM_CCW].count == 20, "the set of conv_ccw kernels changed: cc_kernel_exists");
+static_assert(count_family(FAM_HALO8) == 4 && kFamilies[FAM_HALO8].count == 4, "the set of conv_halo8_f32 kernels changed: halo8_kernel_exists");
+static_assert(count_family(FAM_SEAM) == 5 && kFamilies[FAM_SEAM].count == 5, "the set of conv_seam_f32 kernels changed: seam_kernel_exists");
+static_assert(count_family(FAM_WGRAD) == 40 && kFamilies[FAM_WGRAD].count == 40, "the set of conv_wgrad kernels changed: wgrad_kernel_exists");
 
 // dad_debug_forward_plan: what one forward evaluation (modes 0 .. 2) or the data-gradient half of one backward pass
 // (mode 3) launches at a batch (layout: include/dad.h, DAD_FP_*).  forward_plan_encode writes down a description the

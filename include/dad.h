@@ -362,8 +362,9 @@ int dad_debug_mish(const float* in, float* out, int64_t n, dad_stream_t stream);
 /* Where dad_train_objective_forward keeps x_t and the denoiser's output inside `saved` (byte offsets; host-side
  * query): lets a test compare x_t with q_sample (diffusion.py:138-157) bit for bit. */
 int dad_debug_objective_offsets(const dad_model* m, int32_t batch, size_t* xt_offset, size_t* out_offset);
-/* 1 when the kernel registry, generated from the planner's statement of which conv-GEMM kernels exist, covers that
- * statement's whole domain and holds nothing else (no device call) */
+/* 1 when the kernel registry, generated from the planner's statements of which kernels of every family (DAD_FAMILY_*)
+ * exist, holds an entry wherever a statement is true over its whole domain, nothing else, and the expected number of
+ * kernels per family (no device call) */
 int dad_debug_kernel_table_consistent(void);
 /* Which kernels a batch takes (host-side query, no device work): launches_out = conv launches of one
  * denoiser evaluation through the small-batch consumer-combine kernels (csrc/conv_cc.hpp), 0 when the
@@ -508,9 +509,6 @@ int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t c
 #define DAD_BS_CL_WRITE 5
 #define DAD_BS_REC_INTS 25
 int dad_debug_backward_steps(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
-/* 1 when conv_wgrad<taps, tile, windowed> is in the library's registry of weight-gradient kernels (tile as
- * DAD_BP_TILE; no device call): lets a test walk the whole domain */
-int dad_debug_wgrad_kernel_exists(int32_t taps, int32_t tile, int32_t windowed);
 
 /* The time chain of one fused objective step (dad_train_objective_forward + dad_train_objective_backward) at a batch:
  * the list of launches the two entry points replay (host-side query, no device work; needs
@@ -717,19 +715,24 @@ int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t a
 #define DAD_SEAM_BUF_RDST 2
 int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out);
 const char* dad_debug_seam_reason(int32_t reason);
-/* 1 where the conv-GEMM instantiation (tile cfg, taps, stride, flag word as above) exists: the planner's one statement of
- * it (kernel_registered_f), whose domain is cfg 0..9, taps 1..7, stride 1..2, flags 0..63.  No device call. */
-int dad_debug_kernel_registered(int32_t cfg, int32_t taps, int32_t stride, int32_t flags);
-/* 1 where the small-batch conv instantiation exists (cc_kernel_exists): conv_cc by (taps, stride, ride, big, rows,
- * windowed) with wide = ride_in = 0, conv_ccw by (taps, stride, ride, ride_in, rows) with wide = 1, big = windowed = 0. */
-int dad_debug_small_kernel_exists(int32_t taps, int32_t stride, int32_t ride, int32_t wide, int32_t big, int32_t ride_in,
-                                  int32_t rows, int32_t windowed);
-/* 1 where the instantiation is in the library's list of its family (the lists the launches look their kernel up in):
- * DAD_FAMILY_HALO8 conv_halo8_f32 by (a = tile cfg, b = riding 1x1 conv), DAD_FAMILY_SEAM conv_seam_f32 by (a = dim,
- * b = the first conv's tile is 0).  No device call. */
-#define DAD_FAMILY_HALO8 0
-#define DAD_FAMILY_SEAM 1
-int dad_debug_fullchip_kernel_exists(int32_t family, int32_t a, int32_t b);
+/* The kernels of one family in the library's own registry: the table every launch looks its kernel up in (no device
+ * call).  Writes min(capacity, *needed_out) int32 values to `out`: [0] the number of kernels, [1] the ints of one key,
+ * then the keys —
+ *   DAD_FAMILY_GEMM   conv_gemm_f32   (tile cfg, taps, stride, flag word as above)
+ *   DAD_FAMILY_CC     conv_cc         (taps, stride, riding 1x1 conv, big, rows per tile, windowed)
+ *   DAD_FAMILY_CCW    conv_ccw        (taps, stride, riding 1x1 conv, ride_in, rows per tile)
+ *   DAD_FAMILY_HALO8  conv_halo8_f32  (tile cfg, riding 1x1 conv)
+ *   DAD_FAMILY_SEAM   conv_seam_f32   (dim, the first conv's tile is 0)
+ *   DAD_FAMILY_WGRAD  conv_wgrad      (taps, tile as DAD_BP_TILE, windowed) */
+#define DAD_FAMILY_GEMM 0
+#define DAD_FAMILY_CC 1
+#define DAD_FAMILY_CCW 2
+#define DAD_FAMILY_HALO8 3
+#define DAD_FAMILY_SEAM 4
+#define DAD_FAMILY_WGRAD 5
+#define DAD_FAMILIES 6
+#define DAD_KERNEL_KEY_MAX 6
+int dad_debug_kernel_list(int32_t family, int32_t* out, int32_t capacity, int32_t* needed_out);
 
 /* ------------------------------------------------------------------------------------------------
  * The optimiser step.  Replaces what Trainer.train_step does after loss.backward() (utils/training.py:158-189):

@@ -10,7 +10,7 @@ launches.  "Not reached in this space" is all it claims.  The data-gradient conv
 tests/forward_census.py and are left out here.
 
 Keys of a plan (step_keys):
-  ("wgrad", taps, tile, windowed)            a conv_wgrad instantiation (the domain: dad_debug_wgrad_kernel_exists), and the
+  ("wgrad", taps, tile, windowed)            a conv_wgrad instantiation (the domain: dad_debug_kernel_list, wgrad family), and the
   ("wgrad", taps, tile, windowed, feature)   same with `steady` (a block stages >= 2 chunks: the double-buffered loop), `part`
                                              (a part-filled last chunk behind full ones), `concat_inside` (the boundary of a
                                              channel concat inside one block's staged columns), `edge_m` / `edge_c` (a partly

@@ -174,7 +174,7 @@ static void check_forward_report(const HostModel& m, int mode, int B, const FwdP
               ((fl & 16) != 0) == g.padded && ((fl & 32) != 0) == g.windowed && fl < (1 << kRegFlags),
               "%s mode %d B=%d: flag word %d", op.name.c_str(), mode, B, fl);
         if (!ok) return;
-        CHECK(kernel_registered_f(g.cfg, op.taps, op.stride, fl) &&
+        CHECK(kernel_registered_f(g.cfg, op.taps, op.stride, fl) && family_kernel_exists(FAM_GEMM, {g.cfg, op.taps, op.stride, fl}) &&
               kernel_registered(g.cfg, op.taps, op.stride, op.x3, op.bdir, g.ragged, g.fused, g.padded, g.windowed),
               "%s mode %d B=%d: the report names a kernel that does not exist", op.name.c_str(), mode, B);
         // samples the launch's N tiles have room for against the batch
@@ -220,6 +220,10 @@ static void check_forward_report(const HostModel& m, int mode, int B, const FwdP
         // the instantiation run_conv_cc looks up: conv_ccw by ride_in, conv_cc by big and windowed
         CHECK(small_kernel_exists(op.taps, op.stride, op.ride, o.wide, o.wide ? false : o.big, o.wide ? o.ride_in : false, o.tile_rows, op.Lout > 32),
               "%s B=%d: the report names a small-batch kernel that does not exist", op.name.c_str(), B);
+        // ... by the key of its family, as run_conv_cc builds it (a wide launch of a layer longer than 32 positions has none)
+        CHECK(o.wide ? !(op.Lout > 32) && family_kernel_exists(FAM_CCW, {op.taps, op.stride, op.ride, o.ride_in, o.tile_rows})
+                     : family_kernel_exists(FAM_CC, {op.taps, op.stride, op.ride, o.big, o.tile_rows, op.Lout > 32}),
+              "%s B=%d: no kernel of the small-batch family for the launch's key", op.name.c_str(), B);
     }
 }
 
@@ -246,6 +250,8 @@ static void check_halo8_report(const HostModel& m, int B, const FwdPlan& f, bool
             ++g_halo8_records;
             CHECK(q[DAD_H8_CONV] == l.conv && q[DAD_H8_CFG] == g.cfg && halo8_kernel_exists(g.cfg) && (q[DAD_H8_RIDE] != 0) == g.fused, "%s B=%d: instantiation",
                   op.name.c_str(), B);
+            CHECK(family_kernel_exists(FAM_HALO8, {q[DAD_H8_CFG], q[DAD_H8_RIDE]}), "%s B=%d: conv_halo8_f32 (tile %d, ride %d) does not exist", op.name.c_str(), B,
+                  q[DAD_H8_CFG], q[DAD_H8_RIDE]);
             const int cin0 = op.cin0, cin1 = op.cin1, KC = 32;
             CHECK((cin0 + cin1) % KC == 0 && cin0 % KC == 0 && q[DAD_H8_CHUNKS] == (cin0 + cin1) / KC, "%s B=%d: %d chunks for %d + %d channels", op.name.c_str(), B,
                   q[DAD_H8_CHUNKS], cin0, cin1);
@@ -339,6 +345,9 @@ static void check_backward_steps(const HostModel& m, int B, const TrainScratch& 
                       q[DAD_BS_WG_LAST_CHUNKS] == last, "B=%d step %zu: weight-gradient record (batch split)", B, i);
                 CHECK(std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) != std::end(kWgradTaps) && g.tile >= 0 && g.tile < 4,
                       "B=%d step %zu: conv_wgrad<%d, tile %d> does not exist", B, i, s.taps, g.tile);
+                CHECK(family_kernel_exists(FAM_WGRAD, {q[DAD_BS_WG_TAPS], q[DAD_BS_WG_TILE], q[DAD_BS_WG_WINDOWED]}) &&
+                      wgrad_kernel_exists(s.taps, g.tile, sh.wshift > 0), "B=%d step %zu: no conv_wgrad for the step's key (%d, %d, %d)", B, i, s.taps, g.tile,
+                      (int)(sh.wshift > 0));
                 used = DAD_BS_REC_INTS;
                 break;
             }

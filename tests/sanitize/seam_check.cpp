@@ -225,6 +225,9 @@ static void check_rule() {
                             ++taken;
                             const LaunchGeom& g = f.launches[0].g;
                             CHECK(s.tile0 == (g.cfg == 0) && s.units == (td > 8 ? 2 : 1), "tile / units");
+                            // the instantiation launch_seam looks up, by the key of its family
+                            CHECK(seam_kernel_exists(q.cfg.dim, s.tile0) && family_kernel_exists(FAM_SEAM, {q.cfg.dim, s.tile0}),
+                                  "td %d dim %d H %d B %d: conv_seam_f32<%d, tile0 %d> does not exist", td, dim, H, B, q.cfg.dim, (int)s.tile0);
                             CHECK(s.grid == (unsigned)(((long)B * H + 31) / 32) && s.threads == dad::seam_threads(dim), "grid %u, %d threads", s.grid, s.threads);
                             CHECK(s.lds_bytes == dad::seam_lds_floats(td, dim, H) * sizeof(float) && s.lds_bytes <= dad::kLdsBytes, "LDS %zu", s.lds_bytes);
                             CHECK(s.xswz == find_xswz(q, H, 1, 2, dad::SEAM_KP / 4, 32), "slot shifts");

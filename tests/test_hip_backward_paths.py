@@ -9,7 +9,7 @@ tests/test_hip_forward_paths.py and are not repeated here.
 
 (a) test_matrix_reaches_every_backward_kernel (no device): every case's plan holds the keys the case exists for; the
     conv_wgrad instantiations the matrix launches and NOT_REACHED are disjoint and together are the 40 of
-    dad_debug_wgrad_kernel_exists; every launched instantiation also runs with two or more chunks in a block (the
+    the registry's conv_wgrad family (dad_debug_kernel_list); every launched instantiation also runs with two or more chunks in a block (the
     double-buffered steady state); a part-filled last chunk behind full ones on every tile, partly filled last M and C
     tiles, the transposed conv's swapped roles on every aligned tile windowed and not; the six GroupNorm-backward forms
     (gn_mish_bwd_wave_kernel<1 | 2 | 4 | 8 | 16>, gn_mish_bwd_kernel) each with and without the d temb store, the block form,

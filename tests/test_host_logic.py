@@ -168,14 +168,20 @@ def test_horizon_padding_entry_point():
 
 
 def test_planner_and_kernel_registry_agree():
-    """The planner refuses launches no kernel was compiled for by one predicate (csrc/host_plan.hpp
-    kernel_registered — what the sanitizer harness checks launch plans against), and the library's kernel
-    registry is generated from that predicate: the table must hold an entry wherever it is true over its whole
-    domain and nothing else (round 3: a 3-tap conv under the split-f16 arithmetic was planned onto a kernel that
-    does not exist)."""
+    """The planner refuses launches no kernel was compiled for by one predicate per kernel family (csrc/host_plan.hpp
+    kFamilies: kernel_registered and its like — what the sanitizer harness checks launch plans against), and the
+    library's kernel registry is generated from those predicates: for each of the six families the table must hold an
+    entry wherever the predicate is true over its whole domain and nothing else (round 3: a 3-tap conv under the
+    split-f16 arithmetic was planned onto a kernel that does not exist).  The registry's own list of each family has
+    the family's count of distinct keys."""
+    import ctypes as C
     from dynamics_aware_diffusion_amd import _engine
     lib = _engine.load_library()
     assert lib.dad_debug_kernel_table_consistent() == 1, lib.dad_last_error()
+    counts = {family: len(_engine.kernel_list(family)) for family in _engine.KERNEL_FAMILIES}
+    assert counts == {"gemm": 335, "cc": 18, "ccw": 20, "halo8": 4, "seam": 5, "wgrad": 40}
+    need = C.c_int32()
+    assert lib.dad_debug_kernel_list(len(_engine.KERNEL_FAMILIES), None, 0, C.byref(need)) == -1       # no such family
 
 
 def _pointmaze_cfg():
