@@ -7,6 +7,7 @@ device the calls raise.  torch is used only for device memory and streams.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 from typing import Dict, Mapping, Optional, Sequence
@@ -70,9 +71,6 @@ class DadOptimArgs(C.Structure):
 
 
 OPTIM_MAX_GROUPS = 8
-# DAD_OS_* of include/dad.h: header and record of dad_debug_optim_plan
-OS_HEADER = ("chunk", "chunks", "grid", "partials", "record_ints")
-OS_REC_FIELDS = ("tensor", "first", "first_hi", "count", "block")
 
 
 # name -> (restype, argtypes); also the list of symbols include/dad.h declares.
@@ -154,6 +152,7 @@ ABI = {
     "dad_debug_seam_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "dad_debug_seam_reason": (C.c_char_p, [C.c_int32]),
     "dad_debug_kernel_list": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+    "dad_debug_report_layout": (C.c_char_p, [C.c_int32, C.c_int32]),
     "dad_optim_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "dad_optim_destroy": (None, [C.c_void_p]),
     "dad_optim_step": (C.c_int, [C.c_void_p, C.POINTER(DadOptimTensor), C.c_int32, C.POINTER(DadOptimArgs), C.c_void_p]),
@@ -216,44 +215,84 @@ def _require_device(t: torch.Tensor, name: str) -> None:
 PRECISIONS = {"fp32": 0, "f16x3": 1}      # DAD_PREC_* of include/dad.h
 LOSS_TYPES = {"l1": 1, "l2": 2}           # DAD_LOSS_* of include/dad.h
 TABLES = {"sinusoid": 0, "time_mlp": 1, "blocks": 2}      # DAD_TABLE_* of include/dad.h
-# DAD_OP_TG_* of include/dad.h: the eight modes of time_gemm_kernel, then time_dtemb_kernel
-TIME_GEMM_MODES = ("FWD_H1", "FWD_TEMB", "FWD_ROWS", "BWD_DWK", "BWD_DACT", "BWD_DW3", "BWD_DH1", "BWD_DW1", "DTEMB")
-
-
-# DAD_FP_* of include/dad.h: the records of dad_debug_forward_plan
-FP_REC_FIELDS = ("conv", "sub", "cfg", "taps", "stride", "flags", "kc", "kslices", "gn_npt", "ntiles_n", "mtiles", "part_tile",
-                 "family")
-FP_FAMILIES = ("gemm", "halo8")           # DAD_FP_FAMILY_* of include/dad.h
-FP_CC_FIELDS = ("conv", "taps", "stride", "wide", "ride", "big", "ride_in", "tile_rows", "windowed", "slice_ch", "kslices",
-                "ntiles", "res_kind")
-FP_FINAL_KERNELS = (None, "final_posterior_kernel", "final_cc_kernel")
 FP_FLAGS = ("x3", "bdir", "ragged", "res", "padded", "windowed")      # bits 0..5 of a record's flag word
-# DAD_PP_* of include/dad.h: the fields and forms of dad_debug_project_plan
-PP_FIELDS = ("form", "rows_per_block", "gx", "gy", "lds_bytes", "refused")
-PP_FORMS = ("row1", "row4", "gemm")       # project_kernel<1,16>, project_kernel<4,16>, project_gemm_kernel
-# DAD_SEAM_* of include/dad.h: the fields of dad_debug_seam_plan
-SEAM_FIELDS = ("taken", "reason", "grid", "threads", "lds_bytes", "tile", "units", "spt", "last", "buffers", "dim", "tile0")
-SEAM_DETAIL_FIELDS = SEAM_FIELDS[7:]        # reported by HipEngine.seam_plan(detail=True) only
-SEAM_BUFFERS = ("apart", "dst", "rdst")   # DAD_SEAM_BUF_* of include/dad.h
-# DAD_H8_* of include/dad.h: the records of dad_debug_halo8_plan
-H8_FIELDS = ("conv", "cfg", "ride", "chunks", "src1_chunk", "res", "temb", "per_row", "gn", "wpp", "xcd_gn", "mtiles", "ntiles_n",
-             "part_tile")
+
+# ---------------------------------------------------------------------- plan reports
+# The debug queries return flat int32 vectors whose layouts include/dad.h states once (its *_LIST lists).  Nothing of a
+# layout is written down here: the library hands the lists over as text, and reports are decoded by name.
+@functools.lru_cache(None)
+def report_layouts() -> dict:
+    """Every section of every plan report as the library states it (dad_debug_report_layout: static text, no model, no
+    device), asked on first use: {the constant that holds the section's length: ((constant, name, span), ...)}.
+    Sections are headers, records and the names of the values a field takes."""
+    lib, found = load_library(), {}
+    for report, section in ((r, s) for r in range(64) for s in range(64)):      # (NULL outside the table, which is smaller)
+        text = lib.dad_debug_report_layout(report, section)
+        if text is not None:
+            length, *f = text.decode().split()
+            found[length] = tuple(zip(f[0::3], f[1::3], map(int, f[2::3])))
+    return found
 
 
-KERNEL_FAMILIES = ("gemm", "cc", "ccw", "halo8", "seam", "wgrad")      # DAD_FAMILY_* of include/dad.h
+@functools.lru_cache(None)
+def _fields(section: str):
+    """(((name, offset, span), ...) of the fields a section reports — the reserved ones, "_", left out —, its length)."""
+    at, fields = 0, []
+    for _, name, span in report_layouts()[section]:
+        if name != "_":
+            fields.append((name, at, span))
+        at += span
+    return tuple(fields), at
+
+
+def _names(section: str) -> tuple:
+    """A section's names in order: a record's fields, or the names of a field's values (value = position)."""
+    return tuple(name for name, _, _ in _fields(section)[0])
+
+
+def _decode(section: str, ints, at: int = 0) -> dict:
+    """The ints from `at` on by the names of `section`: an int per field, a list for a field that spans several."""
+    return {name: ints[at + o] if span == 1 else list(ints[at + o:at + o + span]) for name, o, span in _fields(section)[0]}
+
+
+def decode_report(ints, header: str, record):
+    """(header dict, [one dict per record]) of a report's ints.  `header` and `record` name the sections by their length
+    constants; with several kinds of record, `record` is a function (header dict, where a record starts) -> section."""
+    head = _decode(header, ints)
+    k = head.pop("record_ints")
+    recs = []
+    for at in range(_fields(header)[1], len(ints), k):
+        section = record(head, at) if callable(record) else record
+        assert _fields(section)[1] == k and at + k <= len(ints)
+        recs.append(_decode(section, ints, at))
+    return head, recs
+
+
+def _fetch(fn, *args) -> list:
+    """The two calls of every sized report: ask how many ints there are, then fetch them."""
+    lib, need = load_library(), C.c_int32()
+    _check(lib, fn(*args, None, 0, C.byref(need)))
+    out = (C.c_int32 * need.value)()
+    _check(lib, fn(*args, out, need.value, C.byref(need)))
+    return list(out)
+
+
+def __getattr__(name: str):
+    """Value names other modules import, served from the library's lists on first use."""
+    sections = {"TIME_GEMM_MODES": "DAD_OP_TG_MODES", "KERNEL_FAMILIES": "DAD_FAMILIES"}
+    if name in sections:
+        return _names(sections[name])
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def kernel_list(family: str):
     """The keys of one family of instantiated kernels in the library's own registry, the table every launch looks its
     kernel up in (dad_debug_kernel_list), as a set of tuples; host logic only."""
-    lib = load_library()
-    fam = KERNEL_FAMILIES.index(family)
-    need = C.c_int32()
-    _check(lib, lib.dad_debug_kernel_list(fam, None, 0, C.byref(need)))
-    out = (C.c_int32 * need.value)()
-    _check(lib, lib.dad_debug_kernel_list(fam, out, need.value, C.byref(need)))
-    n, ints = out[0], out[1]
-    return {tuple(out[2 + i * ints:2 + (i + 1) * ints]) for i in range(n)}
+    out = _fetch(load_library().dad_debug_kernel_list, _names("DAD_FAMILIES").index(family))
+    head, start = _decode("DAD_KL_HEADER", out), _fields("DAD_KL_HEADER")[1]
+    ints = head["key_ints"]
+    assert len(out) - start == head["kernels"] * ints
+    return {tuple(out[at:at + ints]) for at in range(start, len(out), ints)}
 
 
 def registered_kernels():
@@ -269,17 +308,6 @@ def fullchip_kernels():
     return tuple({(family,) + k for k in kernel_list(family)} for family in ("halo8", "seam"))
 
 
-# DAD_BS_* of include/dad.h: the records of dad_debug_backward_steps, by kind (field 0 is the kind itself)
-BS_KINDS = ("bias", "wgrad", "dgrad", "gn", "resid", "cols")
-BS_FIELDS = {
-    "bias": ("rows", "C"),
-    "wgrad": ("taps", "tile", "windowed", "M", "C0", "C1", "stride", "pad", "Lg", "Lz", "gx", "gy", "ragged", "concat_inside",
-              "edge_m", "edge_c", "swapped", "ksplit", "slab_n4", "samples", "spc", "sps", "chunks", "last_chunks"),
-    "dgrad": ("conv", "sub", "write"),
-    "gn": ("nv", "cpg", "L", "lreal", "cpg_real", "dtemb", "short_pair", "C"),
-    "resid": ("write", "n", "to_x"),
-    "cols": ("C", "off", "ld", "rows", "write"),
-}
 BS_WRITES = ("set", "add", "stage")       # BwdWrite of csrc/host_plan.hpp
 
 
@@ -295,11 +323,11 @@ def projection_plan(state_dim: int, observation_dim: int, action_dim: int, batch
     launch from; host logic only).  Returns ``form`` ("row1", "row4" or "gemm"), ``rows_per_block``, ``grid`` (x, y),
     ``lds_bytes`` and ``refused`` (the call fails: the row does not fit LDS and the GEMM form is not to be had)."""
     lib = load_library()
-    out = (C.c_int32 * len(PP_FIELDS))()
+    out = (C.c_int32 * _fields("DAD_PP_INTS")[1])()
     _check(lib, lib.dad_debug_project_plan(int(state_dim), int(observation_dim), int(action_dim), int(batch), int(horizon),
                                            int(scratch_bytes), int(bool(violation)), out))
-    q = dict(zip(PP_FIELDS, out))
-    q["form"], q["refused"] = PP_FORMS[q["form"]], bool(q["refused"])
+    q = _decode("DAD_PP_INTS", out)
+    q["form"], q["refused"] = _names("DAD_PP_FORMS")[q["form"]], bool(q["refused"])
     q["grid"] = (q.pop("gx"), q.pop("gy"))
     return q
 
@@ -307,21 +335,11 @@ def projection_plan(state_dim: int, observation_dim: int, action_dim: int, batch
 def optim_plan(numel: Sequence[int]) -> dict:
     """The work split of one optimiser step over tensors of these sizes (dad_debug_optim_plan; host logic only):
     chunk size, chunks, grid, partials and one record per chunk, with ``first`` as the whole element index."""
-    lib = load_library()
-    n = len(numel)
-    sizes = (C.c_int64 * max(n, 1))(*[int(v) for v in numel])
-    needed = C.c_int32()
-    _check(lib, lib.dad_debug_optim_plan(sizes, n, None, 0, C.byref(needed)))
-    out = (C.c_int32 * needed.value)()
-    _check(lib, lib.dad_debug_optim_plan(sizes, n, out, needed.value, C.byref(needed)))
-    head = dict(zip(OS_HEADER, out[:len(OS_HEADER)]))
-    k = head.pop("record_ints")
-    assert k == len(OS_REC_FIELDS)
-    recs = []
-    for i in range(head["chunks"]):
-        r = dict(zip(OS_REC_FIELDS, out[len(OS_HEADER) + i * k:len(OS_HEADER) + (i + 1) * k]))
+    sizes = (C.c_int64 * max(len(numel), 1))(*[int(v) for v in numel])
+    head, recs = decode_report(_fetch(load_library().dad_debug_optim_plan, sizes, len(numel)), "DAD_OS_HEADER", "DAD_OS_REC_INTS")
+    assert head["chunks"] == len(recs)
+    for r in recs:
         r["first"] += r.pop("first_hi") << 31
-        recs.append(r)
     head["records"] = recs
     return head
 
@@ -853,14 +871,13 @@ class HipEngine:
         the fields that name the path inside the kernel: ``spt`` (samples of a 32-row tile), ``last`` (samples in the
         last tile), ``buffers`` (which allowed relation final_act has to the buffers the launch writes: "apart", "dst"
         or "rdst"; None when refused) and ``dim`` / ``tile0``: the instantiation conv_seam_f32<dim, tile0>."""
-        out = (C.c_int32 * len(SEAM_FIELDS))()
+        out = (C.c_int32 * _fields("DAD_SEAM_INTS")[1])()
         _check(self.lib, self.lib.dad_debug_seam_plan(self._h, int(batch), int(bool(projection)), out))
-        q = dict(zip(SEAM_FIELDS, out))
-        q["taken"] = bool(q["taken"])
-        q["reason"] = self.lib.dad_debug_seam_reason(q["reason"]).decode()
-        q["buffers"] = SEAM_BUFFERS[q["buffers"]] if q["buffers"] >= 0 else None
-        if not detail:
-            for k in SEAM_DETAIL_FIELDS:
+        q = _decode("DAD_SEAM_INTS", out)
+        q["taken"], q["reason"] = bool(q["taken"]), self.lib.dad_debug_seam_reason(q["reason"]).decode()
+        q["buffers"] = _names("DAD_SEAM_BUFS")[q["buffers"]] if q["buffers"] >= 0 else None
+        if not detail:                     # the fields from ``spt`` on name the path inside the kernel
+            for k in list(q)[list(q).index("spt"):]:
                 del q[k]
         return q
 
@@ -868,14 +885,9 @@ class HipEngine:
         """The conv_halo8_f32 launches (csrc/conv_halo8.hpp) of one evaluation at `batch` under the current debug
         options (dad_debug_halo8_plan: host logic only; ``mode`` 0 / 1 as :meth:`forward_plan`): one dict per launch in
         launch order with the fields of DAD_H8_* — what the kernel makes of the operands the launch hands it."""
-        need = C.c_int32()
-        _check(self.lib, self.lib.dad_debug_halo8_plan(self._h, int(batch), int(mode), None, 0, C.byref(need)))
-        buf = (C.c_int32 * need.value)()
-        _check(self.lib, self.lib.dad_debug_halo8_plan(self._h, int(batch), int(mode), buf, need.value, C.byref(need)))
-        r = list(buf)
-        k = len(H8_FIELDS)
-        assert r[1] == k and len(r) - 2 == r[0] * k
-        return [dict(zip(H8_FIELDS, r[at:at + k])) for at in range(2, len(r), k)]
+        head, recs = decode_report(_fetch(self.lib.dad_debug_halo8_plan, self._h, int(batch), int(mode)), "DAD_H8_HEADER", "DAD_H8_INTS")
+        assert head["records"] == len(recs)
+        return recs
 
     def small_batch_plan(self, batch: int):
         """(conv launches through the consumer-combine kernels, how many of them are the
@@ -890,45 +902,33 @@ class HipEngine:
         (launches whose fullest block stages more than one chunk), ``max_chunks``, ``max_ksplit``, ``part``,
         ``part_multi``, ``windowed``, ``tile`` [4], ``taps_tile`` {(taps, tile): launches}, ``fwd`` / ``dgrad``
         {(conv tile cfg, grid split-K?): launches}, and ``launches``: one dict per weight-gradient launch."""
-        need = C.c_int32()
-        _check(self.lib, self.lib.dad_debug_backward_plan(self._h, int(batch), None, 0, C.byref(need)))
-        buf = (C.c_int32 * need.value)()
-        _check(self.lib, self.lib.dad_debug_backward_plan(self._h, int(batch), buf, need.value, C.byref(need)))
-        r = list(buf)
-        fields = ("taps", "tile", "windowed", "samples", "spc", "sps", "ksplit", "chunks", "last_chunks")
-        assert r[71] == len(fields) and (len(r) - 72) == r[0] * r[71]
-        hist = lambda at: {(cfg, bool(s)): r[at + 2 * cfg + s] for cfg in range(10) for s in (0, 1) if r[at + 2 * cfg + s]}
-        return {
-            "wgrads": r[0], "multi": r[1], "max_chunks": r[2], "max_ksplit": r[3], "part": r[4], "part_multi": r[5],
-            "windowed": r[6], "tile": r[7:11],
-            "taps_tile": {(taps, tile): r[11 + 4 * i + tile] for i, taps in enumerate((1, 3, 4, 5, 7)) for tile in range(4)
-                          if r[11 + 4 * i + tile]},
-            "fwd": hist(31), "dgrad": hist(51),
-            "launches": [dict(zip(fields, r[at:at + len(fields)])) for at in range(72, len(r), len(fields))],
-        }
+        q, recs = decode_report(_fetch(self.lib.dad_debug_backward_plan, self._h, int(batch)), "DAD_BP_HEADER", "DAD_BP_REC_INTS")
+        assert q["wgrads"] == len(recs)
+        tiles = len(q["tile"])
+        q["taps_tile"] = {(taps, tile): n for i, taps in enumerate((1, 3, 4, 5, 7)) for tile in range(tiles)
+                          if (n := q["taps_tile"][tiles * i + tile])}
+        for name in ("fwd", "dgrad"):      # launches per (conv tile cfg, grid split-K?)
+            q[name] = {(i // 2, bool(i % 2)): n for i, n in enumerate(q[name]) if n}
+        q["launches"] = recs
+        return q
 
     def backward_steps(self, batch: int) -> dict:
         """Everything dad_unet_backward replays at `batch` under the current debug options (dad_debug_backward_steps:
         host logic only, as :meth:`backward_plan`).  Returns ``batch``, ``colsums`` (launches, entries, widest),
         ``padcopy`` (the zero-padded horizon's copies run), ``horizon`` / ``real_horizon``, ``dx`` and ``steps``: one
-        dict per step in launch order with ``kind`` (a name of BS_KINDS) and the fields of BS_FIELDS for that kind
-        (DAD_BS_* of include/dad.h); ``write`` is a name of BS_WRITES."""
-        need = C.c_int32()
-        _check(self.lib, self.lib.dad_debug_backward_steps(self._h, int(batch), None, 0, C.byref(need)))
-        buf = (C.c_int32 * need.value)()
-        _check(self.lib, self.lib.dad_debug_backward_steps(self._h, int(batch), buf, need.value, C.byref(need)))
-        r = list(buf)
-        ints = r[1]
-        assert ints == 25 and len(r) - 12 == r[0] * ints
-        steps = []
-        for at in range(12, len(r), ints):
-            kind = BS_KINDS[r[at]]
-            q = dict(zip(BS_FIELDS[kind], r[at + 1:at + ints]), kind=kind)
+        dict per step in launch order with ``kind`` ("bias", "wgrad", "dgrad", "gn", "resid" or "cols": DAD_BS_K_* of
+        include/dad.h) and the fields that kind's list there names (DAD_BS_*_INTS_LIST); ``write`` is a name of BS_WRITES."""
+        kinds, ints = _names("DAD_BS_KINDS"), _fetch(self.lib.dad_debug_backward_steps, self._h, int(batch))
+        head, steps = decode_report(ints, "DAD_BS_HEADER",      # a kind's list is named after it: DAD_BS_WGRAD_INTS
+                                    lambda head, at: f"DAD_BS_{kinds[_decode('DAD_BS_REC_INTS', ints, at)['kind']].upper()}_INTS")
+        assert head["steps"] == len(steps)
+        for q in steps:
+            q["kind"] = kinds[q.pop("kind")]
             if "write" in q:
                 q["write"] = BS_WRITES[q["write"]]
-            steps.append(q)
-        return {"batch": r[2], "colsums": (r[3], r[4], r[5]), "padcopy": bool(r[6]), "horizon": r[7], "real_horizon": r[8],
-                "dx": bool(r[9]), "steps": steps}
+        return {"batch": head["batch"], "colsums": (head["colsums_launches"], head["colsums_entries"], head["colsums_widest"]),
+                "padcopy": bool(head["padcopy"]), "horizon": head["horizon"], "real_horizon": head["real_horizon"],
+                "dx": bool(head["dx"]), "steps": steps}
 
     def objective_plan(self, batch: int) -> dict:
         """The time chain of one fused objective step at `batch` (host logic only, as :meth:`backward_plan`).  Keys as
@@ -936,21 +936,14 @@ class HipEngine:
         ``launches``: one dict per launch in launch order with ``mode`` (a name of TIME_GEMM_MODES), ``M``, ``N``,
         ``K``, ``grid`` (x, y, z), ``chunks`` (32-wide K chunks of a full slice), ``last_chunks``, ``ktail`` (K % 32)
         and ``kslice``."""
-        need = C.c_int32()
-        _check(self.lib, self.lib.dad_debug_objective_plan(self._h, int(batch), None, 0, C.byref(need)))
-        buf = (C.c_int32 * need.value)()
-        _check(self.lib, self.lib.dad_debug_objective_plan(self._h, int(batch), buf, need.value, C.byref(need)))
-        r = list(buf)
-        fields = ("mode", "M", "N", "K", "gx", "gy", "gz", "chunks", "last_chunks", "ktail", "kslice")
-        assert r[6] == len(fields) and (len(r) - 8) == r[7] * r[6]
-        launches = []
-        for at in range(8, len(r), len(fields)):
-            q = dict(zip(fields, r[at:at + len(fields)]))
-            q["mode"] = TIME_GEMM_MODES[q["mode"]]
+        head, launches = decode_report(_fetch(self.lib.dad_debug_objective_plan, self._h, int(batch)), "DAD_OP_HEADER", "DAD_OP_REC_INTS")
+        assert head["launches"] == len(launches)
+        modes = _names("DAD_OP_TG_MODES")
+        for q in launches:
+            q["mode"] = modes[q["mode"]]
             q["grid"] = (q.pop("gx"), q.pop("gy"), q.pop("gz"))
-            launches.append(q)
-        return {"loss_blocks": r[0], "kslices": r[1], "kslice": r[2], "temb_width": r[3], "blocks": r[4], "n": r[5],
-                "launches": launches}
+        head["launches"] = launches
+        return head
 
     def forward_plan(self, batch: int, mode: int = 0) -> dict:
         """What one evaluation launches at `batch` under the current debug options (dad_debug_forward_plan: host logic
@@ -962,27 +955,22 @@ class HipEngine:
         of DAD_FP_CC_*; each has ``key``, the instantiation it runs: ("gemm", cfg, taps, stride, flags),
         ("halo8", cfg, ride) — conv_halo8_f32 on tile cfg —, ("cc", taps, stride, ride, big, rows, windowed) or
         ("ccw", taps, stride, ride, ride_in, rows)."""
-        need = C.c_int32()
-        _check(self.lib, self.lib.dad_debug_forward_plan(self._h, int(batch), int(mode), None, 0, C.byref(need)))
-        buf = (C.c_int32 * need.value)()
-        _check(self.lib, self.lib.dad_debug_forward_plan(self._h, int(batch), int(mode), buf, need.value, C.byref(need)))
-        r = list(buf)
-        small = bool(r[2])
-        fields = FP_CC_FIELDS if small else FP_REC_FIELDS
-        assert r[4] == len(fields) and len(r) - 8 == r[3] * r[4]
-        launches = []
-        for at in range(8, len(r), len(fields)):
-            q = dict(zip(fields, r[at:at + len(fields)]))
-            if not small and FP_FAMILIES[q["family"]] == "halo8":
-                q["key"] = ("halo8", q["cfg"], (q["flags"] >> 3) & 1)
+        head, launches = decode_report(_fetch(self.lib.dad_debug_forward_plan, self._h, int(batch), int(mode)), "DAD_FP_HEADER",
+                                       lambda head, at: "DAD_FP_CC_INTS" if head["small"] else "DAD_FP_REC_INTS")
+        assert head["records"] == len(launches)
+        small, families = bool(head["small"]), _names("DAD_FP_FAMILIES")
+        for q in launches:
+            if not small and families[q["family"]] == "halo8":
+                q["key"] = ("halo8", q["cfg"], (q["flags"] >> FP_FLAGS.index("res")) & 1)
             elif not small:
                 q["key"] = ("gemm", q["cfg"], q["taps"], q["stride"], q["flags"])
             elif q["wide"]:
                 q["key"] = ("ccw", q["taps"], q["stride"], q["ride"], q["ride_in"], q["tile_rows"])
             else:
                 q["key"] = ("cc", q["taps"], q["stride"], q["ride"], q["big"], q["tile_rows"], q["windowed"])
-            launches.append(q)
-        return {"mode": r[0], "batch": r[1], "small": small, "final": (r[5], r[6], FP_FINAL_KERNELS[r[7]]), "launches": launches}
+        final = _names("DAD_FP_FINALS")[head["final_kernel"]]
+        return {"mode": head["mode"], "batch": head["batch"], "small": small,
+                "final": (head["final_gx"], head["final_gy"], None if final == "none" else final), "launches": launches}
 
     def mish(self, x: torch.Tensor) -> torch.Tensor:
         """The conv epilogue's Mish applied to a device tensor (test hook)."""

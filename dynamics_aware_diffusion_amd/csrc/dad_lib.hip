@@ -1531,6 +1531,23 @@ dad::ObjectiveParams objective_params(const dad_model* m, const ObjectiveLayout&
     return q;
 }
 
+// How every plan report leaves: its length in *needed_out, min(capacity, length) ints in `out`.
+int copy_report(const std::vector<int32_t>& r, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (needed_out) *needed_out = (int32_t)r.size();
+    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
+    return DAD_OK;
+}
+// A report of the training step: needs a backward plan; a batch the pass (or the objective) refuses is refused here too.
+int training_report(const dad_model* m, int32_t batch, int (*report)(const HostModel&, int, std::vector<int32_t>&), int32_t* out,
+                    int32_t capacity, int32_t* needed_out) {
+    if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
+    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
+    std::vector<int32_t> r;
+    const int rc = report(*m, batch, r);
+    return rc != DAD_OK ? rc : copy_report(r, out, capacity, needed_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1691,16 +1708,17 @@ int dad_debug_kernel_table_consistent(void) {
 int dad_debug_kernel_list(int32_t family, int32_t* out, int32_t capacity, int32_t* needed_out) {
     if (family < 0 || family >= kNumFamilies || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
     const int axes = kFamilies[family].axes;
-    std::vector<int32_t> r = {0, axes};
+    std::vector<int32_t> r(DAD_KL_HEADER, 0);
+    r[DAD_KL_KEY_INTS] = axes;
     for (const KernelEntry& e : kernel_table()) {
         if ((int)(e.key >> (8 * kMaxKeyInts)) != family) continue;
         for (int a = 0; a < axes; ++a) r.push_back((int32_t)(e.key >> (8 * (kMaxKeyInts - 1 - a)) & 0xff));
-        ++r[0];
+        ++r[DAD_KL_KERNELS];
     }
-    if (needed_out) *needed_out = (int32_t)r.size();
-    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
-    return DAD_OK;
+    return copy_report(r, out, capacity, needed_out);
 }
+
+const char* dad_debug_report_layout(int32_t report, int32_t section) { return report_layout(report, section); }
 
 #ifdef DAD_WG_STAMPS
 extern "C" int dad_debug_wgrad_stamps(unsigned long long* host32) {
@@ -1792,39 +1810,15 @@ int dad_debug_small_batch_plan(dad_model* m, int32_t batch, int32_t* launches_ou
 }
 
 int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
-    if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
-    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
-    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
-    std::vector<int32_t> r;
-    const int rc = backward_plan_report(*m, batch, r);      // (a batch the backward pass refuses is refused here too)
-    if (rc != DAD_OK) return rc;
-    if (needed_out) *needed_out = (int32_t)r.size();
-    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
-    return DAD_OK;
+    return training_report(m, batch, backward_plan_report, out, capacity, needed_out);
 }
 
 int dad_debug_backward_steps(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
-    if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
-    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
-    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
-    std::vector<int32_t> r;
-    const int rc = backward_steps_report(*m, batch, r);     // (a batch the backward pass refuses is refused here too)
-    if (rc != DAD_OK) return rc;
-    if (needed_out) *needed_out = (int32_t)r.size();
-    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
-    return DAD_OK;
+    return training_report(m, batch, backward_steps_report, out, capacity, needed_out);
 }
 
 int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
-    if (!m || batch <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
-    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
-    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
-    std::vector<int32_t> r;
-    const int rc = objective_plan_report(*m, batch, r);     // (a batch the objective refuses is refused here too)
-    if (rc != DAD_OK) return rc;
-    if (needed_out) *needed_out = (int32_t)r.size();
-    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
-    return DAD_OK;
+    return training_report(m, batch, objective_plan_report, out, capacity, needed_out);
 }
 
 int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out) {
@@ -1833,10 +1827,7 @@ int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* o
     if (mode == 3 && m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
     std::vector<int32_t> r;
     const int rc = forward_plan_report(*m, batch, mode, r);     // (a batch the call refuses is refused here too)
-    if (rc != DAD_OK) return rc;
-    if (needed_out) *needed_out = (int32_t)r.size();
-    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
-    return DAD_OK;
+    return rc != DAD_OK ? rc : copy_report(r, out, capacity, needed_out);
 }
 
 int dad_debug_halo8_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out) {
@@ -1846,47 +1837,19 @@ int dad_debug_halo8_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out
     if (rc != DAD_OK) return rc;
     std::vector<int32_t> r;
     halo8_plan_encode(*m, f, mode == 1, r);
-    if (needed_out) *needed_out = (int32_t)r.size();
-    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
-    return DAD_OK;
+    return copy_report(r, out, capacity, needed_out);
 }
 
 int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
                            size_t scratch_bytes, int32_t violation, int32_t* out) {
     if (!out || state_dim <= 0 || observation_dim < state_dim || action_dim <= 0 || batch <= 0 || horizon <= 0)
         return fail(DAD_E_INVALID, "bad argument");
-    const long D = (long)(horizon + 1) * state_dim + (long)horizon * action_dim;
-    if (D > INT32_MAX / 64) return fail(DAD_E_INVALID, "projection dimension D=%ld too large", D);
-    const size_t x_bytes = (size_t)batch * horizon * (observation_dim + action_dim) * sizeof(float);
-    const ProjectPlan q = plan_project((int)D, batch, x_bytes, scratch_bytes, violation != 0);
-    out[DAD_PP_FORM] = q.form;
-    out[DAD_PP_ROWS_PER_BLOCK] = q.rows_per_block;
-    out[DAD_PP_GX] = (int32_t)q.gx;
-    out[DAD_PP_GY] = (int32_t)q.gy;
-    out[DAD_PP_LDS_BYTES] = (int32_t)std::min<size_t>(q.lds_bytes, INT32_MAX);
-    out[DAD_PP_REFUSED] = q.refused;
-    return DAD_OK;
+    return project_plan_report(state_dim, observation_dim, action_dim, batch, horizon, scratch_bytes, violation != 0, out);
 }
 
 int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out) {
     if (!m || !out || batch <= 0) return fail(DAD_E_INVALID, "bad argument");
-    FwdPlan f;
-    const int rc = plan_forward(*m, false, batch, true, f);      // (a batch the loop refuses is refused here too)
-    if (rc != DAD_OK) return rc;
-    const SeamPlan s = plan_seam(*m, f, projection != 0);
-    out[DAD_SEAM_TAKEN] = s.taken();
-    out[DAD_SEAM_REASON] = s.why;
-    out[DAD_SEAM_GRID] = s.taken() ? (int32_t)s.grid : 0;
-    out[DAD_SEAM_THREADS] = s.taken() ? s.threads : 0;
-    out[DAD_SEAM_LDS_BYTES] = s.taken() ? (int32_t)s.lds_bytes : 0;
-    out[DAD_SEAM_TILE] = s.taken() ? s.cfg : -1;
-    out[DAD_SEAM_UNITS] = s.taken() ? s.units : 0;
-    out[DAD_SEAM_SPT] = s.taken() ? s.spt : 0;
-    out[DAD_SEAM_LAST] = s.taken() ? s.last : 0;
-    out[DAD_SEAM_BUFFERS] = s.taken() ? s.buffers : -1;
-    out[DAD_SEAM_DIM] = s.taken() ? s.dim : 0;
-    out[DAD_SEAM_TILE0] = s.taken() ? (int32_t)s.tile0 : -1;
-    return DAD_OK;
+    return seam_plan_report(*m, batch, projection != 0, out);
 }
 
 const char* dad_debug_seam_reason(int32_t reason) { return seam_reason(reason); }
@@ -2067,10 +2030,7 @@ int dad_debug_optim_plan(const int64_t* numel, int32_t n, int32_t* out, int32_t 
     if (!numel || n <= 0 || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
     std::vector<int32_t> r;
     const int rc = optim_plan_report(numel, n, r);
-    if (rc != DAD_OK) return rc;
-    if (needed_out) *needed_out = (int32_t)r.size();
-    std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), (size_t)capacity), out);
-    return DAD_OK;
+    return rc != DAD_OK ? rc : copy_report(r, out, capacity, needed_out);
 }
 
 }  // extern "C"

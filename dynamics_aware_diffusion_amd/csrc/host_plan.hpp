@@ -6,7 +6,8 @@
 // of steps of build_backward_plan with its per-batch geometry, train_scratch), and the workspace layout of the fused
 // training objective behind both (objective_layout).  The entry points of dad_lib.hip
 // build those two once per call, refuse before their first launch, and only replay them; the size queries and
-// the plan report read the same descriptions.  Plain C++17, no HIP: dad_lib.hip includes it for the product,
+// the plan reports (csrc/plan_report.hpp, which writes them down and decides nothing) read the same descriptions.
+// Plain C++17, no HIP: dad_lib.hip includes it for the product,
 // tests/sanitize/host_check.cpp compiles it host-only under -fsanitize=address,undefined.
 #pragma once
 #include <algorithm>
@@ -1906,148 +1907,12 @@ inline int objective_layout(const HostModel& m, int B, ObjectiveLayout& o) {
     return rc;
 }
 
-// dad_debug_backward_plan: which kernels one training step takes at batch B (layout: include/dad.h, DAD_BP_*),
-// read from what dad_unet_forward_train and dad_unet_backward replay: plan_forward of the training plan, train_scratch.
-inline int backward_plan_report(const HostModel& m, int B, std::vector<int32_t>& r) {
-    TrainScratch ts;
-    FwdPlan fwd;
-    plan_forward(m, true, B, false, fwd);
-    const int rc = train_scratch(m, B, ts);
-    r.assign(DAD_BP_HEADER, 0);
-    r[DAD_BP_RECORD_INTS] = DAD_BP_REC_INTS;
-    size_t nw = 0;
-    auto conv = [&](const LaunchGeom& g, int at) { if (g.cfg >= 0) ++r[at + 2 * g.cfg + (g.split.kslices > 1 ? 1 : 0)]; };
-    for (const FwdLaunch& l : fwd.launches) conv(l.g, DAD_BP_FWD);
-    for (const TrainScratch::Dgrad& d : ts.dgrads) conv(d.g, DAD_BP_DGRAD);
-    for (const BwdStep& s : m.bsteps) {
-        if (s.kind != BK_WGRAD) continue;
-        const WgradShape& sh = ts.wgrads[nw].sh;
-        const WgradGeom& g = ts.wgrads[nw++].g;
-        const int fullest = (std::min(g.sps, sh.B) + g.spc - 1) / g.spc;
-        const int last = (sh.B - (g.ksplit - 1) * g.sps + g.spc - 1) / g.spc;
-        const bool part = sh.B % g.spc != 0;
-        const int ti = (int)(std::find(std::begin(kWgradTaps), std::end(kWgradTaps), s.taps) - std::begin(kWgradTaps));
-        ++r[DAD_BP_WGRADS];
-        r[DAD_BP_MULTI] += fullest > 1;
-        r[DAD_BP_MAX_CHUNKS] = std::max(r[DAD_BP_MAX_CHUNKS], fullest);
-        r[DAD_BP_MAX_KSPLIT] = std::max(r[DAD_BP_MAX_KSPLIT], g.ksplit);
-        r[DAD_BP_PART] += part;
-        r[DAD_BP_PART_MULTI] += part && last > 1;
-        r[DAD_BP_WINDOWED] += sh.wshift > 0;
-        ++r[DAD_BP_TILE + g.tile];
-        if (ti < (int)std::size(kWgradTaps)) ++r[DAD_BP_TAPS_TILE + 4 * ti + g.tile];
-        const int32_t rec[DAD_BP_REC_INTS] = {s.taps, g.tile, sh.wshift > 0, sh.B, g.spc, g.sps, g.ksplit, fullest, last};
-        r.insert(r.end(), rec, rec + DAD_BP_REC_INTS);
-    }
-    return rc;
-}
-
 // What a BK_GN step hands gn_mish_bwd_kernel / gn_mish_bwd_wave_kernel besides its pointers: read from the forward conv
 // the step belongs to.  dad_unet_backward fills GnBwdParams from it, backward_steps_encode writes it down.
 struct GnBwdShape { int C, L, cpg, lreal, cpg_real; bool dtemb; };
 inline GnBwdShape gn_bwd_shape(const ConvOp& f) { return {f.cout, f.Lout, f.cout / 8, f.lreal, f.gn_real, f.temb_off >= 0}; }
 // The col_sums_many_kernel launches that end a pass: bsums in order, at most dad::COLS_MAX per launch.
 inline int col_sums_launches(const HostModel& m) { return (int)((m.bsums.size() + dad::COLS_MAX - 1) / dad::COLS_MAX); }
-
-// dad_debug_backward_steps: everything dad_unet_backward replays at batch B, step by step (layout: include/dad.h,
-// DAD_BS_*).  backward_steps_encode writes down m.bsteps / m.bsums with the geometry `ts` (train_scratch) the entry
-// point launches from and decides nothing; backward_steps_report plans the pass as the entry point does and encodes it.
-inline void backward_steps_encode(const HostModel& m, int B, const TrainScratch& ts, std::vector<int32_t>& r) {
-    const int H = m.cfg.horizon, Hr = traj_horizon(m);
-    r.assign(DAD_BS_HEADER, 0);
-    r[DAD_BS_RECORD_INTS] = DAD_BS_REC_INTS;
-    r[DAD_BS_BATCH] = B;
-    r[DAD_BS_COLSUMS_LAUNCHES] = col_sums_launches(m);
-    r[DAD_BS_COLSUMS_ENTRIES] = (int32_t)m.bsums.size();
-    for (const BwdSum& q : m.bsums) r[DAD_BS_COLSUMS_WIDEST] = std::max(r[DAD_BS_COLSUMS_WIDEST], (int32_t)q.C);
-    r[DAD_BS_PADCOPY] = Hr != H;
-    r[DAD_BS_HORIZON] = H;
-    r[DAD_BS_REAL_HORIZON] = Hr;
-    r[DAD_BS_DX] = m.bdx;
-    size_t nw = 0;
-    for (const BwdStep& s : m.bsteps) {
-        int32_t rec[DAD_BS_REC_INTS] = {0};
-        rec[DAD_BS_KIND] = (int32_t)s.kind;
-        switch (s.kind) {
-            case BK_BIAS:
-                rec[DAD_BS_BIAS_ROWS] = s.rows; rec[DAD_BS_BIAS_C] = s.C;
-                break;
-            case BK_WGRAD: {
-                if (nw >= ts.wgrads.size()) break;
-                const WgradShape& sh = ts.wgrads[nw].sh;
-                const WgradGeom& g = ts.wgrads[nw++].g;
-                const int Ctot = s.C0 + s.C1, wm = 32 * g.tm, wn = 32 * g.tn;
-                const long numel = (long)s.M * Ctot * s.taps;
-                rec[DAD_BS_WG_TAPS] = s.taps; rec[DAD_BS_WG_TILE] = g.tile; rec[DAD_BS_WG_WINDOWED] = sh.wshift > 0;
-                rec[DAD_BS_WG_M] = s.M; rec[DAD_BS_WG_C0] = s.C0; rec[DAD_BS_WG_C1] = s.C1;
-                rec[DAD_BS_WG_STRIDE] = s.stride; rec[DAD_BS_WG_PAD] = s.pad; rec[DAD_BS_WG_LG] = sh.Lg; rec[DAD_BS_WG_LZ] = sh.Lz;
-                rec[DAD_BS_WG_GX] = (int32_t)g.gx; rec[DAD_BS_WG_GY] = (int32_t)g.gy;
-                rec[DAD_BS_WG_RAGGED] = g.tile == 3;
-                rec[DAD_BS_WG_CONCAT_INSIDE] = s.C1 > 0 && s.C0 % wn != 0;
-                rec[DAD_BS_WG_EDGE_M] = s.M % wm != 0;
-                rec[DAD_BS_WG_EDGE_C] = Ctot % wn != 0;
-                rec[DAD_BS_WG_SWAPPED] = s.in.sp == BSP_ACT || s.in.sp == BSP_X;
-                rec[DAD_BS_WG_KSPLIT] = g.ksplit;
-                rec[DAD_BS_WG_SLAB_N4] = g.ksplit > 1 ? (int32_t)(numel / 4) : 0;
-                rec[DAD_BS_WG_SAMPLES] = sh.B; rec[DAD_BS_WG_SPC] = g.spc; rec[DAD_BS_WG_SPS] = g.sps;
-                rec[DAD_BS_WG_CHUNKS] = (std::min(g.sps, sh.B) + g.spc - 1) / g.spc;
-                rec[DAD_BS_WG_LAST_CHUNKS] = (sh.B - (g.ksplit - 1) * g.sps + g.spc - 1) / g.spc;
-                break;
-            }
-            case BK_DGRAD:
-                rec[DAD_BS_DG_CONV] = s.conv; rec[DAD_BS_DG_SUB] = s.sub; rec[DAD_BS_DG_WRITE] = (int32_t)s.write;
-                break;
-            case BK_GN: {
-                const GnBwdShape q = gn_bwd_shape(m.tplan.convs[s.conv]);
-                rec[DAD_BS_GN_NV] = s.nv; rec[DAD_BS_GN_CPG] = q.cpg; rec[DAD_BS_GN_L] = q.L; rec[DAD_BS_GN_LREAL] = q.lreal;
-                rec[DAD_BS_GN_CPG_REAL] = q.cpg_real; rec[DAD_BS_GN_DTEMB] = q.dtemb; rec[DAD_BS_GN_C] = q.C;
-                rec[DAD_BS_GN_SHORT_PAIR] = q.cpg / 4 * q.L < 64;
-                break;
-            }
-            case BK_RESID:
-                rec[DAD_BS_RS_WRITE] = (int32_t)s.write; rec[DAD_BS_RS_N] = (int32_t)std::min<long>(s.n, INT32_MAX);
-                rec[DAD_BS_RS_TO_X] = s.out.sp == BSP_DX;
-                break;
-            case BK_COLS:
-                rec[DAD_BS_CL_C] = s.C; rec[DAD_BS_CL_OFF] = s.off; rec[DAD_BS_CL_LD] = s.ld; rec[DAD_BS_CL_ROWS] = s.rows;
-                rec[DAD_BS_CL_WRITE] = (int32_t)s.write;
-                break;
-        }
-        r.insert(r.end(), rec, rec + DAD_BS_REC_INTS);
-        ++r[DAD_BS_STEPS];
-    }
-}
-inline int backward_steps_report(const HostModel& m, int B, std::vector<int32_t>& r) {
-    TrainScratch ts;
-    const int rc = train_scratch(m, B, ts);
-    backward_steps_encode(m, B, ts, r);
-    return rc;
-}
-
-// dad_debug_objective_plan: the time chain of one fused objective step at batch B (layout: include/dad.h, DAD_OP_*),
-// read from the list dad_train_objective_forward / _backward replay (ObjectivePlan::time).
-inline int objective_plan_report(const HostModel& m, int B, std::vector<int32_t>& r) {
-    ObjectivePlan p;
-    const int rc = objective_plan(m, B, true, p);
-    const long n = (long)B * traj_horizon(m) * m.cfg.transition_dim;
-    r.assign(DAD_OP_HEADER, 0);
-    r[DAD_OP_LOSS_BLOCKS] = p.o.loss_blocks;
-    r[DAD_OP_KSLICES] = p.o.kslices;
-    r[DAD_OP_KSLICE] = p.o.kslice;
-    r[DAD_OP_TEMB_WIDTH] = m.tplan.temb_width;
-    r[DAD_OP_BLOCKS] = (int32_t)time_block_list(m).size();
-    r[DAD_OP_N] = (int32_t)std::min<long>(n, INT32_MAX);
-    r[DAD_OP_RECORD_INTS] = DAD_OP_REC_INTS;
-    r[DAD_OP_LAUNCHES] = (int32_t)p.time.size();
-    for (const TimeLaunch& l : p.time) {
-        const bool gemm = l.mode != DAD_OP_TG_DTEMB;
-        const int full = std::min(l.kslice, l.K), last = l.K - (l.kslices - 1) * l.kslice;
-        const int32_t rec[DAD_OP_REC_INTS] = {l.mode, l.M, l.N, l.K, (int32_t)l.gx(), (int32_t)l.gy(), (int32_t)l.gz(),
-                                              gemm ? (full + 31) / 32 : 0, gemm ? (last + 31) / 32 : 0, gemm ? l.K % 32 : 0, l.kslice};
-        r.insert(r.end(), rec, rec + DAD_OP_REC_INTS);
-    }
-    return rc;
-}
 
 // The small-batch kernels of one launch, whichever of the two families it takes: conv_cc has no `ride_in` form (a
 // consumer of ride slabs runs the same instantiation), conv_ccw (`wide`) neither `big` nor `windowed`.
@@ -2151,83 +2016,9 @@ static_assert(count_family(FAM_HALO8) == 4 && kFamilies[FAM_HALO8].count == 4, "
 static_assert(count_family(FAM_SEAM) == 5 && kFamilies[FAM_SEAM].count == 5, "the set of conv_seam_f32 kernels changed: seam_kernel_exists");
 static_assert(count_family(FAM_WGRAD) == 40 && kFamilies[FAM_WGRAD].count == 40, "the set of conv_wgrad kernels changed: wgrad_kernel_exists");
 
-// dad_debug_forward_plan: what one forward evaluation (modes 0 .. 2) or the data-gradient half of one backward pass
-// (mode 3) launches at a batch (layout: include/dad.h, DAD_FP_*).  forward_plan_encode writes down a description the
-// entry points replay — `f`: plan_forward's (modes 0 .. 2), `ts`: train_scratch's (mode 3) — and decides nothing;
-// forward_plan_report plans the call the mode names, as its entry point does, and encodes that.
+// The flag word of kernel_registered_f for one launch: with (cfg, taps, stride) it names the conv_gemm_f32 instantiation.
 inline int32_t launch_flags(const ConvOp& op, const LaunchGeom& g) {
     return (op.x3 ? 1 : 0) | (op.bdir ? 2 : 0) | (g.ragged ? 4 : 0) | (g.fused ? 8 : 0) | (g.padded ? 16 : 0) | (g.windowed ? 32 : 0);
-}
-inline void forward_plan_encode(const HostModel& m, int mode, int batch, const FwdPlan* f, const TrainScratch* ts,
-                                std::vector<int32_t>& r) {
-    r.assign(DAD_FP_HEADER, 0);
-    r[DAD_FP_MODE] = mode;
-    r[DAD_FP_BATCH] = batch;
-    r[DAD_FP_FINAL_KERNEL] = DAD_FP_FINAL_NONE;
-    auto conv = [&](int index, int sub, const ConvOp& op, const LaunchGeom& g) {
-        const int bn = g.cfg >= 0 ? kTiles[g.cfg].BN : 0;
-        const bool part = g.cfg >= 0 && op.Lout <= bn && batch % (bn / op.Lout) != 0;
-        const int32_t rec[DAD_FP_REC_INTS] = {index, sub, g.cfg, op.taps, op.stride, launch_flags(op, g), g.kc, g.split.kslices,
-                                              g.gn_npt, g.ntiles_n, g.mtiles, part, g.halo8 ? DAD_FP_FAMILY_HALO8 : DAD_FP_FAMILY_GEMM};
-        r.insert(r.end(), rec, rec + DAD_FP_REC_INTS);
-        ++r[DAD_FP_RECORDS];
-    };
-    r[DAD_FP_RECORD_INTS] = DAD_FP_REC_INTS;
-    if (mode == 3) {
-        size_t nd = 0;
-        for (const BwdStep& s : m.bsteps)
-            if (s.kind == BK_DGRAD && nd < ts->dgrads.size()) conv(s.conv, s.sub, bwd_op(m, s), ts->dgrads[nd++].g);
-        return;
-    }
-    const Plan& plan = f->train ? m.tplan : m.plan;
-    r[DAD_FP_FINAL_GX] = (int32_t)f->final_gx;
-    r[DAD_FP_FINAL_GY] = (int32_t)f->final_gy;
-    r[DAD_FP_FINAL_KERNEL] = f->cc.ok ? DAD_FP_FINAL_CC : DAD_FP_FINAL_POSTERIOR;
-    if (!f->cc.ok) {
-        for (const FwdLaunch& l : f->launches) conv(l.conv, 0, plan.convs[l.conv], l.g);
-        return;
-    }
-    r[DAD_FP_SMALL] = 1;
-    r[DAD_FP_RECORD_INTS] = DAD_FP_CC_INTS;
-    for (size_t i = 0; i < f->cc.ops.size(); ++i) {
-        const CcOp& o = f->cc.ops[i];
-        if (!o.launched) continue;
-        const ConvOp& op = plan.convs[i];
-        const int32_t rec[DAD_FP_CC_INTS] = {(int32_t)i, op.taps, op.stride, o.wide, op.ride, o.big, o.ride_in, o.tile_rows,
-                                             op.Lout > 32, o.slice_ch, o.kslices, o.ntiles, o.res_kind};
-        r.insert(r.end(), rec, rec + DAD_FP_CC_INTS);
-        ++r[DAD_FP_RECORDS];
-    }
-}
-inline int forward_plan_report(const HostModel& m, int batch, int mode, std::vector<int32_t>& r) {
-    FwdPlan f;
-    TrainScratch ts;
-    const int rc = mode == 3 ? train_scratch(m, batch, ts) : plan_forward(m, mode == 2, batch, mode == 0, f);
-    forward_plan_encode(m, mode, batch, &f, &ts, r);
-    return rc;
-}
-// dad_debug_halo8_plan: the conv_halo8_f32 launches of `f` (plan_forward on m.plan, modes 0 / 1) with what the kernel
-// makes of the ConvParams that conv_params / conv_io of dad_lib.hip fill from the same ConvOp and LaunchGeom (layout:
-// include/dad.h, DAD_H8_*).  `rows`: the evaluation indexes its time embedding per sample (dad_unet_forward_rows).
-inline void halo8_plan_encode(const HostModel& m, const FwdPlan& f, bool rows, std::vector<int32_t>& r) {
-    r.assign(DAD_H8_HEADER, 0);
-    r[1] = DAD_H8_INTS;
-    if (f.train || f.cc.ok) return;
-    for (const FwdLaunch& l : f.launches) {
-        if (!l.g.halo8) continue;
-        const ConvOp& op = m.plan.convs[l.conv];
-        const LaunchGeom& g = l.g;
-        const TileCfg& t = kTiles[g.cfg];
-        const bool gn = !op.norm.empty() && g.gn_npt == 0;
-        const bool temb = op.temb_off >= 0;
-        // waves per pair: the kernel's own `wpp` is lpp >> 6, 0 for a pair inside one wave; the report says 1 there
-        const int lpp = gn ? dad::halo8_lanes_per_pair(t.BM, g.threads, op.cout / 8) : 0;
-        const int32_t rec[DAD_H8_INTS] = {l.conv, g.cfg, g.fused, (op.cin0 + op.cin1) / 32, op.src1 >= 0 ? op.cin0 / 32 : -1,
-                                          op.res == -2 || op.res >= 0, temb, rows && temb, gn, gn ? std::max(1, lpp >> 6) : 0,
-                                          g.xcd_gn, g.mtiles, g.ntiles_n, f.batch % (t.BN / op.Lout) != 0};
-        r.insert(r.end(), rec, rec + DAD_H8_INTS);
-        ++r[0];
-    }
 }
 
 // Bytes the parameter arena must hold: the parameter copies, the per-timestep tables, the zero row of the
@@ -2298,32 +2089,5 @@ inline int optim_plan(const int64_t* numel, int n, OptimPlan& p) {
     return DAD_OK;
 }
 
-// dad_debug_optim_plan: the plan above written down chunk by chunk (layout: include/dad.h, DAD_OS_*), by walking
-// the blocks with the two functions the kernels walk them with.
-inline int optim_plan_report(const int64_t* numel, int n, std::vector<int32_t>& r) {
-    OptimPlan p;
-    const int rc = optim_plan(numel, n, p);
-    if (rc != DAD_OK) return rc;
-    r.assign(DAD_OS_HEADER, 0);
-    r[DAD_OS_CHUNK] = p.g.chunk;
-    r[DAD_OS_CHUNKS] = p.g.nchunks;
-    r[DAD_OS_GRID] = p.g.grid;
-    r[DAD_OS_PARTIALS] = p.g.grid;
-    r[DAD_OS_RECORD_INTS] = DAD_OS_REC_INTS;
-    for (int b = 0; b < p.g.grid; ++b) {
-        int lo, hi;
-        optim_block_chunks(p.g, b, lo, hi);
-        int t = (int)(std::upper_bound(p.first.begin(), p.first.end(), lo) - p.first.begin()) - 1;
-        for (int c = lo; c < hi; ++c) {
-            while (c >= p.first[(size_t)t + 1]) ++t;
-            int64_t first;
-            int32_t count;
-            optim_chunk_span(p.g, c, p.first[(size_t)t], numel[t], first, count);
-            const int32_t rec[DAD_OS_REC_INTS] = {t, (int32_t)(first & 0x7fffffff), (int32_t)(first >> 31), count, b};
-            r.insert(r.end(), rec, rec + DAD_OS_REC_INTS);
-        }
-    }
-    return DAD_OK;
-}
-
 }  // namespace dadhost
+#include "plan_report.hpp"      // the reports travel with the planner: last, since they read everything above

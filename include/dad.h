@@ -371,192 +371,181 @@ int dad_debug_kernel_table_consistent(void);
  * batch runs the batch-256 kernels; wide_out = how many of them are the streamed-weight form for
  * wide layers (csrc/conv_ccw.hpp). */
 int dad_debug_small_batch_plan(dad_model* m, int32_t batch, int32_t* launches_out, int32_t* wide_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Plan reports: host-side queries (no device work) that carry the planner's decisions out as flat int32 vectors.  A
+ * sized report writes min(capacity, *needed_out) values to `out`: its header, then its records in launch order.
+ * Every section of a report — header, record, one kind of record — is stated ONCE, as a list LENGTH_LIST(F) of
+ *   F(CONSTANT, the name the Python binding gives the field, ints the field spans, "what it holds")
+ * named after the constant LENGTH that holds the section's length.  DAD_LAYOUT(LENGTH, first) makes the constants:
+ * each field's offset (the spans before it, counted from `first`) and LENGTH, where the section ends.  A field named
+ * `_` is reserved: 0, not reported.  The values a field can take are lists of the same form: value = position.
+ * dad_debug_report_layout returns the lists as text, all the binding knows of a layout: a new field costs its line
+ * here and one named write in the encoder (csrc/plan_report.hpp). */
+#define DAD_LAYOUT_ENUM(NAME, name, span, doc) NAME, NAME##_LAST_ = NAME + (span) - 1,
+#define DAD_LAYOUT(LENGTH, first) enum { LENGTH##_FIRST_ = (first) - 1, LENGTH##_LIST(DAD_LAYOUT_ENUM) LENGTH }
+/* Section `section` of report `report` (both from 0), NULL outside the table: "LENGTH CONSTANT name span CONSTANT name
+ * span ...".  Static text; needs neither a model nor a device. */
+const char* dad_debug_report_layout(int32_t report, int32_t section);
+
 /* Which kernels one training step (dad_unet_forward_train + dad_unet_backward) takes at a batch, under the current
- * debug options (host-side query, no device work; needs dad_model_set_training(m, 1) but neither weights nor
- * dad_model_finalize).  Writes min(capacity, *needed_out) int32 values to `out`:
- *   [DAD_BP_WGRADS]         weight-gradient launches (conv_wgrad)
- *   [DAD_BP_MULTI]          ... whose fullest block stages more than one chunk (the double-buffered steady state)
- *   [DAD_BP_MAX_CHUNKS]     most chunks a block stages
- *   [DAD_BP_MAX_KSPLIT]     deepest batch split (slabs sum_slabs_kernel adds)
- *   [DAD_BP_PART]           launches whose last chunk is part filled (samples % chunk samples != 0; the windows of a
- *                           long layer count as samples)
- *   [DAD_BP_PART_MULTI]     ... in a block that stages more than one chunk
- *   [DAD_BP_WINDOWED]       launches of the windowed kernel (layers longer than 128 positions)
- *   [DAD_BP_TILE + tile]    launches per wgrad tile: 0 = 64x64, 1 = 64x32, 2 = 32x32, 3 = 32x32 on rows that are not
- *                           whole aligned float4s (the trajectory's columns)
- *   [DAD_BP_TAPS_TILE + 4 * i + tile]   the same per tap count, i indexing 1, 3, 4, 5, 7 taps
- *   [DAD_BP_FWD + 2 * cfg + s]          conv launches of the training forward on conv tile cfg (0..9) without (s = 0)
- *                                       and with (s = 1) grid-level split-K
- *   [DAD_BP_DGRAD + 2 * cfg + s]        the same for the data-gradient convs
- *   [DAD_BP_RECORD_INTS]    ints per record (DAD_BP_REC_*); one record per weight-gradient launch follows from
- *                           DAD_BP_HEADER on, in launch order:
- *     taps, tile, windowed (0 / 1), samples (windows of a windowed launch), samples per chunk, samples per block
- *     (a whole number of chunks), blocks over the batch (ksplit), chunks the fullest block stages, chunks the last
- *     block stages. */
-#define DAD_BP_WGRADS 0
-#define DAD_BP_MULTI 1
-#define DAD_BP_MAX_CHUNKS 2
-#define DAD_BP_MAX_KSPLIT 3
-#define DAD_BP_PART 4
-#define DAD_BP_PART_MULTI 5
-#define DAD_BP_WINDOWED 6
-#define DAD_BP_TILE 7
-#define DAD_BP_TAPS_TILE 11
-#define DAD_BP_FWD 31
-#define DAD_BP_DGRAD 51
-#define DAD_BP_RECORD_INTS 71
-#define DAD_BP_HEADER 72
-#define DAD_BP_REC_TAPS 0
-#define DAD_BP_REC_TILE 1
-#define DAD_BP_REC_WINDOWED 2
-#define DAD_BP_REC_SAMPLES 3
-#define DAD_BP_REC_SPC 4
-#define DAD_BP_REC_SPS 5
-#define DAD_BP_REC_KSPLIT 6
-#define DAD_BP_REC_CHUNKS 7
-#define DAD_BP_REC_LAST_CHUNKS 8
-#define DAD_BP_REC_INTS 9
+ * debug options (needs dad_model_set_training(m, 1) but neither weights nor dad_model_finalize): one record per
+ * weight-gradient launch. */
+#define DAD_BP_HEADER_LIST(F) \
+    F(DAD_BP_WGRADS, wgrads, 1, "weight-gradient launches (conv_wgrad)") \
+    F(DAD_BP_MULTI, multi, 1, "... whose fullest block stages more than one chunk (the double-buffered steady state)") \
+    F(DAD_BP_MAX_CHUNKS, max_chunks, 1, "most chunks a block stages") \
+    F(DAD_BP_MAX_KSPLIT, max_ksplit, 1, "deepest batch split (slabs sum_slabs_kernel adds)") \
+    F(DAD_BP_PART, part, 1, "launches whose last chunk is part filled (samples % chunk samples != 0; windows count as samples)") \
+    F(DAD_BP_PART_MULTI, part_multi, 1, "... in a block that stages more than one chunk") \
+    F(DAD_BP_WINDOWED, windowed, 1, "launches of the windowed kernel (layers longer than 128 positions)") \
+    F(DAD_BP_TILE, tile, 4, "[+ tile] launches per wgrad tile: 0 = 64x64, 1 = 64x32, 2 = 32x32, 3 = 32x32 on ragged rows (the trajectory's)") \
+    F(DAD_BP_TAPS_TILE, taps_tile, 20, "[+ 4 * i + tile] the same per tap count, i indexing 1, 3, 4, 5, 7 taps") \
+    F(DAD_BP_FWD, fwd, 20, "[+ 2 * cfg + s] training-forward conv launches on conv tile cfg (0..9) without / with (s) grid split-K") \
+    F(DAD_BP_DGRAD, dgrad, 20, "[+ 2 * cfg + s] the same for the data-gradient convs") \
+    F(DAD_BP_RECORD_INTS, record_ints, 1, "ints per record")
+DAD_LAYOUT(DAD_BP_HEADER, 0);
+#define DAD_BP_REC_INTS_LIST(F) \
+    F(DAD_BP_REC_TAPS, taps, 1, "taps") \
+    F(DAD_BP_REC_TILE, tile, 1, "wgrad tile, as DAD_BP_TILE") \
+    F(DAD_BP_REC_WINDOWED, windowed, 1, "0 / 1") \
+    F(DAD_BP_REC_SAMPLES, samples, 1, "samples (windows of a windowed launch)") \
+    F(DAD_BP_REC_SPC, spc, 1, "samples per chunk") \
+    F(DAD_BP_REC_SPS, sps, 1, "samples per block (a whole number of chunks)") \
+    F(DAD_BP_REC_KSPLIT, ksplit, 1, "blocks over the batch") \
+    F(DAD_BP_REC_CHUNKS, chunks, 1, "chunks the fullest block stages") \
+    F(DAD_BP_REC_LAST_CHUNKS, last_chunks, 1, "chunks the last block stages")
+DAD_LAYOUT(DAD_BP_REC_INTS, 0);
 int dad_debug_backward_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
 
 /* Everything dad_unet_backward replays at a batch, step by step, read from the list of steps and the per-batch geometry
- * the entry point launches from (host-side query, no device work; the conditions of dad_debug_backward_plan).  Writes
- * min(capacity, *needed_out) int32 values to `out`:
- *   [DAD_BS_STEPS]             records that follow from DAD_BS_HEADER on, [DAD_BS_RECORD_INTS] ints each, in launch order
- *   [DAD_BS_BATCH]             the batch
- *   [DAD_BS_COLSUMS_LAUNCHES]  col_sums_many_kernel launches that end the pass ([DAD_BS_COLSUMS_ENTRIES] arrays of
- *                              `batch` rows in all, the widest of [DAD_BS_COLSUMS_WIDEST] columns)
- *   [DAD_BS_PADCOPY]           1: the horizon is zero padded ([DAD_BS_REAL_HORIZON] of [DAD_BS_HORIZON] positions exist):
- *                              pad_rows_kernel copies the trajectory and d out in, slice_rows_cols_kernel copies d x out
- *   [DAD_BS_DX]                1: a gradient reaches the trajectory
- * A record starts with its kind, [DAD_BS_KIND] = DAD_BS_K_*; fields a kind does not name are 0.
- *   DAD_BS_K_BIAS   row_partial_sums_kernel: rows per sample, columns
- *   DAD_BS_K_WGRAD  conv_wgrad<taps, tile, windowed>: M, C0, C1 (the Z operand is the concat [C0 | C1]), stride, pad, Lg and
- *                   Lz (rows per sample of G and Z as the kernel counts them: per window when windowed), grid x / y,
- *                   ragged (rows that are not whole aligned float4s), concat_inside (the boundary C0 falls inside one
- *                   block's staged columns), edge_m / edge_c (the last M / C tile is partly filled), swapped (G is the
- *                   conv's input, Z the gradient: the transposed conv), ksplit, slab_n4 (float4s per slab
- *                   sum_slabs_kernel adds; 0 when ksplit == 1), and samples, spc, sps, chunks, last_chunks as
- *                   DAD_BP_REC_* of dad_debug_backward_plan
- *   DAD_BS_K_DGRAD  a data-gradient conv (its launch: mode 3 of dad_debug_forward_plan): forward conv, sub, write (0 set,
- *                   1 add through the residual operand, 2 staged and added by add_inplace_kernel)
- *   DAD_BS_K_GN     gn_mish_bwd_wave_kernel<nv> (nv = 0: gn_mish_bwd_kernel): channels per group, L, lreal (> 0: positions
- *                   that exist), cpg_real (> 0: channels per group that exist), dtemb (d time projection is written),
- *                   short_pair (a pair has fewer than 64 float4), C
- *   DAD_BS_K_RESID  identity residual: write (0: a copy, 1: add_inplace_kernel), floats per sample, to_x (into d x)
- *   DAD_BS_K_COLS   take_cols_kernel: C columns at `off` of rows of `ld`, rows per sample, write (1: accumulates) */
-#define DAD_BS_STEPS 0
-#define DAD_BS_RECORD_INTS 1
-#define DAD_BS_BATCH 2
-#define DAD_BS_COLSUMS_LAUNCHES 3
-#define DAD_BS_COLSUMS_ENTRIES 4
-#define DAD_BS_COLSUMS_WIDEST 5
-#define DAD_BS_PADCOPY 6
-#define DAD_BS_HORIZON 7
-#define DAD_BS_REAL_HORIZON 8
-#define DAD_BS_DX 9
-#define DAD_BS_HEADER 12
-#define DAD_BS_K_BIAS 0
-#define DAD_BS_K_WGRAD 1
-#define DAD_BS_K_DGRAD 2
-#define DAD_BS_K_GN 3
-#define DAD_BS_K_RESID 4
-#define DAD_BS_K_COLS 5
-#define DAD_BS_KIND 0
-#define DAD_BS_BIAS_ROWS 1
-#define DAD_BS_BIAS_C 2
-#define DAD_BS_WG_TAPS 1
-#define DAD_BS_WG_TILE 2
-#define DAD_BS_WG_WINDOWED 3
-#define DAD_BS_WG_M 4
-#define DAD_BS_WG_C0 5
-#define DAD_BS_WG_C1 6
-#define DAD_BS_WG_STRIDE 7
-#define DAD_BS_WG_PAD 8
-#define DAD_BS_WG_LG 9
-#define DAD_BS_WG_LZ 10
-#define DAD_BS_WG_GX 11
-#define DAD_BS_WG_GY 12
-#define DAD_BS_WG_RAGGED 13
-#define DAD_BS_WG_CONCAT_INSIDE 14
-#define DAD_BS_WG_EDGE_M 15
-#define DAD_BS_WG_EDGE_C 16
-#define DAD_BS_WG_SWAPPED 17
-#define DAD_BS_WG_KSPLIT 18
-#define DAD_BS_WG_SLAB_N4 19
-#define DAD_BS_WG_SAMPLES 20
-#define DAD_BS_WG_SPC 21
-#define DAD_BS_WG_SPS 22
-#define DAD_BS_WG_CHUNKS 23
-#define DAD_BS_WG_LAST_CHUNKS 24
-#define DAD_BS_DG_CONV 1
-#define DAD_BS_DG_SUB 2
-#define DAD_BS_DG_WRITE 3
-#define DAD_BS_GN_NV 1
-#define DAD_BS_GN_CPG 2
-#define DAD_BS_GN_L 3
-#define DAD_BS_GN_LREAL 4
-#define DAD_BS_GN_CPG_REAL 5
-#define DAD_BS_GN_DTEMB 6
-#define DAD_BS_GN_SHORT_PAIR 7
-#define DAD_BS_GN_C 8
-#define DAD_BS_RS_WRITE 1
-#define DAD_BS_RS_N 2
-#define DAD_BS_RS_TO_X 3
-#define DAD_BS_CL_C 1
-#define DAD_BS_CL_OFF 2
-#define DAD_BS_CL_LD 3
-#define DAD_BS_CL_ROWS 4
-#define DAD_BS_CL_WRITE 5
-#define DAD_BS_REC_INTS 25
+ * the entry point launches from (the conditions of dad_debug_backward_plan): one record per step. */
+#define DAD_BS_HEADER_LIST(F) \
+    F(DAD_BS_STEPS, steps, 1, "records") \
+    F(DAD_BS_RECORD_INTS, record_ints, 1, "ints per record") \
+    F(DAD_BS_BATCH, batch, 1, "the batch") \
+    F(DAD_BS_COLSUMS_LAUNCHES, colsums_launches, 1, "col_sums_many_kernel launches that end the pass") \
+    F(DAD_BS_COLSUMS_ENTRIES, colsums_entries, 1, "arrays of `batch` rows they sum, in all") \
+    F(DAD_BS_COLSUMS_WIDEST, colsums_widest, 1, "columns of the widest") \
+    F(DAD_BS_PADCOPY, padcopy, 1, "1: the horizon is zero padded: pad_rows_kernel copies x and d out in, slice_rows_cols_kernel d x out") \
+    F(DAD_BS_HORIZON, horizon, 1, "positions of the padded layout") \
+    F(DAD_BS_REAL_HORIZON, real_horizon, 1, "positions that exist") \
+    F(DAD_BS_DX, dx, 1, "1: a gradient reaches the trajectory") \
+    F(DAD_BS_UNUSED, _, 2, "reserved")
+DAD_LAYOUT(DAD_BS_HEADER, 0);
+#define DAD_BS_KINDS_LIST(F) \
+    F(DAD_BS_K_BIAS, bias, 1, "row_partial_sums_kernel") \
+    F(DAD_BS_K_WGRAD, wgrad, 1, "conv_wgrad<taps, tile, windowed>") \
+    F(DAD_BS_K_DGRAD, dgrad, 1, "a data-gradient conv (its launch: mode 3 of dad_debug_forward_plan)") \
+    F(DAD_BS_K_GN, gn, 1, "gn_mish_bwd_wave_kernel<nv> (nv = 0: gn_mish_bwd_kernel)") \
+    F(DAD_BS_K_RESID, resid, 1, "identity residual") \
+    F(DAD_BS_K_COLS, cols, 1, "take_cols_kernel")
+DAD_LAYOUT(DAD_BS_KINDS, 0);
+#define DAD_BS_KIND_FIELD(F) F(DAD_BS_KIND, kind, 1, "DAD_BS_K_*: which of the six lists below names the rest")
+#define DAD_BS_REC_INTS_LIST(F) DAD_BS_KIND_FIELD(F) F(DAD_BS_REC_REST, _, 24, "as the kind's list says; 0 where it names nothing")
+DAD_LAYOUT(DAD_BS_REC_INTS, 0);
+#define DAD_BS_BIAS_INTS_LIST(F) \
+    F(DAD_BS_BIAS_ROWS, rows, 1, "rows per sample") \
+    F(DAD_BS_BIAS_C, C, 1, "columns") \
+    F(DAD_BS_BIAS_UNUSED, _, 22, "reserved")
+DAD_LAYOUT(DAD_BS_BIAS_INTS, DAD_BS_REC_REST);
+#define DAD_BS_WGRAD_INTS_LIST(F) \
+    F(DAD_BS_WG_TAPS, taps, 1, "the instantiation: taps") \
+    F(DAD_BS_WG_TILE, tile, 1, "... tile, as DAD_BP_TILE") \
+    F(DAD_BS_WG_WINDOWED, windowed, 1, "... windowed") \
+    F(DAD_BS_WG_M, M, 1, "rows of the gradient") \
+    F(DAD_BS_WG_C0, C0, 1, "columns of the first source") \
+    F(DAD_BS_WG_C1, C1, 1, "... of the second (the Z operand is the concat [C0 | C1])") \
+    F(DAD_BS_WG_STRIDE, stride, 1, "stride") \
+    F(DAD_BS_WG_PAD, pad, 1, "pad") \
+    F(DAD_BS_WG_LG, Lg, 1, "rows per sample of G as the kernel counts them (per window when windowed)") \
+    F(DAD_BS_WG_LZ, Lz, 1, "... of Z") \
+    F(DAD_BS_WG_GX, gx, 1, "grid x") \
+    F(DAD_BS_WG_GY, gy, 1, "grid y") \
+    F(DAD_BS_WG_RAGGED, ragged, 1, "rows that are not whole aligned float4s") \
+    F(DAD_BS_WG_CONCAT_INSIDE, concat_inside, 1, "the boundary C0 falls inside one block's staged columns") \
+    F(DAD_BS_WG_EDGE_M, edge_m, 1, "the last M tile is partly filled") \
+    F(DAD_BS_WG_EDGE_C, edge_c, 1, "the last C tile is partly filled") \
+    F(DAD_BS_WG_SWAPPED, swapped, 1, "G is the conv's input, Z the gradient: the transposed conv") \
+    F(DAD_BS_WG_KSPLIT, ksplit, 1, "blocks over the batch") \
+    F(DAD_BS_WG_SLAB_N4, slab_n4, 1, "float4s per slab sum_slabs_kernel adds; 0 when ksplit == 1") \
+    F(DAD_BS_WG_SAMPLES, samples, 1, "as DAD_BP_REC_SAMPLES") \
+    F(DAD_BS_WG_SPC, spc, 1, "as DAD_BP_REC_SPC") \
+    F(DAD_BS_WG_SPS, sps, 1, "as DAD_BP_REC_SPS") \
+    F(DAD_BS_WG_CHUNKS, chunks, 1, "as DAD_BP_REC_CHUNKS") \
+    F(DAD_BS_WG_LAST_CHUNKS, last_chunks, 1, "as DAD_BP_REC_LAST_CHUNKS")
+DAD_LAYOUT(DAD_BS_WGRAD_INTS, DAD_BS_REC_REST);
+#define DAD_BS_DGRAD_INTS_LIST(F) \
+    F(DAD_BS_DG_CONV, conv, 1, "the forward conv") \
+    F(DAD_BS_DG_SUB, sub, 1, "which of its data-gradient launches") \
+    F(DAD_BS_DG_WRITE, write, 1, "0 set, 1 add through the residual operand, 2 staged and added by add_inplace_kernel") \
+    F(DAD_BS_DG_UNUSED, _, 21, "reserved")
+DAD_LAYOUT(DAD_BS_DGRAD_INTS, DAD_BS_REC_REST);
+#define DAD_BS_GN_INTS_LIST(F) \
+    F(DAD_BS_GN_NV, nv, 1, "the instantiation") \
+    F(DAD_BS_GN_CPG, cpg, 1, "channels per group") \
+    F(DAD_BS_GN_L, L, 1, "positions") \
+    F(DAD_BS_GN_LREAL, lreal, 1, "> 0: positions that exist") \
+    F(DAD_BS_GN_CPG_REAL, cpg_real, 1, "> 0: channels per group that exist") \
+    F(DAD_BS_GN_DTEMB, dtemb, 1, "d time projection is written") \
+    F(DAD_BS_GN_SHORT_PAIR, short_pair, 1, "a pair has fewer than 64 float4") \
+    F(DAD_BS_GN_C, C, 1, "channels") \
+    F(DAD_BS_GN_UNUSED, _, 16, "reserved")
+DAD_LAYOUT(DAD_BS_GN_INTS, DAD_BS_REC_REST);
+#define DAD_BS_RESID_INTS_LIST(F) \
+    F(DAD_BS_RS_WRITE, write, 1, "0: a copy, 1: add_inplace_kernel") \
+    F(DAD_BS_RS_N, n, 1, "floats per sample") \
+    F(DAD_BS_RS_TO_X, to_x, 1, "into d x") \
+    F(DAD_BS_RS_UNUSED, _, 21, "reserved")
+DAD_LAYOUT(DAD_BS_RESID_INTS, DAD_BS_REC_REST);
+#define DAD_BS_COLS_INTS_LIST(F) \
+    F(DAD_BS_CL_C, C, 1, "columns taken") \
+    F(DAD_BS_CL_OFF, off, 1, "... from this column on") \
+    F(DAD_BS_CL_LD, ld, 1, "... of rows this long") \
+    F(DAD_BS_CL_ROWS, rows, 1, "rows per sample") \
+    F(DAD_BS_CL_WRITE, write, 1, "1: accumulates") \
+    F(DAD_BS_CL_UNUSED, _, 19, "reserved")
+DAD_LAYOUT(DAD_BS_COLS_INTS, DAD_BS_REC_REST);
 int dad_debug_backward_steps(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
 
 /* The time chain of one fused objective step (dad_train_objective_forward + dad_train_objective_backward) at a batch:
- * the list of launches the two entry points replay (host-side query, no device work; needs
- * dad_model_set_training(m, 1) but neither weights nor dad_model_finalize; a batch the objective refuses is refused
- * here too).  Writes min(capacity, *needed_out) int32 values to `out`:
- *   [DAD_OP_LOSS_BLOCKS]    blocks of the loss's partial sums (at most 1024)
- *   [DAD_OP_KSLICES]        K slices of d act = d rows . W (slabs time_dtemb_kernel adds in slice order)
- *   [DAD_OP_KSLICE]         k values per slice (a multiple of 128)
- *   [DAD_OP_TEMB_WIDTH]     columns of the time projections (padded widths), the K of that product
- *   [DAD_OP_BLOCKS]         ResidualTemporalBlocks
- *   [DAD_OP_N]              batch x horizon x transition_dim: the elements the loss is a mean of (real ones only)
- *   [DAD_OP_RECORD_INTS]    ints per record (DAD_OP_REC_*)
- *   [DAD_OP_LAUNCHES]       records: 9, one per launch in launch order (3 forward, 6 backward), from DAD_OP_HEADER on:
- *     mode (DAD_OP_TG_*: the eight instantiations of time_gemm_kernel in the order of its TimeGemm enumeration, and
- *     DAD_OP_TG_DTEMB for time_dtemb_kernel: M x N elements, K = slabs added), M, N, K of out[M][N] = sum over K, the
- *     grid x / y / z (32 x 32 output tiles, K slices), 32-wide K chunks in a full slice (the block's four waves take
- *     them round robin) and in the last slice, K % 32, k values per slice; the three chunk / tail fields are 0 for
- *     DAD_OP_TG_DTEMB. */
-#define DAD_OP_LOSS_BLOCKS 0
-#define DAD_OP_KSLICES 1
-#define DAD_OP_KSLICE 2
-#define DAD_OP_TEMB_WIDTH 3
-#define DAD_OP_BLOCKS 4
-#define DAD_OP_N 5
-#define DAD_OP_RECORD_INTS 6
-#define DAD_OP_LAUNCHES 7
-#define DAD_OP_HEADER 8
-#define DAD_OP_REC_MODE 0
-#define DAD_OP_REC_M 1
-#define DAD_OP_REC_N 2
-#define DAD_OP_REC_K 3
-#define DAD_OP_REC_GRID_X 4
-#define DAD_OP_REC_GRID_Y 5
-#define DAD_OP_REC_GRID_Z 6
-#define DAD_OP_REC_CHUNKS 7
-#define DAD_OP_REC_LAST_CHUNKS 8
-#define DAD_OP_REC_KTAIL 9
-#define DAD_OP_REC_KSLICE 10
-#define DAD_OP_REC_INTS 11
-#define DAD_OP_TG_FWD_H1 0
-#define DAD_OP_TG_FWD_TEMB 1
-#define DAD_OP_TG_FWD_ROWS 2
-#define DAD_OP_TG_BWD_DWK 3
-#define DAD_OP_TG_BWD_DACT 4
-#define DAD_OP_TG_BWD_DW3 5
-#define DAD_OP_TG_BWD_DH1 6
-#define DAD_OP_TG_BWD_DW1 7
-#define DAD_OP_TG_DTEMB 8
+ * the list of launches the two entry points replay (needs dad_model_set_training(m, 1) but neither weights nor
+ * dad_model_finalize; a batch the objective refuses is refused here too): one record per launch (3 forward, 6
+ * backward), each out[M][N] = sum over K on a grid of 32 x 32 output tiles (x, y) and K slices (z). */
+#define DAD_OP_HEADER_LIST(F) \
+    F(DAD_OP_LOSS_BLOCKS, loss_blocks, 1, "blocks of the loss's partial sums (at most 1024)") \
+    F(DAD_OP_KSLICES, kslices, 1, "K slices of d act = d rows . W (slabs time_dtemb_kernel adds in slice order)") \
+    F(DAD_OP_KSLICE, kslice, 1, "k values per slice (a multiple of 128)") \
+    F(DAD_OP_TEMB_WIDTH, temb_width, 1, "columns of the time projections (padded widths), the K of that product") \
+    F(DAD_OP_BLOCKS, blocks, 1, "ResidualTemporalBlocks") \
+    F(DAD_OP_N, n, 1, "batch x horizon x transition_dim: the elements the loss is a mean of (real ones only)") \
+    F(DAD_OP_RECORD_INTS, record_ints, 1, "ints per record") \
+    F(DAD_OP_LAUNCHES, launches, 1, "records: 9")
+DAD_LAYOUT(DAD_OP_HEADER, 0);
+#define DAD_OP_REC_INTS_LIST(F) \
+    F(DAD_OP_REC_MODE, mode, 1, "DAD_OP_TG_*") \
+    F(DAD_OP_REC_M, M, 1, "M") \
+    F(DAD_OP_REC_N, N, 1, "N") \
+    F(DAD_OP_REC_K, K, 1, "K") \
+    F(DAD_OP_REC_GRID_X, gx, 1, "grid x") \
+    F(DAD_OP_REC_GRID_Y, gy, 1, "grid y") \
+    F(DAD_OP_REC_GRID_Z, gz, 1, "grid z") \
+    F(DAD_OP_REC_CHUNKS, chunks, 1, "32-wide K chunks in a full slice (the block's four waves take them round robin); 0 for DTEMB") \
+    F(DAD_OP_REC_LAST_CHUNKS, last_chunks, 1, "... in the last slice; 0 for DTEMB") \
+    F(DAD_OP_REC_KTAIL, ktail, 1, "K % 32; 0 for DTEMB") \
+    F(DAD_OP_REC_KSLICE, kslice, 1, "k values per slice")
+DAD_LAYOUT(DAD_OP_REC_INTS, 0);
+#define DAD_OP_TG_MODES_LIST(F) \
+    F(DAD_OP_TG_FWD_H1, FWD_H1, 1, "(time_gemm_kernel's eight instantiations, in the order of TimeGemm) h1 = emb W1^T + b1") \
+    F(DAD_OP_TG_FWD_TEMB, FWD_TEMB, 1, "temb = mish(h1) W3^T + b3, act = mish(temb)") \
+    F(DAD_OP_TG_FWD_ROWS, FWD_ROWS, 1, "rows = act Wk^T + bk, all blocks") \
+    F(DAD_OP_TG_BWD_DWK, BWD_DWK, 1, "d Wk = d rows^T act, d bk") \
+    F(DAD_OP_TG_BWD_DACT, BWD_DACT, 1, "d act = d rows W, K slices in slabs") \
+    F(DAD_OP_TG_BWD_DW3, BWD_DW3, 1, "d W3 = d temb^T mish(h1), d b3") \
+    F(DAD_OP_TG_BWD_DH1, BWD_DH1, 1, "d h1 = (d temb W3) mish'(h1)") \
+    F(DAD_OP_TG_BWD_DW1, BWD_DW1, 1, "d W1 = d h1^T emb, d b1") \
+    F(DAD_OP_TG_DTEMB, DTEMB, 1, "time_dtemb_kernel: M x N elements, K = slabs added")
+DAD_LAYOUT(DAD_OP_TG_MODES, 0);
 int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
 
 /* What one forward evaluation launches at a batch under the current debug options: the description the entry point
@@ -567,170 +556,138 @@ int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t 
  *   1  the same evaluation on the batch kernels: dad_unet_forward_rows (per-row timesteps)
  *   2  dad_unet_forward_train (the training plan)
  *   3  the data-gradient conv launches of dad_unet_backward, in launch order
- * Writes min(capacity, *needed_out) int32 values to `out`:
- *   [DAD_FP_MODE] [DAD_FP_BATCH]   as asked
- *   [DAD_FP_SMALL]          1: the small-batch plan is taken (csrc/conv_cc.hpp, conv_ccw.hpp), the records are DAD_FP_CC_*
- *   [DAD_FP_RECORDS]        records that follow from DAD_FP_HEADER on, [DAD_FP_RECORD_INTS] ints each
- *   [DAD_FP_FINAL_GX] [DAD_FP_FINAL_GY]   grid of the final kernel (0 in mode 3)
- *   [DAD_FP_FINAL_KERNEL]   DAD_FP_FINAL_POSTERIOR (final_posterior_kernel), DAD_FP_FINAL_CC (final_cc_kernel) or
- *                           DAD_FP_FINAL_NONE (mode 3)
- * One record per conv-GEMM launch in launch order (a 1x1 residual conv that rides in its carrier's launch has none):
- *   conv index into the plan (mode 3: the forward conv whose data gradient this is, -1 = final_conv[1]), sub (mode 3:
- *   which of that conv's data-gradient launches), tile cfg, taps, stride, flags (bit 0 x3, 1 bdir, 2 ragged, 3 res —
- *   the ride —, 4 padded, 5 windowed: the flag word of kernel_registered_f, so (cfg, taps, stride, flags) names the
- *   instantiation), K chunk, grid-level K slices, npt of the gn_pass_kernel<npt> launch that follows (0: none),
- *   N tiles, M tiles, 1 when the last N tile holds fewer samples than it has room for, kernel family:
- *   DAD_FP_FAMILY_GEMM (conv_gemm_f32, the instantiation named above) or DAD_FP_FAMILY_HALO8 (conv_halo8_f32 of
- *   csrc/conv_halo8.hpp on the same tile, grid and ride: cfg 0 / 1 and flag bit 3 name its instantiation).
- * With [DAD_FP_SMALL] one record per launched small-batch conv instead:
- *   conv index, taps, stride, wide (conv_ccw), ride, big, ride_in, rows per tile (16 / 32), windowed, channels per K
- *   slice, K slices, N tiles, res_kind (how the output's residual reaches its consumer: 0 none, 1 the trajectory,
- *   2 a finished tensor, 3 the ride slabs of a carrier, 4 the slabs of a stand-alone 1x1 conv). */
-#define DAD_FP_MODE 0
-#define DAD_FP_BATCH 1
-#define DAD_FP_SMALL 2
-#define DAD_FP_RECORDS 3
-#define DAD_FP_RECORD_INTS 4
-#define DAD_FP_FINAL_GX 5
-#define DAD_FP_FINAL_GY 6
-#define DAD_FP_FINAL_KERNEL 7
-#define DAD_FP_HEADER 8
-#define DAD_FP_FINAL_NONE 0
-#define DAD_FP_FINAL_POSTERIOR 1
-#define DAD_FP_FINAL_CC 2
-#define DAD_FP_REC_CONV 0
-#define DAD_FP_REC_SUB 1
-#define DAD_FP_REC_CFG 2
-#define DAD_FP_REC_TAPS 3
-#define DAD_FP_REC_STRIDE 4
-#define DAD_FP_REC_FLAGS 5
-#define DAD_FP_REC_KC 6
-#define DAD_FP_REC_KSLICES 7
-#define DAD_FP_REC_GN_NPT 8
-#define DAD_FP_REC_NTILES_N 9
-#define DAD_FP_REC_MTILES 10
-#define DAD_FP_REC_PART_TILE 11
-#define DAD_FP_REC_FAMILY 12
-#define DAD_FP_REC_INTS 13
-#define DAD_FP_FAMILY_GEMM 0
-#define DAD_FP_FAMILY_HALO8 1
-#define DAD_FP_CC_CONV 0
-#define DAD_FP_CC_TAPS 1
-#define DAD_FP_CC_STRIDE 2
-#define DAD_FP_CC_WIDE 3
-#define DAD_FP_CC_RIDE 4
-#define DAD_FP_CC_BIG 5
-#define DAD_FP_CC_RIDE_IN 6
-#define DAD_FP_CC_TILE_ROWS 7
-#define DAD_FP_CC_WINDOWED 8
-#define DAD_FP_CC_SLICE_CH 9
-#define DAD_FP_CC_KSLICES 10
-#define DAD_FP_CC_NTILES 11
-#define DAD_FP_CC_RES_KIND 12
-#define DAD_FP_CC_INTS 13
+ * One record per conv-GEMM launch (a 1x1 residual conv that rides in its carrier's launch has none) or, with
+ * [DAD_FP_SMALL], one DAD_FP_CC_* record per launched small-batch conv instead. */
+#define DAD_FP_HEADER_LIST(F) \
+    F(DAD_FP_MODE, mode, 1, "as asked") \
+    F(DAD_FP_BATCH, batch, 1, "as asked") \
+    F(DAD_FP_SMALL, small, 1, "1: the small-batch plan is taken (csrc/conv_cc.hpp, conv_ccw.hpp)") \
+    F(DAD_FP_RECORDS, records, 1, "records") \
+    F(DAD_FP_RECORD_INTS, record_ints, 1, "ints per record") \
+    F(DAD_FP_FINAL_GX, final_gx, 1, "grid x of the final kernel (0 in mode 3)") \
+    F(DAD_FP_FINAL_GY, final_gy, 1, "grid y") \
+    F(DAD_FP_FINAL_KERNEL, final_kernel, 1, "DAD_FP_FINAL_*")
+DAD_LAYOUT(DAD_FP_HEADER, 0);
+#define DAD_FP_FINALS_LIST(F) \
+    F(DAD_FP_FINAL_NONE, none, 1, "mode 3") \
+    F(DAD_FP_FINAL_POSTERIOR, final_posterior_kernel, 1, "the batch kernels' final kernel") \
+    F(DAD_FP_FINAL_CC, final_cc_kernel, 1, "the small-batch plan's")
+DAD_LAYOUT(DAD_FP_FINALS, 0);
+#define DAD_FP_REC_INTS_LIST(F) \
+    F(DAD_FP_REC_CONV, conv, 1, "index into the plan (mode 3: the forward conv whose data gradient this is, -1 = final_conv[1])") \
+    F(DAD_FP_REC_SUB, sub, 1, "mode 3: which of that conv's data-gradient launches") \
+    F(DAD_FP_REC_CFG, cfg, 1, "tile cfg") \
+    F(DAD_FP_REC_TAPS, taps, 1, "taps") \
+    F(DAD_FP_REC_STRIDE, stride, 1, "stride") \
+    F(DAD_FP_REC_FLAGS, flags, 1, "bit 0 x3, 1 bdir, 2 ragged, 3 res (the ride), 4 padded, 5 windowed: kernel_registered_f's flag word; (cfg, taps, stride, flags) names the conv_gemm_f32 instantiation, cfg 0 / 1 and bit 3 the conv_halo8_f32 one") \
+    F(DAD_FP_REC_KC, kc, 1, "K chunk") \
+    F(DAD_FP_REC_KSLICES, kslices, 1, "grid-level K slices") \
+    F(DAD_FP_REC_GN_NPT, gn_npt, 1, "npt of the gn_pass_kernel<npt> launch that follows (0: none)") \
+    F(DAD_FP_REC_NTILES_N, ntiles_n, 1, "N tiles") \
+    F(DAD_FP_REC_MTILES, mtiles, 1, "M tiles") \
+    F(DAD_FP_REC_PART_TILE, part_tile, 1, "1 when the last N tile holds fewer samples than it has room for") \
+    F(DAD_FP_REC_FAMILY, family, 1, "DAD_FP_FAMILY_*")
+DAD_LAYOUT(DAD_FP_REC_INTS, 0);
+#define DAD_FP_FAMILIES_LIST(F) \
+    F(DAD_FP_FAMILY_GEMM, gemm, 1, "conv_gemm_f32") \
+    F(DAD_FP_FAMILY_HALO8, halo8, 1, "conv_halo8_f32 of csrc/conv_halo8.hpp on the same tile, grid and ride")
+DAD_LAYOUT(DAD_FP_FAMILIES, 0);
+#define DAD_FP_CC_INTS_LIST(F) \
+    F(DAD_FP_CC_CONV, conv, 1, "index into the plan") \
+    F(DAD_FP_CC_TAPS, taps, 1, "taps") \
+    F(DAD_FP_CC_STRIDE, stride, 1, "stride") \
+    F(DAD_FP_CC_WIDE, wide, 1, "conv_ccw") \
+    F(DAD_FP_CC_RIDE, ride, 1, "a 1x1 residual conv rides") \
+    F(DAD_FP_CC_BIG, big, 1, "the big form") \
+    F(DAD_FP_CC_RIDE_IN, ride_in, 1, "consumes ride slabs") \
+    F(DAD_FP_CC_TILE_ROWS, tile_rows, 1, "rows per tile (16 / 32)") \
+    F(DAD_FP_CC_WINDOWED, windowed, 1, "windowed") \
+    F(DAD_FP_CC_SLICE_CH, slice_ch, 1, "channels per K slice") \
+    F(DAD_FP_CC_KSLICES, kslices, 1, "K slices") \
+    F(DAD_FP_CC_NTILES, ntiles, 1, "N tiles") \
+    F(DAD_FP_CC_RES_KIND, res_kind, 1, "how the residual reaches its consumer: 0 none, 1 the trajectory, 2 a finished tensor, 3 a carrier's ride slabs, 4 a stand-alone 1x1 conv's slabs")
+DAD_LAYOUT(DAD_FP_CC_INTS, 0);
 int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out);
 /* The conv_halo8_f32 launches (csrc/conv_halo8.hpp) of the same description, modes 0 and 1 only, with what the kernel
- * makes of its ConvParams: read from the ConvOp / LaunchGeom the launch fills them from (csrc/host_plan.hpp,
- * halo8_plan_encode), nothing decided.  Writes min(capacity, *needed_out) int32 values: [0] the records, [1]
- * DAD_H8_INTS, then per launch in launch order
- *   [DAD_H8_CONV] [DAD_H8_CFG] [DAD_H8_RIDE]   conv index, tile (0 / 1), the riding 1x1 conv: the instantiation
- *   [DAD_H8_CHUNKS]       32-channel K chunks, (cin0 + cin1) / 32
- *   [DAD_H8_SRC1_CHUNK]   the chunk from which the second source is read, -1 without one
- *   [DAD_H8_RES] [DAD_H8_TEMB]   a residual operand / a time embedding is present
- *   [DAD_H8_PER_ROW]      the time embedding is indexed per sample (mode 1, where there is one)
- *   [DAD_H8_GN]           GroupNorm runs in the kernel
- *   [DAD_H8_WPP]          waves one (sample, group) pair spans (0 without GroupNorm; > 1: the cross-wave sum through LDS)
- *   [DAD_H8_XCD_GN]       0: the plain grid (y = M tile, z = N tile), else the XCD-aware tile order
- *   [DAD_H8_MTILES] [DAD_H8_NTILES_N] [DAD_H8_PART_TILE]   as the DAD_FP_REC_* fields of those names */
-#define DAD_H8_HEADER 2
-#define DAD_H8_CONV 0
-#define DAD_H8_CFG 1
-#define DAD_H8_RIDE 2
-#define DAD_H8_CHUNKS 3
-#define DAD_H8_SRC1_CHUNK 4
-#define DAD_H8_RES 5
-#define DAD_H8_TEMB 6
-#define DAD_H8_PER_ROW 7
-#define DAD_H8_GN 8
-#define DAD_H8_WPP 9
-#define DAD_H8_XCD_GN 10
-#define DAD_H8_MTILES 11
-#define DAD_H8_NTILES_N 12
-#define DAD_H8_PART_TILE 13
-#define DAD_H8_INTS 14
+ * makes of its ConvParams: read from the ConvOp / LaunchGeom the launch fills them from (csrc/plan_report.hpp,
+ * halo8_plan_encode), nothing decided: one record per launch. */
+#define DAD_H8_HEADER_LIST(F) \
+    F(DAD_H8_RECORDS, records, 1, "records") \
+    F(DAD_H8_RECORD_INTS, record_ints, 1, "ints per record")
+DAD_LAYOUT(DAD_H8_HEADER, 0);
+#define DAD_H8_INTS_LIST(F) \
+    F(DAD_H8_CONV, conv, 1, "conv index") \
+    F(DAD_H8_CFG, cfg, 1, "the instantiation: tile (0 / 1)") \
+    F(DAD_H8_RIDE, ride, 1, "... the riding 1x1 conv") \
+    F(DAD_H8_CHUNKS, chunks, 1, "32-channel K chunks, (cin0 + cin1) / 32") \
+    F(DAD_H8_SRC1_CHUNK, src1_chunk, 1, "the chunk from which the second source is read, -1 without one") \
+    F(DAD_H8_RES, res, 1, "a residual operand is present") \
+    F(DAD_H8_TEMB, temb, 1, "a time embedding is present") \
+    F(DAD_H8_PER_ROW, per_row, 1, "the time embedding is indexed per sample (mode 1, where there is one)") \
+    F(DAD_H8_GN, gn, 1, "GroupNorm runs in the kernel") \
+    F(DAD_H8_WPP, wpp, 1, "waves one (sample, group) pair spans (0 without GroupNorm; > 1: the cross-wave sum through LDS)") \
+    F(DAD_H8_XCD_GN, xcd_gn, 1, "0: the plain grid (y = M tile, z = N tile), else the XCD-aware tile order") \
+    F(DAD_H8_MTILES, mtiles, 1, "as DAD_FP_REC_MTILES") \
+    F(DAD_H8_NTILES_N, ntiles_n, 1, "as DAD_FP_REC_NTILES_N") \
+    F(DAD_H8_PART_TILE, part_tile, 1, "as DAD_FP_REC_PART_TILE")
+DAD_LAYOUT(DAD_H8_INTS, 0);
 int dad_debug_halo8_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out);
 /* Which kernel one dad_project (violation == 0) or dad_projection_violation (violation != 0) call launches for
  * trajectories (batch, horizon, observation_dim + action_dim) and a dad_project_args.scratch of scratch_bytes (0: none),
- * and on which grid: the plan the two entry points launch from.  Host logic only, no device call.  out[DAD_PP_INTS]:
- *   [DAD_PP_FORM]            DAD_PP_ROW1 (project_kernel<1,16>: one trajectory per block), DAD_PP_ROW4 (project_kernel<4,16>:
- *                            four per block, batches beyond 512 whose four rows fit LDS) or DAD_PP_GEMM (project_gemm_kernel:
- *                            32 trajectories x 32 columns of P per block; never for the violation)
- *   [DAD_PP_ROWS_PER_BLOCK]  1, 4 or 32
- *   [DAD_PP_GX] [DAD_PP_GY]  the grid
- *   [DAD_PP_LDS_BYTES]       dynamic LDS of one block
- *   [DAD_PP_REFUSED]         1: the call fails with DAD_E_INVALID (one trajectory's partial sums exceed LDS and there is
- *                            no scratch, or fewer than 32 trajectories, for the GEMM form); the other fields then describe
- *                            the launch that does not fit */
-#define DAD_PP_FORM 0
-#define DAD_PP_ROWS_PER_BLOCK 1
-#define DAD_PP_GX 2
-#define DAD_PP_GY 3
-#define DAD_PP_LDS_BYTES 4
-#define DAD_PP_REFUSED 5
-#define DAD_PP_INTS 6
-#define DAD_PP_ROW1 0
-#define DAD_PP_ROW4 1
-#define DAD_PP_GEMM 2
+ * and on which grid: the plan the two entry points launch from.  Host logic only, no device call.  out[DAD_PP_INTS]. */
+#define DAD_PP_INTS_LIST(F) \
+    F(DAD_PP_FORM, form, 1, "DAD_PP_ROW1 / ROW4 / GEMM") \
+    F(DAD_PP_ROWS_PER_BLOCK, rows_per_block, 1, "1, 4 or 32") \
+    F(DAD_PP_GX, gx, 1, "grid x") \
+    F(DAD_PP_GY, gy, 1, "grid y") \
+    F(DAD_PP_LDS_BYTES, lds_bytes, 1, "dynamic LDS of one block") \
+    F(DAD_PP_REFUSED, refused, 1, "1: the call fails with DAD_E_INVALID (a trajectory's partial sums exceed LDS and the GEMM form has no scratch or fewer than 32 trajectories); the other fields then describe the launch that does not fit")
+DAD_LAYOUT(DAD_PP_INTS, 0);
+#define DAD_PP_FORMS_LIST(F) \
+    F(DAD_PP_ROW1, row1, 1, "project_kernel<1,16>: one trajectory per block") \
+    F(DAD_PP_ROW4, row4, 1, "project_kernel<4,16>: four per block, batches beyond 512 whose four rows fit LDS") \
+    F(DAD_PP_GEMM, gemm, 1, "project_gemm_kernel: 32 trajectories x 32 columns of P per block; never for the violation")
+DAD_LAYOUT(DAD_PP_FORMS, 0);
 int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
                            size_t scratch_bytes, int32_t violation, int32_t* out);
 /* Whether dad_sample_loop at `batch` (projection != 0: called with a projection argument) takes the seam between two
  * denoise steps as one launch (csrc/conv_seam.hpp; the rule: plan_seam in csrc/host_plan.hpp), under the model's current
- * options.  Host logic only, no device call; the model needs no weights.  out[DAD_SEAM_INTS]:
- *   [DAD_SEAM_TAKEN]      1 / 0
- *   [DAD_SEAM_REASON]     0 = taken, else the first condition that refuses it; dad_debug_seam_reason names it
- *   [DAD_SEAM_GRID] [DAD_SEAM_THREADS] [DAD_SEAM_LDS_BYTES]   the launch (0 when refused)
- *   [DAD_SEAM_TILE]       the first conv's tile (0 or 1), whose summation order the launch keeps; -1 when refused
- *   [DAD_SEAM_UNITS]      8-channel units it multiplies (1: transition_dim <= 8, 2)
- *   [DAD_SEAM_SPT]        samples of one 32-row tile (32 / horizon); 0 when refused
- *   [DAD_SEAM_LAST]       samples in the last tile (1 .. DAD_SEAM_SPT); 0 when refused
- *   [DAD_SEAM_BUFFERS]    which allowed relation of seam_buffers_ok holds: DAD_SEAM_BUF_APART (final_act overlaps neither
- *                         buffer the launch writes), DAD_SEAM_BUF_DST (it is the conv's dst), DAD_SEAM_BUF_RDST (it is the
- *                         ride's); -1 when refused
- *   [DAD_SEAM_DIM] [DAD_SEAM_TILE0]   the instantiation conv_seam_f32<dim, tile0>; 0 / -1 when refused */
-#define DAD_SEAM_TAKEN 0
-#define DAD_SEAM_REASON 1
-#define DAD_SEAM_GRID 2
-#define DAD_SEAM_THREADS 3
-#define DAD_SEAM_LDS_BYTES 4
-#define DAD_SEAM_TILE 5
-#define DAD_SEAM_UNITS 6
-#define DAD_SEAM_SPT 7
-#define DAD_SEAM_LAST 8
-#define DAD_SEAM_BUFFERS 9
-#define DAD_SEAM_DIM 10
-#define DAD_SEAM_TILE0 11
-#define DAD_SEAM_INTS 12
-#define DAD_SEAM_BUF_APART 0
-#define DAD_SEAM_BUF_DST 1
-#define DAD_SEAM_BUF_RDST 2
+ * options.  Host logic only, no device call; the model needs no weights.  out[DAD_SEAM_INTS]. */
+#define DAD_SEAM_INTS_LIST(F) \
+    F(DAD_SEAM_TAKEN, taken, 1, "1 / 0") \
+    F(DAD_SEAM_REASON, reason, 1, "0 = taken, else the first condition that refuses it; dad_debug_seam_reason names it") \
+    F(DAD_SEAM_GRID, grid, 1, "the launch: blocks (0 when refused)") \
+    F(DAD_SEAM_THREADS, threads, 1, "... threads (0 when refused)") \
+    F(DAD_SEAM_LDS_BYTES, lds_bytes, 1, "... LDS (0 when refused)") \
+    F(DAD_SEAM_TILE, tile, 1, "the first conv's tile (0 or 1), whose summation order the launch keeps; -1 when refused") \
+    F(DAD_SEAM_UNITS, units, 1, "8-channel units it multiplies (1: transition_dim <= 8, 2)") \
+    F(DAD_SEAM_SPT, spt, 1, "samples of one 32-row tile (32 / horizon); 0 when refused") \
+    F(DAD_SEAM_LAST, last, 1, "samples in the last tile (1 .. spt); 0 when refused") \
+    F(DAD_SEAM_BUFFERS, buffers, 1, "which allowed relation of seam_buffers_ok holds, DAD_SEAM_BUF_*; -1 when refused") \
+    F(DAD_SEAM_DIM, dim, 1, "the instantiation conv_seam_f32<dim, tile0>: dim; 0 when refused") \
+    F(DAD_SEAM_TILE0, tile0, 1, "... tile0; -1 when refused")
+DAD_LAYOUT(DAD_SEAM_INTS, 0);
+#define DAD_SEAM_BUFS_LIST(F) \
+    F(DAD_SEAM_BUF_APART, apart, 1, "final_act overlaps neither buffer the launch writes") \
+    F(DAD_SEAM_BUF_DST, dst, 1, "it is the conv's dst") \
+    F(DAD_SEAM_BUF_RDST, rdst, 1, "it is the ride's")
+DAD_LAYOUT(DAD_SEAM_BUFS, 0);
 int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out);
 const char* dad_debug_seam_reason(int32_t reason);
 /* The kernels of one family in the library's own registry: the table every launch looks its kernel up in (no device
- * call).  Writes min(capacity, *needed_out) int32 values to `out`: [0] the number of kernels, [1] the ints of one key,
- * then the keys —
- *   DAD_FAMILY_GEMM   conv_gemm_f32   (tile cfg, taps, stride, flag word as above)
- *   DAD_FAMILY_CC     conv_cc         (taps, stride, riding 1x1 conv, big, rows per tile, windowed)
- *   DAD_FAMILY_CCW    conv_ccw        (taps, stride, riding 1x1 conv, ride_in, rows per tile)
- *   DAD_FAMILY_HALO8  conv_halo8_f32  (tile cfg, riding 1x1 conv)
- *   DAD_FAMILY_SEAM   conv_seam_f32   (dim, the first conv's tile is 0)
- *   DAD_FAMILY_WGRAD  conv_wgrad      (taps, tile as DAD_BP_TILE, windowed) */
-#define DAD_FAMILY_GEMM 0
-#define DAD_FAMILY_CC 1
-#define DAD_FAMILY_CCW 2
-#define DAD_FAMILY_HALO8 3
-#define DAD_FAMILY_SEAM 4
-#define DAD_FAMILY_WGRAD 5
-#define DAD_FAMILIES 6
+ * call): the header, then the keys. */
+#define DAD_KL_HEADER_LIST(F) \
+    F(DAD_KL_KERNELS, kernels, 1, "keys that follow") \
+    F(DAD_KL_KEY_INTS, key_ints, 1, "ints of one key")
+DAD_LAYOUT(DAD_KL_HEADER, 0);
+#define DAD_FAMILIES_LIST(F) \
+    F(DAD_FAMILY_GEMM, gemm, 1, "conv_gemm_f32   (tile cfg, taps, stride, flag word as DAD_FP_REC_FLAGS)") \
+    F(DAD_FAMILY_CC, cc, 1, "conv_cc         (taps, stride, riding 1x1 conv, big, rows per tile, windowed)") \
+    F(DAD_FAMILY_CCW, ccw, 1, "conv_ccw        (taps, stride, riding 1x1 conv, ride_in, rows per tile)") \
+    F(DAD_FAMILY_HALO8, halo8, 1, "conv_halo8_f32  (tile cfg, riding 1x1 conv)") \
+    F(DAD_FAMILY_SEAM, seam, 1, "conv_seam_f32   (dim, the first conv's tile is 0)") \
+    F(DAD_FAMILY_WGRAD, wgrad, 1, "conv_wgrad      (taps, tile as DAD_BP_TILE, windowed)")
+DAD_LAYOUT(DAD_FAMILIES, 0);
 #define DAD_KERNEL_KEY_MAX 6
 int dad_debug_kernel_list(int32_t family, int32_t* out, int32_t capacity, int32_t* needed_out);
 
@@ -790,26 +747,21 @@ void dad_optim_destroy(dad_optim* o);
  * neither grad nor ema. */
 int dad_optim_step(dad_optim* o, const dad_optim_tensor* tensors, int32_t n, const dad_optim_args* a, dad_stream_t s);
 /* The work split dad_optim_step replays for tensors of these sizes (csrc/host_plan.hpp: optim_plan; host-side query,
- * no device call).  Writes min(capacity, *needed_out) int32 values to `out`:
- *   [DAD_OS_CHUNK]        elements per chunk (a multiple of 4)
- *   [DAD_OS_CHUNKS]       chunks = records that follow from DAD_OS_HEADER on
- *   [DAD_OS_GRID]         blocks of each of the two kernels (at most 2048)
- *   [DAD_OS_PARTIALS]     partial square sums (one per block)
- *   [DAD_OS_RECORD_INTS]  ints per record (DAD_OS_REC_*)
- * One record per chunk in chunk order: tensor, first element (its low 31 bits, then the bits above), elements, and
- * the block that owns the chunk (a block walks its chunks in this order). */
-#define DAD_OS_CHUNK 0
-#define DAD_OS_CHUNKS 1
-#define DAD_OS_GRID 2
-#define DAD_OS_PARTIALS 3
-#define DAD_OS_RECORD_INTS 4
-#define DAD_OS_HEADER 5
-#define DAD_OS_REC_TENSOR 0
-#define DAD_OS_REC_FIRST 1
-#define DAD_OS_REC_FIRST_HI 2
-#define DAD_OS_REC_COUNT 3
-#define DAD_OS_REC_BLOCK 4
-#define DAD_OS_REC_INTS 5
+ * no device call): one record per chunk in chunk order. */
+#define DAD_OS_HEADER_LIST(F) \
+    F(DAD_OS_CHUNK, chunk, 1, "elements per chunk (a multiple of 4)") \
+    F(DAD_OS_CHUNKS, chunks, 1, "chunks = records") \
+    F(DAD_OS_GRID, grid, 1, "blocks of each of the two kernels (at most 2048)") \
+    F(DAD_OS_PARTIALS, partials, 1, "partial square sums (one per block)") \
+    F(DAD_OS_RECORD_INTS, record_ints, 1, "ints per record")
+DAD_LAYOUT(DAD_OS_HEADER, 0);
+#define DAD_OS_REC_INTS_LIST(F) \
+    F(DAD_OS_REC_TENSOR, tensor, 1, "tensor") \
+    F(DAD_OS_REC_FIRST, first, 1, "first element: its low 31 bits") \
+    F(DAD_OS_REC_FIRST_HI, first_hi, 1, "... the bits above") \
+    F(DAD_OS_REC_COUNT, count, 1, "elements") \
+    F(DAD_OS_REC_BLOCK, block, 1, "the block that owns the chunk (a block walks its chunks in this order)")
+DAD_LAYOUT(DAD_OS_REC_INTS, 0);
 int dad_debug_optim_plan(const int64_t* numel, int32_t n, int32_t* out, int32_t capacity, int32_t* needed_out);
 
 #ifdef __cplusplus

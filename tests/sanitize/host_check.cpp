@@ -13,6 +13,26 @@
 
 using namespace dadhost;
 
+// The report layouts of include/dad.h against literal offsets (independent of dad_debug_report_layout, which
+// tests/test_host_logic.py holds against tests/golden/report_layouts.json): per report the first and the last field, the
+// lengths, and the four fields that span more than one int.
+static_assert(DAD_FP_MODE == 0 && DAD_FP_FINAL_KERNEL == 7 && DAD_FP_HEADER == 8 && DAD_FP_REC_CONV == 0 && DAD_FP_REC_FAMILY == 12 &&
+              DAD_FP_REC_INTS == 13 && DAD_FP_CC_CONV == 0 && DAD_FP_CC_RES_KIND == 12 && DAD_FP_CC_INTS == 13, "DAD_FP_*");
+static_assert(DAD_H8_HEADER == 2 && DAD_H8_CONV == 0 && DAD_H8_PART_TILE == 13 && DAD_H8_INTS == 14, "DAD_H8_*");
+static_assert(DAD_SEAM_TAKEN == 0 && DAD_SEAM_TILE0 == 11 && DAD_SEAM_INTS == 12 && DAD_SEAM_BUF_RDST == 2, "DAD_SEAM_*");
+static_assert(DAD_PP_FORM == 0 && DAD_PP_REFUSED == 5 && DAD_PP_INTS == 6 && DAD_PP_GEMM == 2, "DAD_PP_*");
+static_assert(DAD_BP_WGRADS == 0 && DAD_BP_TILE == 7 && DAD_BP_TAPS_TILE == 11 && DAD_BP_FWD == 31 && DAD_BP_DGRAD == 51 &&
+              DAD_BP_RECORD_INTS == 71 && DAD_BP_HEADER == 72 && DAD_BP_REC_TAPS == 0 && DAD_BP_REC_LAST_CHUNKS == 8 && DAD_BP_REC_INTS == 9,
+              "DAD_BP_*");
+static_assert(DAD_BS_STEPS == 0 && DAD_BS_DX == 9 && DAD_BS_HEADER == 12 && DAD_BS_KIND == 0 && DAD_BS_BIAS_ROWS == 1 && DAD_BS_WG_TAPS == 1 &&
+              DAD_BS_WG_LAST_CHUNKS == 24 && DAD_BS_DG_WRITE == 3 && DAD_BS_GN_C == 8 && DAD_BS_RS_TO_X == 3 && DAD_BS_CL_WRITE == 5 &&
+              DAD_BS_REC_INTS == 25 && DAD_BS_K_COLS == 5, "DAD_BS_*");
+static_assert(DAD_OP_LOSS_BLOCKS == 0 && DAD_OP_LAUNCHES == 7 && DAD_OP_HEADER == 8 && DAD_OP_REC_MODE == 0 && DAD_OP_REC_KSLICE == 10 &&
+              DAD_OP_REC_INTS == 11 && DAD_OP_TG_DTEMB == 8, "DAD_OP_*");
+static_assert(DAD_OS_CHUNK == 0 && DAD_OS_RECORD_INTS == 4 && DAD_OS_HEADER == 5 && DAD_OS_REC_TENSOR == 0 && DAD_OS_REC_BLOCK == 4 &&
+              DAD_OS_REC_INTS == 5, "DAD_OS_*");
+static_assert(DAD_FAMILY_GEMM == 0 && DAD_FAMILY_WGRAD == 5 && DAD_FAMILIES == 6, "DAD_FAMILY_*");
+
 static int g_failures = 0;
 #define CHECK(cond, ...)                                                       \
     do {                                                                       \

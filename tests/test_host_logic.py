@@ -184,6 +184,59 @@ def test_planner_and_kernel_registry_agree():
     assert lib.dad_debug_kernel_list(len(_engine.KERNEL_FAMILIES), None, 0, C.byref(need)) == -1       # no such family
 
 
+def test_report_layouts_are_the_ones_every_reader_was_written_against():
+    """The plan reports are the instrument the censuses and the path tests read plans through, and the binding decodes
+    them by the field lists the library exports (dad_debug_report_layout), so a field that moved would move silently.
+    tests/golden/report_layouts.json holds every DAD_{FP,BP,BS,OP,H8,SEAM,PP,OS}_* constant as include/dad.h defined them
+    by hand before the layouts were stated as lists: each is rebuilt from the export — a field's offset is the sum of the
+    spans before it, a section's length constant the sum of all its spans — and must be there with that value."""
+    from dynamics_aware_diffusion_amd import _engine
+    lib = _engine.load_library()
+    assert lib.dad_debug_report_layout(-1, 0) is None and lib.dad_debug_report_layout(0, -1) is None
+    assert lib.dad_debug_report_layout(1000, 0) is None and lib.dad_debug_report_layout(0, 1000) is None
+    layouts = _engine.report_layouts()
+    rebuilt = {}
+    for length, fields in layouts.items():
+        names = [name for _, name, _ in fields if name != "_"]
+        assert len(names) == len(set(names)), f"{length}: a field name twice"
+        at = 0
+        for constant, _, span in fields:
+            assert span >= 1 and rebuilt.setdefault(constant, at) == at, (length, constant)
+            at += span
+        assert rebuilt.setdefault(length, at) == at, length
+    with open(os.path.join(GOLDEN, "report_layouts.json")) as fh:
+        pinned = json.load(fh)
+    assert len(pinned) == 213
+    assert {k: rebuilt.get(k) for k in pinned} == pinned
+    spans = {c: s for fields in layouts.values() for c, n, s in fields if s != 1 and n != "_"}
+    assert spans == {"DAD_BP_TILE": 4, "DAD_BP_TAPS_TILE": 20, "DAD_BP_FWD": 20, "DAD_BP_DGRAD": 20}
+
+
+def test_every_report_says_the_record_length_its_layout_states():
+    """The header field ``record_ints`` of each report with records, read from real reports (engines without weights or
+    a device), is the length of the record section the export gives: of every kind of record the report holds."""
+    from dynamics_aware_diffusion_amd import _engine
+    length = lambda section: _engine._fields(section)[1]
+    eng = _engine.HipEngine(transition_dim=6, dim=32, channels=(32, 64, 128), horizon=32, n_timesteps=10, training=True)
+    lib, h = eng.lib, eng._h
+
+    def record_ints(header, fn, *args):
+        return _engine._decode(header, _engine._fetch(fn, *args))["record_ints"]
+
+    assert record_ints("DAD_BP_HEADER", lib.dad_debug_backward_plan, h, 4) == length("DAD_BP_REC_INTS")
+    steps = record_ints("DAD_BS_HEADER", lib.dad_debug_backward_steps, h, 4)
+    kinds = _engine._names("DAD_BS_KINDS")
+    assert len(kinds) == 6 and {length(f"DAD_BS_{kind.upper()}_INTS") for kind in kinds} == {steps} == {length("DAD_BS_REC_INTS")}
+    assert record_ints("DAD_OP_HEADER", lib.dad_debug_objective_plan, h, 4) == length("DAD_OP_REC_INTS")
+    assert eng.forward_plan(1)["small"] and not eng.forward_plan(256)["small"]
+    assert record_ints("DAD_FP_HEADER", lib.dad_debug_forward_plan, h, 1, 0) == length("DAD_FP_CC_INTS")
+    assert record_ints("DAD_FP_HEADER", lib.dad_debug_forward_plan, h, 256, 0) == length("DAD_FP_REC_INTS")
+    assert eng.halo8_plan(1024), "no conv_halo8_f32 launch: the record length below would be read from an empty report"
+    assert record_ints("DAD_H8_HEADER", lib.dad_debug_halo8_plan, h, 1024, 0) == length("DAD_H8_INTS")
+    import ctypes as C
+    assert record_ints("DAD_OS_HEADER", lib.dad_debug_optim_plan, (C.c_int64 * 2)(5000, 7), 2) == length("DAD_OS_REC_INTS")
+
+
 def _pointmaze_cfg():
     from dynamics_aware_diffusion_amd import _engine
     cfg = _engine.DadCfg()
