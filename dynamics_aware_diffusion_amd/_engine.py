@@ -12,6 +12,7 @@ import math
 import os
 from typing import Dict, Mapping, Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,6 +38,36 @@ class DadStepArgs(C.Structure):
         ("guide_grad", C.c_void_p), ("guide_weight", C.c_float),
         ("mean_out", C.c_void_p), ("eps_out", C.c_void_p),
     ]
+
+
+class DadSamplerCoef(C.Structure):
+    _fields_ = [("t", C.c_int32)] + [(k, C.c_float) for k in (
+        "c_recip", "c_recipm1", "guide_x0", "coef_x0", "coef_xt", "guide_mean", "sigma")]
+
+
+SAMPLER_COEF_FIELDS = tuple(name for name, _ in DadSamplerCoef._fields_[1:])
+# numpy view of an array of dad_sampler_coef (32 bytes, no padding)
+SAMPLER_COEF_DTYPE = np.dtype([("t", "<i4")] + [(k, "<f4") for k in SAMPLER_COEF_FIELDS])
+
+
+def pack_sampler_steps(table: Mapping[str, "np.ndarray"], order: Optional[Sequence[int]] = None) -> "np.ndarray":
+    """Rows ``order`` (default: all, as given) of a coefficient table such as ``models.diffusion.ddim_table``
+    returns — ``tau`` and one float64 array per field of ``dad_sampler_coef`` — as an array of that struct.  This is
+    the one rounding to fp32."""
+    tau = np.asarray(table["tau"], dtype=np.int64)
+    idx = np.arange(tau.shape[0]) if order is None else np.asarray(order, dtype=np.int64)
+    out = np.zeros(idx.shape[0], dtype=SAMPLER_COEF_DTYPE)
+    out["t"] = tau[idx]
+    for k in SAMPLER_COEF_FIELDS:
+        out[k] = np.asarray(table[k], dtype=np.float64)[idx]
+    return out
+
+
+def _steps_array(steps, what: str) -> "np.ndarray":
+    arr = np.ascontiguousarray(steps)
+    if arr.dtype != SAMPLER_COEF_DTYPE or arr.ndim != 1:
+        raise TypeError(f"{what} must be a 1-d array of SAMPLER_COEF_DTYPE (pack_sampler_steps)")
+    return arr
 
 
 class DadProjectArgs(C.Structure):
@@ -101,6 +132,13 @@ ABI = {
                                   C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32,
                                   C.POINTER(DadProjectArgs), C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),
+    "dad_sampler_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.POINTER(DadStepArgs), C.c_int32, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "dad_sampler_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32,
+                                   C.POINTER(DadProjectArgs), C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
     "dad_project": (C.c_int, [C.POINTER(DadProjectArgs), C.c_float, C.c_void_p, C.c_int32,
                               C.c_int32, C.c_void_p]),
     "dad_fill_normal": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
@@ -543,6 +581,32 @@ class HipEngine:
                      mean_out: Optional[torch.Tensor] = None,
                      eps_out: Optional[torch.Tensor] = None, update_x: bool = True) -> None:
         """In-place reverse step on ``x`` (see dad_denoise_step in include/dad.h)."""
+        B, a = self._step_args(x, noise, seed, row_offset, draw, cond0, guide_grad, guide_weight, mean_out, eps_out)
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_denoise_step(
+                self._h, x.data_ptr(), int(t), B, C.byref(a), int(not update_x), ws.data_ptr(),
+                ws.numel() * 4, self._stream()))
+
+    def sampler_step(self, x: torch.Tensor, coef, *, noise: Optional[torch.Tensor] = None,
+                     seed: int = 0, row_offset: int = 0, draw: int = 0,
+                     cond0: Optional[torch.Tensor] = None,
+                     guide_grad: Optional[torch.Tensor] = None, guide_weight: float = 0.0,
+                     mean_out: Optional[torch.Tensor] = None,
+                     eps_out: Optional[torch.Tensor] = None, update_x: bool = True) -> None:
+        """``denoise_step`` with the step given by its coefficients: ``coef`` is one element of
+        ``pack_sampler_steps`` (see dad_sampler_step in include/dad.h)."""
+        one = _steps_array(np.asarray(coef).reshape(-1), "coef")
+        if one.shape[0] != 1:
+            raise ValueError("sampler_step takes one step")
+        B, a = self._step_args(x, noise, seed, row_offset, draw, cond0, guide_grad, guide_weight, mean_out, eps_out)
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_sampler_step(
+                self._h, x.data_ptr(), one.ctypes.data, B, C.byref(a), int(not update_x), ws.data_ptr(),
+                ws.numel() * 4, self._stream()))
+
+    def _step_args(self, x, noise, seed, row_offset, draw, cond0, guide_grad, guide_weight, mean_out, eps_out):
         B = self._traj(x)
         a = DadStepArgs()
         for name, ten in (("noise", noise), ("guide_grad", guide_grad), ("mean_out", mean_out),
@@ -560,11 +624,7 @@ class HipEngine:
             a.cond0 = cond0.data_ptr()
             a.cond_per_row = int(rows == B and B > 1)
         a.guide_weight = float(guide_weight)
-        ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.dad_denoise_step(
-                self._h, x.data_ptr(), int(t), B, C.byref(a), int(not update_x), ws.data_ptr(),
-                ws.numel() * 4, self._stream()))
+        return B, a
 
     def sample_loop(self, x: torch.Tensor, n_steps: int, *,
                     noise_stack: Optional[torch.Tensor] = None, seed: int = 0,
@@ -572,6 +632,41 @@ class HipEngine:
                     projection: Optional["ProjectionState"] = None,
                     proj_alphas: Optional[Sequence[float]] = None,
                     use_graph: bool = False) -> None:
+        B, cond_ptr, per_row, pa = self._loop_args(x, n_steps, noise_stack, cond0, projection)
+        alphas = None
+        if projection is not None:
+            alphas = (C.c_float * self.n_timesteps)(*[float(a) for a in proj_alphas])
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_sample_loop(
+                self._h, x.data_ptr(), int(n_steps), B, _ptr(noise_stack), int(seed),
+                int(row_offset), cond_ptr, per_row, pa, alphas, int(use_graph), ws.data_ptr(),
+                ws.numel() * 4, self._stream()))
+
+    def sampler_loop(self, x: torch.Tensor, steps, *,
+                     noise_stack: Optional[torch.Tensor] = None, seed: int = 0,
+                     row_offset: int = 0, cond0: Optional[torch.Tensor] = None,
+                     projection: Optional["ProjectionState"] = None,
+                     proj_alphas: Optional[Sequence[float]] = None,
+                     use_graph: bool = False) -> None:
+        """``sample_loop`` over caller-given steps: ``steps`` is ``pack_sampler_steps`` in execution order, and so are
+        ``proj_alphas`` and ``noise_stack`` (see dad_sampler_loop in include/dad.h)."""
+        arr = _steps_array(steps, "steps")
+        n_steps = int(arr.shape[0])
+        B, cond_ptr, per_row, pa = self._loop_args(x, n_steps, noise_stack, cond0, projection)
+        alphas = None
+        if projection is not None:
+            if proj_alphas is None or len(proj_alphas) != n_steps:
+                raise ValueError("proj_alphas must hold one strength per step, in execution order")
+            alphas = (C.c_float * n_steps)(*[float(a) for a in proj_alphas])
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_sampler_loop(
+                self._h, x.data_ptr(), arr.ctypes.data, n_steps, B, _ptr(noise_stack), int(seed),
+                int(row_offset), cond_ptr, per_row, pa, alphas, int(use_graph), ws.data_ptr(),
+                ws.numel() * 4, self._stream()))
+
+    def _loop_args(self, x, n_steps, noise_stack, cond0, projection):
         B = self._traj(x)
         cond_ptr, per_row = None, 0
         if cond0 is not None:
@@ -584,17 +679,11 @@ class HipEngine:
             _require_device(noise_stack, "noise_stack")
             if tuple(noise_stack.shape) != (n_steps, B, self.horizon, self.transition_dim):
                 raise RuntimeError("noise_stack must be (n_steps, B, H, td)")
-        pa, alphas = None, None
+        pa = None
         if projection is not None:
             projection._check_x(x)
             pa = C.byref(projection.args)
-            alphas = (C.c_float * self.n_timesteps)(*[float(a) for a in proj_alphas])
-        ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.dad_sample_loop(
-                self._h, x.data_ptr(), int(n_steps), B, _ptr(noise_stack), int(seed),
-                int(row_offset), cond_ptr, per_row, pa, alphas, int(use_graph), ws.data_ptr(),
-                ws.numel() * 4, self._stream()))
+        return B, cond_ptr, per_row, pa
 
     def fill_normal(self, x: torch.Tensor, seed: int, row_offset: int = 0, draw: int = 0) -> None:
         _require_device(x, "x")

@@ -671,6 +671,7 @@ __global__ __launch_bounds__(CC_THREADS) void final_cc_kernel(const FinalCcParam
         if (p.eps_out != nullptr) p.eps_out[idx] = out;
         if (p.x_out_disabled && p.mean_out == nullptr) continue;
         float x0 = p.predict_epsilon ? p.c_recip * xv - p.c_recipm1 * out : out;
+        if (p.guide != nullptr) x0 = fmaf(p.guide_x0, p.guide[idx], x0);
         if (p.clip_denoised) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
         float mean = p.coef1 * x0 + p.coef2 * xv;
         if (p.guide != nullptr) mean = mean + p.guide_scale * p.guide[idx];

@@ -49,7 +49,8 @@ struct SeamParams {
 // Roundings as that kernel compiles: hipcc forms its two-term sums from v_pk_mul_f32 products — c_recip * x -
 // c_recipm1 * out and coef1 * x0 + coef2 * x are two products and an add, no FMA — and contracts guide and noise
 // (v_fmac_f32).  Here, with one output per thread at dim 128, it contracted the former as well (1 ulp of x on a fifth
-// of the elements): they run with contraction off, the latter are written as fmaf.
+// of the elements): they run with contraction off, the latter are written as fmaf.  The guide's shift of x0 (the DDIM
+// form of guidance, FinalParams.guide_x0) is an explicit fmaf in all three copies: one rounding, whatever is contracted.
 __device__ __forceinline__ bool posterior_finish(const FinalParams& p, const float* bl, long n, int td, int b, int l, int j,
                                                  float acc, float xv, float zpre, float& xn) {
     const long idx = n * td + j;
@@ -60,6 +61,7 @@ __device__ __forceinline__ bool posterior_finish(const FinalParams& p, const flo
     {
 #pragma clang fp contract(off)
         if (p.predict_epsilon) x0 = p.c_recip * xv - p.c_recipm1 * out;
+        if (p.guide != nullptr) x0 = fmaf(p.guide_x0, p.guide[idx], x0);
         if (p.clip_denoised) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
         mean = p.coef1 * x0 + p.coef2 * xv;
     }

@@ -57,6 +57,7 @@ struct GraphKey {
     int force_tile, flags;    // tile / split-K / fusion hooks change the captured launches
     uint64_t row_offset;
     uint64_t alpha_hash;      // projection strengths are baked into the captured launches
+    uint64_t steps_hash;      //   and so are the coefficients of every step (the sampler)
     bool operator<(const GraphKey& o) const {
         return std::memcmp(this, &o, sizeof(GraphKey)) < 0;
     }
@@ -538,9 +539,14 @@ int run_conv_cc(dad_model* m, const CcPlan& cc, int i, const float* xext, float*
     return DAD_OK;
 }
 
-// final_conv[1] and the posterior update of step t on the trajectories x (dad_step_args `a`), as kernel parameters
-void posterior_params(dad_model* m, const FwdPlan& f, float* x, int t, const dad_step_args* a, int x_out_disabled,
-                      bool seed_from_device, float* ws, dad::FinalParams& p) {
+// The ancestral step at t of the loaded schedule (host_plan.hpp ancestral_coef)
+dad_sampler_coef schedule_step(const dad_model* m, int t) {
+    return ancestral_coef(t, m->sched[0][t], m->sched[1][t], m->sched[2][t], m->sched[3][t], m->sched[4][t]);
+}
+
+// final_conv[1] and the posterior update of step `s` on the trajectories x (dad_step_args `a`), as kernel parameters
+void posterior_params(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coef& s, const dad_step_args* a,
+                      int x_out_disabled, bool seed_from_device, float* ws, dad::FinalParams& p) {
     const dad_cfg& c = m->cfg;
     const Plan& plan = f.train ? m->tplan : m->plan;
     p.act = ws + plan.bufs[plan.final_act].offset * (long)f.batch;
@@ -552,23 +558,23 @@ void posterior_params(dad_model* m, const FwdPlan& f, float* x, int t, const dad
     p.guide = (a->guide_grad && a->guide_weight > 0.0f) ? a->guide_grad : nullptr;
     p.mean_out = a->mean_out; p.eps_out = a->eps_out;
     p.x_out_disabled = x_out_disabled;
-    const float lv = m->sched[4][t];
-    p.c_recip = m->sched[0][t]; p.c_recipm1 = m->sched[1][t];
-    p.coef1 = m->sched[2][t]; p.coef2 = m->sched[3][t];
-    p.sigma = t == 0 ? 0.0f : expf(0.5f * lv);
-    p.guide_scale = a->guide_weight * expf(lv);
+    p.c_recip = s.c_recip; p.c_recipm1 = s.c_recipm1;
+    p.coef1 = s.coef_x0; p.coef2 = s.coef_xt;
+    p.sigma = s.sigma;
+    p.guide_scale = a->guide_weight * s.guide_mean;
+    p.guide_x0 = a->guide_weight * s.guide_x0;
     p.seed = a->seed;
     p.elem_offset = a->row_offset * (uint64_t)traj_horizon(*m) * (uint64_t)c.transition_dim;
     p.draw = a->draw;
     p.seed_dev = seed_from_device ? (const unsigned long long*)m->d_rng : nullptr;
 }
 
-// The seam of dad_sample_loop (conv_seam.hpp, plan_seam): the posterior update of step `t` and, on the new x, the
-// first launch of the evaluation at t - 1.
+// The seam of the sampling loop (conv_seam.hpp, plan_seam): the posterior update of one step and, on the new x, the
+// first launch of the next step's evaluation.
 struct SeamCall {
     const SeamPlan* plan;
     float* x;
-    int t;                       // the step whose posterior update the launch carries
+    const dad_sampler_coef* s;   // the step whose posterior update the launch carries
     const dad_step_args* a;      //   and its arguments
     bool seed_from_device;
 };
@@ -576,7 +582,7 @@ int launch_seam(dad_model* m, const FwdPlan& f, const SeamCall& sc, int t_conv, 
     const FwdLaunch& l = f.launches[0];
     const ConvOp& op = m->plan.convs[l.conv];
     dad::SeamParams q{};
-    posterior_params(m, f, sc.x, sc.t, sc.a, 0, sc.seed_from_device, ws, q.f);
+    posterior_params(m, f, sc.x, *sc.s, sc.a, 0, sc.seed_from_device, ws, q.f);
     q.c = conv_params(m, op, l.g, f.batch, conv_io(m, f, l, sc.x, ws, t_conv, nullptr, nullptr));
     q.c.xswz = sc.plan->xswz;
     q.units = sc.plan->units;
@@ -629,8 +635,9 @@ int run_unet(dad_model* m, const FwdPlan& f, const float* x, int t, float* ws, h
 }
 
 // final_conv[1] and the posterior update (or, `eps_only`, the network output alone), on the grid `f` planned
-int run_final(dad_model* m, const FwdPlan& f, float* x, const float* x_ro, int t, const dad_step_args* a,
-              int x_out_disabled, float* eps_only, float* ws, hipStream_t st, bool seed_from_device = false) {
+int run_final(dad_model* m, const FwdPlan& f, float* x, const float* x_ro, int t, const dad_sampler_coef* s,
+              const dad_step_args* a, int x_out_disabled, float* eps_only, float* ws, hipStream_t st,
+              bool seed_from_device = false) {
     const dad_cfg& c = m->cfg;
     const int batch = f.batch;
     dad::FinalParams p{};
@@ -644,7 +651,7 @@ int run_final(dad_model* m, const FwdPlan& f, float* x, const float* x_ro, int t
         p.eps_out = eps_only;
         p.x_out_disabled = 1;
     } else {
-        posterior_params(m, f, x, t, a, x_out_disabled, seed_from_device, ws, p);
+        posterior_params(m, f, x, *s, a, x_out_disabled, seed_from_device, ws, p);
     }
     const dim3 grid(f.final_gx, f.final_gy);
     if (f.cc.ok) {
@@ -697,6 +704,110 @@ int run_project(const dad_project_args* pa, float alpha, float* x, int batch, in
     else
         hipLaunchKernelGGL((dad::project_kernel<4, dad::PROJ_KP>), grid, dim3(64 * dad::PROJ_KP), q.lds_bytes, st, p);
     HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
+// One reverse step `s` (already checked) on the plan `f`: the body of dad_denoise_step and dad_sampler_step
+int sampler_step(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coef& s, const dad_step_args* args,
+                 int x_out_disabled, void* workspace, dad_stream_t stream) {
+    if (!x || !args || !workspace) return fail(DAD_E_INVALID, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;
+    if ((rc = run_unet(m, f, x, s.t, (float*)workspace, st)) != DAD_OK) return rc;
+    return run_final(m, f, x, nullptr, s.t, &s, args, x_out_disabled, nullptr, (float*)workspace, st);
+}
+
+// The sampling loop over `n_steps` checked steps in execution order (proj_alphas likewise), on the plan `f`: the body
+// of dad_sample_loop and dad_sampler_loop, and the one place a loop is captured and replayed.
+int sampler_loop(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coef* steps, int n_steps, int batch,
+                 const float* noise_stack, uint64_t seed, uint64_t row_offset, const float* cond0, int cond_per_row,
+                 const dad_project_args* proj, const float* proj_alphas, int use_graph, void* workspace,
+                 dad_stream_t stream) {
+    int rc;
+    if (!x || !workspace) return fail(DAD_E_INVALID, "null pointer");
+    if (proj && !proj_alphas) return fail(DAD_E_INVALID, "projection needs per-step alphas");
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;      // (before any capture: the replayed loop reads the tables)
+    const long step_elems = (long)batch * traj_horizon(*m) * m->cfg.transition_dim;
+
+    const bool seed_dev = use_graph && !m->profile && noise_stack == nullptr;
+    // The seam between two steps as one launch (plan_seam): iteration 0 runs the whole evaluation, every later one starts
+    // with the seam launch — the previous step's posterior update and this evaluation's first conv — and the last
+    // step ends with the posterior launch.
+    const SeamPlan seam = plan_seam(*m, f, proj != nullptr);
+    const bool seamed = seam.taken() && n_steps > 1;
+    auto enqueue_all = [&](hipStream_t st) -> int {
+        dad_step_args prev{};
+        for (int j = 0; j < n_steps; ++j) {
+            const int t = steps[j].t;
+            dad_step_args a{};
+            a.noise = noise_stack ? noise_stack + (long)j * step_elems : nullptr;
+            a.seed = seed; a.row_offset = row_offset; a.draw = (uint64_t)(j + 1);
+            a.cond0 = cond0; a.cond_per_row = cond_per_row;
+            const SeamCall sc{&seam, x, j > 0 ? &steps[j - 1] : nullptr, &prev, seed_dev};
+            int r = run_unet(m, f, x, t, (float*)workspace, st, nullptr, nullptr, seamed && j > 0 ? &sc : nullptr);
+            if (r != DAD_OK) return r;
+            prev = a;
+            if (seamed && j + 1 < n_steps) continue;
+            if ((r = run_final(m, f, x, nullptr, t, &steps[j], &a, 0, nullptr, (float*)workspace, st, seed_dev)) != DAD_OK) return r;
+            if (proj && (r = run_project(proj, proj_alphas[j], x, batch, traj_horizon(*m), st)) != DAD_OK)
+                return r;
+        }
+        return DAD_OK;
+    };
+
+    if (!use_graph || m->profile) return enqueue_all(st);
+
+    // Graph replay: the whole loop is one hipGraph keyed by every frozen pointer and scalar (the
+    // steps' coefficients by their hash).  With in-kernel noise the Philox key is read from device
+    // memory, written by a tiny kernel ahead of the replay, so a new seed does not need a new capture.
+    if (seed_dev) {
+        hipLaunchKernelGGL(dad::set_u64_kernel, dim3(1), dim3(1), 0, st,
+                           (unsigned long long*)m->d_rng, (unsigned long long)seed);
+        HIP_TRY(hipGetLastError());
+    }
+    GraphKey key{};
+    key.x = x; key.noise = noise_stack; key.cond = cond0; key.ws = workspace;
+    if (proj) {
+        key.P = proj->P; key.obs_mean = proj->obs_mean; key.obs_std = proj->obs_std;
+        key.act_mean = proj->act_mean; key.act_std = proj->act_std;
+        key.proj_scratch = proj->scratch;
+        key.state_dim = proj->state_dim; key.observation_dim = proj->observation_dim;
+        key.action_dim = proj->action_dim;
+    }
+    key.n_steps = n_steps; key.batch = batch; key.cond_per_row = cond_per_row;
+    key.force_tile = m->force_tile;
+    key.flags = (m->split_enabled ? 1 : 0) | (m->fuse_residual ? 2 : 0) | (m->xswz_enabled ? 4 : 0) |
+                (m->xcd_order ? 8 : 0) | (f.cc.ok ? 16 : 0) | (m->step_seam ? 32 : 0) | (m->split_target << 8);
+    key.row_offset = row_offset;
+    if (proj) key.alpha_hash = fnv1a_bytes(proj_alphas, (size_t)n_steps * sizeof(float));
+    key.steps_hash = sampler_steps_hash(steps, n_steps);
+    auto it = m->graphs.find(key);
+    if (it == m->graphs.end()) {
+        if (m->graphs.size() >= 16) {                 // bounded cache: drop everything, re-capture
+            // a replay may still be in flight on the caller's stream (or on another one the caller
+            // used earlier): wait for the device before destroying executable graphs
+            HIP_TRY(hipDeviceSynchronize());
+            for (auto& kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
+            m->graphs.clear();
+        }
+        // capture on a private stream: the caller's stream may be the null stream, which
+        // cannot be captured; nothing executes during capture.
+        if (!m->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeRelaxed));
+        rc = enqueue_all(m->cap_stream);
+        hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
+        if (rc != DAD_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (e != hipSuccess) return fail(DAD_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+        hipGraphExec_t exec = nullptr;
+        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (e != hipSuccess) return fail(DAD_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+        it = m->graphs.emplace(key, exec).first;
+    }
+    HIP_TRY(hipGraphLaunch(it->second, st));
     return DAD_OK;
 }
 
@@ -942,7 +1053,7 @@ int dad_unet_forward(dad_model* m, const float* x, int32_t t, float* out, int32_
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;
     if ((rc = run_unet(m, f, x, t, (float*)workspace, st)) != DAD_OK) return rc;
-    return run_final(m, f, nullptr, x, t, nullptr, 1, out, (float*)workspace, st);
+    return run_final(m, f, nullptr, x, t, nullptr, nullptr, 1, out, (float*)workspace, st);
 }
 
 int dad_unet_forward_rows(dad_model* m, const float* x, const int32_t* t_rows, float* out, int32_t batch,
@@ -954,7 +1065,7 @@ int dad_unet_forward_rows(dad_model* m, const float* x, const int32_t* t_rows, f
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;
     if ((rc = run_unet(m, f, x, 0, (float*)workspace, st, t_rows)) != DAD_OK) return rc;
-    return run_final(m, f, nullptr, x, 0, nullptr, 1, out, (float*)workspace, st);
+    return run_final(m, f, nullptr, x, 0, nullptr, nullptr, 1, out, (float*)workspace, st);
 }
 
 int dad_denoise_step(dad_model* m, float* x, int32_t t, int32_t batch, const dad_step_args* args,
@@ -963,11 +1074,18 @@ int dad_denoise_step(dad_model* m, float* x, int32_t t, int32_t batch, const dad
     FwdPlan f;
     int rc = check_ready(m, batch, t, workspace_bytes, true, f);
     if (rc != DAD_OK) return rc;
-    if (!x || !args || !workspace) return fail(DAD_E_INVALID, "null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;
-    if ((rc = run_unet(m, f, x, t, (float*)workspace, st)) != DAD_OK) return rc;
-    return run_final(m, f, x, nullptr, t, args, x_out_disabled, nullptr, (float*)workspace, st);
+    const dad_sampler_coef s = schedule_step(m, t);
+    return sampler_step(m, f, x, s, args, x_out_disabled, workspace, stream);
+}
+
+int dad_sampler_step(dad_model* m, float* x, const dad_sampler_coef* coef, int32_t batch, const dad_step_args* args,
+                     int32_t x_out_disabled, void* workspace, size_t workspace_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    int rc = check_sampler_steps(coef, 1, m->cfg.n_timesteps);
+    if (rc != DAD_OK) return rc;
+    FwdPlan f;
+    if ((rc = check_ready(m, batch, coef->t, workspace_bytes, true, f)) != DAD_OK) return rc;
+    return sampler_step(m, f, x, *coef, args, x_out_disabled, workspace, stream);
 }
 
 int dad_project(const dad_project_args* p, float alpha, float* x, int32_t batch, int32_t horizon,
@@ -991,97 +1109,30 @@ int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
     FwdPlan f;                  // one description for all n_steps evaluations (and for a capture of them)
     int rc = check_ready(m, batch, n_steps - 1, workspace_bytes, true, f);
     if (rc != DAD_OK) return rc;
-    if (!x || !workspace) return fail(DAD_E_INVALID, "null pointer");
     if (proj && !proj_alphas_host) return fail(DAD_E_INVALID, "projection needs per-step alphas");
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;      // (before any capture: the replayed loop reads the tables)
-    const long step_elems = (long)batch * traj_horizon(*m) * m->cfg.transition_dim;
+    // the ancestral sampler over the first n_steps entries of the loaded schedule, t = n_steps - 1 .. 0
+    std::vector<dad_sampler_coef> steps((size_t)n_steps);
+    std::vector<float> alphas(proj ? (size_t)n_steps : 0);
+    for (int j = 0; j < n_steps; ++j) {
+        steps[j] = schedule_step(m, n_steps - 1 - j);
+        if (proj) alphas[j] = proj_alphas_host[n_steps - 1 - j];
+    }
+    return sampler_loop(m, f, x, steps.data(), n_steps, batch, noise_stack, seed, row_offset, cond0, cond_per_row, proj,
+                        proj ? alphas.data() : nullptr, use_graph, workspace, stream);
+}
 
-    const bool seed_dev = use_graph && !m->profile && noise_stack == nullptr;
-    // The seam between two steps as one launch (plan_seam): step 0 runs the whole evaluation, every later one starts
-    // with the seam launch — the previous step's posterior update and this evaluation's first conv — and the last
-    // step ends with the posterior launch.
-    const SeamPlan seam = plan_seam(*m, f, proj != nullptr);
-    const bool seamed = seam.taken() && n_steps > 1;
-    auto enqueue_all = [&](hipStream_t st) -> int {
-        dad_step_args prev{};
-        for (int j = 0; j < n_steps; ++j) {
-            const int t = n_steps - 1 - j;
-            dad_step_args a{};
-            a.noise = noise_stack ? noise_stack + (long)j * step_elems : nullptr;
-            a.seed = seed; a.row_offset = row_offset; a.draw = (uint64_t)(j + 1);
-            a.cond0 = cond0; a.cond_per_row = cond_per_row;
-            const SeamCall sc{&seam, x, t + 1, &prev, seed_dev};
-            int r = run_unet(m, f, x, t, (float*)workspace, st, nullptr, nullptr, seamed && j > 0 ? &sc : nullptr);
-            if (r != DAD_OK) return r;
-            prev = a;
-            if (seamed && j + 1 < n_steps) continue;
-            if ((r = run_final(m, f, x, nullptr, t, &a, 0, nullptr, (float*)workspace, st, seed_dev)) != DAD_OK) return r;
-            if (proj && (r = run_project(proj, proj_alphas_host[t], x, batch, traj_horizon(*m), st)) != DAD_OK)
-                return r;
-        }
-        return DAD_OK;
-    };
-
-    if (!use_graph || m->profile) return enqueue_all(st);
-
-    // Graph replay: the whole T-step loop is one hipGraph keyed by every frozen pointer and
-    // scalar.  With in-kernel noise the Philox key is read from device memory, written by a
-    // tiny kernel ahead of the replay, so a new seed does not need a new capture.
-    if (seed_dev) {
-        hipLaunchKernelGGL(dad::set_u64_kernel, dim3(1), dim3(1), 0, st,
-                           (unsigned long long*)m->d_rng, (unsigned long long)seed);
-        HIP_TRY(hipGetLastError());
-    }
-    GraphKey key{};
-    key.x = x; key.noise = noise_stack; key.cond = cond0; key.ws = workspace;
-    if (proj) {
-        key.P = proj->P; key.obs_mean = proj->obs_mean; key.obs_std = proj->obs_std;
-        key.act_mean = proj->act_mean; key.act_std = proj->act_std;
-        key.proj_scratch = proj->scratch;
-        key.state_dim = proj->state_dim; key.observation_dim = proj->observation_dim;
-        key.action_dim = proj->action_dim;
-    }
-    key.n_steps = n_steps; key.batch = batch; key.cond_per_row = cond_per_row;
-    key.force_tile = m->force_tile;
-    key.flags = (m->split_enabled ? 1 : 0) | (m->fuse_residual ? 2 : 0) | (m->xswz_enabled ? 4 : 0) |
-                (m->xcd_order ? 8 : 0) | (f.cc.ok ? 16 : 0) | (m->step_seam ? 32 : 0) | (m->split_target << 8);
-    key.row_offset = row_offset;
-    if (proj) {
-        uint64_t hsh = 1469598103934665603ull;            // FNV-1a over the per-step alphas
-        for (int i = 0; i < n_steps; ++i) {
-            uint32_t bits;
-            std::memcpy(&bits, &proj_alphas_host[i], 4);
-            hsh = (hsh ^ bits) * 1099511628211ull;
-        }
-        key.alpha_hash = hsh;
-    }
-    auto it = m->graphs.find(key);
-    if (it == m->graphs.end()) {
-        if (m->graphs.size() >= 16) {                 // bounded cache: drop everything, re-capture
-            // a replay may still be in flight on the caller's stream (or on another one the caller
-            // used earlier): wait for the device before destroying executable graphs
-            HIP_TRY(hipDeviceSynchronize());
-            for (auto& kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-            m->graphs.clear();
-        }
-        // capture on a private stream: the caller's stream may be the null stream, which
-        // cannot be captured; nothing executes during capture.
-        if (!m->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeRelaxed));
-        rc = enqueue_all(m->cap_stream);
-        hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
-        if (rc != DAD_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) return fail(DAD_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-        hipGraphExec_t exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) return fail(DAD_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-        it = m->graphs.emplace(key, exec).first;
-    }
-    HIP_TRY(hipGraphLaunch(it->second, st));
-    return DAD_OK;
+int dad_sampler_loop(dad_model* m, float* x, const dad_sampler_coef* steps, int32_t n_steps, int32_t batch,
+                     const float* noise_stack, uint64_t seed, uint64_t row_offset,
+                     const float* cond0, int32_t cond_per_row, const dad_project_args* proj,
+                     const float* proj_alphas_host, int32_t use_graph, void* workspace,
+                     size_t workspace_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    int rc = check_sampler_steps(steps, n_steps, m->cfg.n_timesteps);
+    if (rc != DAD_OK) return rc;
+    FwdPlan f;
+    if ((rc = check_ready(m, batch, steps[0].t, workspace_bytes, true, f)) != DAD_OK) return rc;
+    return sampler_loop(m, f, x, steps, n_steps, batch, noise_stack, seed, row_offset, cond0, cond_per_row, proj,
+                        proj_alphas_host, use_graph, workspace, stream);
 }
 
 // ---------------------------------------------------------------------------------- training
@@ -1267,7 +1318,7 @@ int dad_unet_forward_train(dad_model* m, const float* x, const int32_t* row_inde
     if (rc != DAD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = run_unet(m, f, x, 0, (float*)saved, st, row_index, temb_rows)) != DAD_OK) return rc;
-    return run_final(m, f, nullptr, x, 0, nullptr, 1, out, (float*)saved, st);
+    return run_final(m, f, nullptr, x, 0, nullptr, nullptr, 1, out, (float*)saved, st);
 }
 
 // `pre`: the pass as the fused objective already planned it for this batch (nothing is planned twice per call);
@@ -1590,7 +1641,7 @@ int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_
     if ((rc = launch_time_gemm<dad::TG_FWD_ROWS>(g, tl[2], st)) != DAD_OK) return rc;
     // the denoiser's training forward on x_t (diffusion.py:272), every activation kept
     if ((rc = run_unet(m, f, q.xt, 0, (float*)saved, st, q.row_index, sv + o.rows)) != DAD_OK) return rc;
-    if ((rc = run_final(m, f, nullptr, q.xt, 0, nullptr, 1, sv + o.out, (float*)saved, st)) != DAD_OK) return rc;
+    if ((rc = run_final(m, f, nullptr, q.xt, 0, nullptr, nullptr, 1, sv + o.out, (float*)saved, st)) != DAD_OK) return rc;
     // 3. weighted L1 / L2 mean (diffusion.py:274-290)
     hipLaunchKernelGGL(dad::objective_loss_partial_kernel, dim3((unsigned)q.nblocks), dim3(dad::OBJ_THREADS), 0, st, q);
     hipLaunchKernelGGL(dad::objective_loss_final_kernel, dim3(1), dim3(dad::OBJ_THREADS), 0, st, q);

@@ -2089,5 +2089,45 @@ inline int optim_plan(const int64_t* numel, int n, OptimPlan& p) {
     return DAD_OK;
 }
 
+// ------------------------------------------------------------------ sampler steps (dad_sampler_step / dad_sampler_loop)
+// A reverse step is its dad_sampler_coef.  The ancestral sampler's step at `t`, from the five loaded schedule entries
+// at t (sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
+// posterior_log_variance_clipped): the tail kernels' scalars as dad_denoise_step has always formed them.
+inline dad_sampler_coef ancestral_coef(int t, float c_recip, float c_recipm1, float coef1, float coef2, float log_var) {
+    dad_sampler_coef s{};
+    s.t = t;
+    s.c_recip = c_recip; s.c_recipm1 = c_recipm1;
+    s.coef_x0 = coef1; s.coef_xt = coef2;
+    s.guide_x0 = 0.0f;
+    s.guide_mean = expf(log_var);
+    s.sigma = t == 0 ? 0.0f : expf(0.5f * log_var);
+    return s;
+}
+// Every refusal of steps that come from outside, before anything else is looked at.
+inline int check_sampler_steps(const dad_sampler_coef* steps, int n_steps, int n_timesteps) {
+    if (n_steps < 1) return fail(DAD_E_INVALID, "n_steps must be positive");
+    if (!steps) return fail(DAD_E_INVALID, "null sampler steps");
+    for (int i = 0; i < n_steps; ++i) {
+        const dad_sampler_coef& s = steps[i];
+        if (s.t < 0 || s.t >= n_timesteps)
+            return fail(DAD_E_RANGE, "index %d is out of bounds for the schedule of size %d", s.t, n_timesteps);
+        const float v[7] = {s.c_recip, s.c_recipm1, s.guide_x0, s.coef_x0, s.coef_xt, s.guide_mean, s.sigma};
+        for (float f : v)
+            if (!std::isfinite(f)) return fail(DAD_E_INVALID, "sampler step %d: a coefficient is not finite", i);
+        if (s.sigma < 0.0f) return fail(DAD_E_INVALID, "sampler step %d: sigma %g is negative", i, (double)s.sigma);
+    }
+    return DAD_OK;
+}
+// FNV-1a over bytes: the key of a captured loop hashes what the capture bakes into its launches
+inline uint64_t fnv1a_bytes(const void* data, size_t n, uint64_t h = 14695981039346656037ull) {
+    const unsigned char* p = static_cast<const unsigned char*>(data);
+    for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 1099511628211ull;
+    return h;
+}
+static_assert(sizeof(dad_sampler_coef) == 32, "dad_sampler_coef has no padding: its bytes are hashed");
+inline uint64_t sampler_steps_hash(const dad_sampler_coef* steps, int n_steps) {
+    return fnv1a_bytes(steps, (size_t)n_steps * sizeof(dad_sampler_coef));
+}
+
 }  // namespace dadhost
-#include "plan_report.hpp"      // the reports travel with the planner: last, since they read everything above
+#include "plan_report.hpp"     // the reports travel with the planner: last, since they read everything above

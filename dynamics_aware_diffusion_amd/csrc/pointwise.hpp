@@ -84,9 +84,12 @@ struct FinalParams {
     int32_t cond_per_row;
     int32_t predict_epsilon, clip_denoised;
     int32_t x_out_disabled;  // 1: only eps_out / mean_out are produced
-    float c_recip, c_recipm1, coef1, coef2;   // schedule scalars at t (diffusion.py:164-178)
+    // the step's dad_sampler_coef (include/dad.h); for the ancestral sampler, from the schedule at t:
+    float c_recip, c_recipm1, coef1, coef2;   // schedule scalars at t (diffusion.py:164-178); coef1 = coef_x0, coef2 = coef_xt
     float sigma;             // [t != 0] * exp(0.5 * log_var_t)
-    float guide_scale;       // guide_weight * exp(log_var_t)      (policies.py:97)
+    float guide_scale;       // guide_weight * guide_mean = guide_weight * exp(log_var_t)      (policies.py:97)
+    float guide_x0;          // guide_weight * (1 - abar_t) / sqrt(abar_t): the guide's shift of x0 before the clamp (the
+                             // DDIM form of classifier guidance; 0 for the ancestral sampler)
     uint64_t seed, elem_offset, draw;
     const unsigned long long* seed_dev;   // when set, the Philox key is read from device memory
                                           // (graph replays take a fresh seed without re-capture)
@@ -170,6 +173,7 @@ __global__ __launch_bounds__(256) void final_posterior_kernel(const FinalParams 
         if (p.eps_out != nullptr) p.eps_out[idx] = out;
         if (p.x_out_disabled && p.mean_out == nullptr) return;
         float x0 = p.predict_epsilon ? p.c_recip * xv - p.c_recipm1 * out : out;
+        if (p.guide != nullptr) x0 = fmaf(p.guide_x0, p.guide[idx], x0);
         if (p.clip_denoised) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
         float mean = p.coef1 * x0 + p.coef2 * xv;
         if (p.guide != nullptr) mean = mean + p.guide_scale * p.guide[idx];

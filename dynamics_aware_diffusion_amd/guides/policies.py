@@ -76,7 +76,8 @@ class GuidedPolicy(nn.Module):
     @torch.no_grad()
     def p_sample_with_guidance(self, x: torch.Tensor, t: torch.Tensor,
                                conditions: Optional[Dict[int, torch.Tensor]] = None) -> torch.Tensor:
-        """Mean (+ guidance) + noise, then inpainting (policies.py:65-112)."""
+        """Mean (+ guidance) + noise, then inpainting (policies.py:65-112): the reference's single ancestral step,
+        whatever ``diffusion.set_sampler`` chose for ``sample_loop``."""
         step = TemporalUnet.shared_timestep(t)
         self.diffusion._check_step(step)
         eng = self.diffusion._engine(x.device)
@@ -100,7 +101,8 @@ class GuidedPolicy(nn.Module):
     def sample_loop(self, batch_size: int = 1, conditions: Optional[Dict[int, torch.Tensor]] = None,
                     verbose: bool = False, row_offset: int = 0) -> torch.Tensor:
         """x_T ~ N(0, I) -> apply conditions -> T guided/inpainted reverse steps
-        (policies.py:114-149)."""
+        (policies.py:114-149).  Under ``diffusion.set_sampler("ddim", ...)`` the steps are the K strided ones over the
+        trained schedule, on the same routes; guidance then takes its DDIM form (``_sample_loop_strided``)."""
         diff = self.diffusion
         device = diff.betas.device
         shape = (batch_size, self.horizon, self.transition_dim)
@@ -128,6 +130,9 @@ class GuidedPolicy(nn.Module):
         if graph and c0 is not None:                       # frozen pointer: stage the condition
             c0 = eng.persistent("cond0", tuple(c0.shape)).copy_(c0)
         projector = self._loop_projector()
+        plan = diff.sampler_plan()
+        if plan is not None:
+            return self._sample_loop_strided(eng, plan, x, c0, rest, projector, graph, row_offset)
 
         if not self._guided() and not rest:
             alphas = None
@@ -172,6 +177,57 @@ class GuidedPolicy(nn.Module):
                 self.apply_conditions(x, rest)
             if projector is not None:
                 projector.apply(x, self._get_projection_alpha(i))
+        return x
+
+    def _sample_loop_strided(self, eng, plan, x, c0, rest, projector, graph: bool, row_offset: int) -> torch.Tensor:
+        """The reverse steps of ``sample_loop`` under the strided sampler, from x_T with its conditions applied.
+
+        Iteration j runs step ``steps[j]`` at timestep ``taus[j]`` (descending) with Philox draw j + 1 — or, on the
+        torch route, the j-th ``randn`` after x_T's; ``eta == 0`` draws nothing after x_T.  The projection strength is
+        ``_get_projection_alpha(tau)``.  A guide is classifier guidance in its DDIM form, eps' = eps - w sqrt(1 - abar)
+        g with g the guide's gradient at x_t: the tail kernels apply it as the shift of x0 it causes (the ancestral
+        form scales by the step's variance, which is 0 at eta == 0)."""
+        diff = self.diffusion
+        steps, taus, eta = plan
+        device, shape, K = x.device, tuple(x.shape), len(steps)
+        philox = diff.sampler_rng == "philox"
+        alphas = None if projector is None else [self._get_projection_alpha(t) for t in taus]
+
+        if not self._guided() and not rest:
+            if philox:
+                eng.sampler_loop(x, steps, seed=diff.seed, row_offset=row_offset, cond0=c0,
+                                 projection=projector, proj_alphas=alphas, use_graph=graph)
+            elif eta > 0.0 and diff.noise_stack_bytes(shape, K) > diff.max_noise_stack_bytes:
+                for j in range(K):
+                    eng.sampler_step(x, steps[j], noise=torch.randn(shape, device=device), cond0=c0)
+                    if projector is not None:
+                        projector.apply(x, alphas[j])
+            else:
+                stack = None
+                if eta > 0.0:
+                    stack = eng.persistent("z", (K,) + shape) if graph else torch.empty((K,) + shape, device=device)
+                    for j in range(K):
+                        torch.randn(shape, out=stack[j])
+                eng.sampler_loop(x, steps, noise_stack=stack, cond0=c0, projection=projector,
+                                 proj_alphas=alphas, use_graph=graph)
+            return x.clone() if graph else x
+
+        for j, t in enumerate(taus):
+            grad, gw = None, 0.0
+            if self._guided():
+                tt = torch.full((shape[0],), t, device=device, dtype=torch.long)
+                grad = self._guide_gradient(x, tt).float()
+                gw = float(self.guide_weight)
+            if philox or eta == 0.0:
+                eng.sampler_step(x, steps[j], seed=diff.seed, row_offset=row_offset, draw=j + 1, cond0=c0,
+                                 guide_grad=grad, guide_weight=gw)
+            else:
+                eng.sampler_step(x, steps[j], noise=torch.randn_like(x), cond0=c0, guide_grad=grad,
+                                 guide_weight=gw)
+            if rest:
+                self.apply_conditions(x, rest)
+            if projector is not None:
+                projector.apply(x, alphas[j])
         return x
 
     def _loop_projector(self) -> Optional[ProjectionState]:

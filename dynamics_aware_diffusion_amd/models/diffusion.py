@@ -10,8 +10,9 @@ training objective on the same kernels and is differentiable (explicit backward 
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -68,6 +69,70 @@ def extract(a: torch.Tensor, t: torch.Tensor, x_shape: tuple) -> torch.Tensor:
     return picked.reshape(t.shape[0], *((1,) * (len(x_shape) - 1)))
 
 
+def sampler_timesteps(n_trained: int, timesteps_or_K) -> np.ndarray:
+    """The strictly ascending timesteps ``tau`` of a strided sampler over a trained schedule of ``n_trained`` entries:
+    ``K`` (an int, 1 <= K <= n_trained) means ``tau_i = floor(i * n_trained / K)``; a sequence is taken as given.
+    ``ValueError`` for K out of range and for a sequence that is empty, unsorted, repeated or out of [0, n_trained)."""
+    T = int(n_trained)
+    if isinstance(timesteps_or_K, (int, np.integer)) and not isinstance(timesteps_or_K, bool):
+        K = int(timesteps_or_K)
+        if K < 1 or K > T:
+            raise ValueError(f"steps = {K} is outside [1, {T}], the trained schedule")
+        return (np.arange(K, dtype=np.int64) * T) // K
+    try:
+        given = [v for v in timesteps_or_K]
+    except TypeError:
+        raise ValueError(f"steps must be an int or a sequence of timesteps, got {timesteps_or_K!r}") from None
+    if not given or any(isinstance(v, bool) or int(v) != v for v in given):
+        raise ValueError("a sampler's timesteps must be a non-empty sequence of integers")
+    tau = np.asarray([int(v) for v in given], dtype=np.int64)
+    if tau.min() < 0 or tau.max() >= T:
+        raise ValueError(f"a sampler's timesteps must lie in [0, {T})")
+    if np.any(np.diff(tau) <= 0):
+        raise ValueError("a sampler's timesteps must be strictly ascending (no repeats)")
+    return tau
+
+
+def ddim_table(alphas_cumprod, timesteps_or_K, eta: float = 0.0) -> Dict[str, np.ndarray]:
+    """Coefficients of the strided (DDIM, Song et al. 2021) sampler over a trained schedule; needs no device.
+
+    ``alphas_cumprod`` is the model's buffer, read as float64; ``timesteps_or_K`` as ``sampler_timesteps``; ``eta`` in
+    [0, 1] (0: deterministic, 1: the ancestral variance).  Step ``i`` goes from ``ab = abar[tau_i]`` to
+    ``ap = abar[tau_{i-1}]`` (``ap = 1`` for i = 0)::
+
+        sigma      = eta * sqrt((1 - ap) / (1 - ab)) * sqrt(1 - ab / ap)
+        c          = sqrt(max(1 - ap - sigma^2, 0)) / sqrt(1 - ab)
+        coef_xt    = c
+        coef_x0    = sqrt(ap) - c * sqrt(ab)
+        c_recip    = sqrt(1 / ab)
+        c_recipm1  = sqrt(1 / ab - 1)
+        guide_x0   = (1 - ab) / sqrt(ab)
+        guide_mean = 0
+
+    so that ``mean = coef_x0 * x0 + coef_xt * x_t`` is ``sqrt(ap) x0 + sqrt(1 - ap - sigma^2) eps`` with eps re-derived
+    from the (clamped) x0, and ``guide_x0`` is the shift of x0 that ``eps' = eps - w sqrt(1 - ab) g`` causes.  Returns
+    ``tau`` (int64) and one float64 array per name above, index i; ``_engine.pack_sampler_steps`` rounds them to fp32,
+    once.  ``eta = 1`` with every timestep is the DDPM posterior (coef1, coef2, variance) of the same ``abar``."""
+    if torch.is_tensor(alphas_cumprod):
+        alphas_cumprod = alphas_cumprod.detach().to("cpu")
+        abar = alphas_cumprod.to(torch.float64).numpy()
+    else:
+        abar = np.asarray(alphas_cumprod, dtype=np.float64)
+    if abar.ndim != 1 or abar.shape[0] < 1:
+        raise ValueError("alphas_cumprod must be a non-empty vector")
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:                      # (NaN fails both comparisons)
+        raise ValueError(f"eta = {eta} is outside [0, 1]")
+    tau = sampler_timesteps(abar.shape[0], timesteps_or_K)
+    ab = abar[tau]
+    ap = np.concatenate([np.ones(1), ab[:-1]])
+    sigma = eta * np.sqrt((1.0 - ap) / (1.0 - ab)) * np.sqrt(np.maximum(1.0 - ab / ap, 0.0))
+    c = np.sqrt(np.maximum(1.0 - ap - sigma * sigma, 0.0)) / np.sqrt(1.0 - ab)
+    return {"tau": tau, "c_recip": np.sqrt(1.0 / ab), "c_recipm1": np.sqrt(1.0 / ab - 1.0),
+            "guide_x0": (1.0 - ab) / np.sqrt(ab), "coef_x0": np.sqrt(ap) - c * np.sqrt(ab), "coef_xt": c,
+            "guide_mean": np.zeros_like(ab), "sigma": sigma}
+
+
 class GaussianDiffusion(nn.Module):
     """DDPM over trajectories (batch, horizon, observation_dim + action_dim).
 
@@ -85,6 +150,10 @@ class GaussianDiffusion(nn.Module):
     ``use_graph = True`` replays the whole T-step loop as one cached hipGraph (persistent
     input buffers, result returned as a copy): removes the per-launch host cost that dominates
     small batches such as the B=1 plans of ``get_action``.
+
+    ``set_sampler("ddim", steps=K, eta=0.0)`` makes every loop (``p_sample_loop``, the policies' ``sample_loop`` and
+    what is built on it) a K-step strided sampler over the whole trained schedule, on the same fused loop; the
+    default, ``"ddpm"``, is the reference's ancestral loop over the first ``n_timesteps`` entries.
     """
 
     def __init__(self, model: TemporalUnet, horizon: int, observation_dim: int, action_dim: int,
@@ -117,6 +186,54 @@ class GaussianDiffusion(nn.Module):
         # True: ``loss`` runs q_sample, the time MLPs, the denoiser and the L1 / L2 mean inside the library, as one
         # autograd node over the parameters (dad_train_objective_forward / _backward).  Opt-in; False changes nothing.
         self.fused_objective = False
+        # ("ddpm", None, 0.0) or ("ddim", (tau_0, ..., tau_{K-1}), eta): plain data, see set_sampler
+        self.sampler = ("ddpm", None, 0.0)
+
+    def set_sampler(self, kind: str, steps: Union[None, int, Sequence[int]] = None, eta: float = 0.0) -> None:
+        """Choose what the sampling loops run.
+
+        ``"ddpm"`` (the default; takes no arguments): the ancestral loop t = n_timesteps-1 .. 0 of the reference.
+        ``"ddim"``: the strided sampler of ``ddim_table`` over the whole trained schedule (``len(betas)`` entries,
+        whatever ``n_timesteps`` was lowered to): ``steps`` is K (``tau_i = floor(i T / K)``) or an explicit strictly
+        ascending sequence of timesteps, ``eta`` in [0, 1] scales the per-step noise (0: deterministic given x_T).
+
+        The choice is a plain attribute (``state_dict`` does not carry it; ``deepcopy`` and pickle do); the engine is
+        neither rebuilt nor re-finalised, the coefficients travel with each call.  The single-step methods
+        (``p_sample``, ``p_mean_variance``, the policies' ``p_sample_with_guidance``) stay ancestral steps."""
+        if kind == "ddpm":
+            if steps is not None or eta != 0.0:
+                raise ValueError("the ancestral sampler takes no steps and no eta: lower n_timesteps to truncate it")
+            self.sampler = ("ddpm", None, 0.0)
+            return
+        if kind != "ddim":
+            raise ValueError(f"unknown sampler {kind!r} (\"ddpm\" or \"ddim\")")
+        if steps is None:
+            raise ValueError("the strided sampler needs steps: K or a sequence of timesteps")
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"eta = {eta} is outside [0, 1]")
+        tau = sampler_timesteps(int(self.betas.shape[0]), steps)
+        self.sampler = ("ddim", tuple(int(v) for v in tau), eta)
+
+    def sampler_plan(self):
+        """``None`` for the ancestral sampler; else ``(steps, tau, eta)`` of the strided one in EXECUTION order
+        (i = K-1 .. 0): the engine's coefficient array, the timesteps the network sees, the noise scale."""
+        kind, tau, eta = getattr(self, "sampler", ("ddpm", None, 0.0))
+        if kind == "ddpm":
+            return None
+        # computed once per (sampler, schedule buffer): reading ``alphas_cumprod`` back is a device-to-host copy, which
+        # would otherwise drain the stream at the start of every loop (plain numpy data: deepcopy and pickle carry it)
+        abar = self.alphas_cumprod
+        key = (kind, tau, eta, abar.data_ptr(), abar._version, str(abar.device))
+        cached = self.__dict__.get("_sampler_cache")
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        from .._engine import pack_sampler_steps
+        table = ddim_table(abar, tau, eta)
+        order = np.arange(len(tau))[::-1]
+        plan = (pack_sampler_steps(table, order), [int(tau[i]) for i in order], eta)
+        self.__dict__["_sampler_cache"] = (key, plan)
+        return plan
 
     @staticmethod
     def noise_stack_bytes(shape, n_steps: int) -> int:
@@ -162,7 +279,8 @@ class GaussianDiffusion(nn.Module):
     @torch.no_grad()
     def p_mean_variance(self, x: torch.Tensor, t: Union[int, torch.Tensor]
                         ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(model mean, (B,1,1) log variance) of p(x_{t-1} | x_t) (diffusion.py:182-203)."""
+        """(model mean, (B,1,1) log variance) of p(x_{t-1} | x_t) (diffusion.py:182-203): the reference's ancestral
+        step, whatever ``set_sampler`` chose for the loops."""
         step = TemporalUnet.shared_timestep(t)
         self._check_step(step)
         eng = self._engine(x.device)
@@ -175,7 +293,8 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample(self, x: torch.Tensor, t: Union[int, torch.Tensor]) -> torch.Tensor:
-        """x_{t-1} ~ p(. | x_t); z is drawn even at t == 0 and masked (diffusion.py:205-223)."""
+        """x_{t-1} ~ p(. | x_t); z is drawn even at t == 0 and masked (diffusion.py:205-223): the reference's
+        ancestral step, whatever ``set_sampler`` chose for the loops."""
         step = TemporalUnet.shared_timestep(t)
         self._check_step(step)
         eng = self._engine(x.device)
@@ -190,10 +309,14 @@ class GaussianDiffusion(nn.Module):
         """Full ancestral sampling t = n_timesteps-1 .. 0 from pure noise (diffusion.py:225-251).
 
         ``n_timesteps`` may have been lowered after construction (evaluate.py:350-353): the
-        loop then walks the first ``n_timesteps`` entries of the trained schedule.
+        loop then walks the first ``n_timesteps`` entries of the trained schedule.  Under
+        ``set_sampler("ddim", ...)`` it is the K-step strided loop over the whole trained schedule instead.
         """
         device = self.betas.device
         eng = self._engine(device)
+        plan = self.sampler_plan()
+        if plan is not None:
+            return self._strided_loop(eng, plan, tuple(shape), row_offset)
         n_steps = int(self.n_timesteps)
         self._check_step(n_steps - 1)
         if self.sampler_rng == "philox":
@@ -216,6 +339,31 @@ class GaussianDiffusion(nn.Module):
         for j in range(n_steps):
             torch.randn(tuple(shape), out=stack[j])
         eng.sample_loop(x, n_steps, noise_stack=stack, use_graph=self.use_graph)
+        return x.clone() if self.use_graph else x
+
+    def _strided_loop(self, eng, plan, shape: tuple, row_offset: int) -> torch.Tensor:
+        """p_sample_loop under the strided sampler: the same routes, K steps given by their coefficients."""
+        steps, _, eta = plan
+        device, K = self.betas.device, len(steps)
+        if self.sampler_rng == "philox":
+            x = eng.persistent("x", shape) if self.use_graph else \
+                torch.empty(shape, device=device, dtype=torch.float32)
+            eng.fill_normal(x, self.seed, row_offset=row_offset, draw=0)
+            eng.sampler_loop(x, steps, seed=self.seed, row_offset=row_offset, use_graph=self.use_graph)
+            return x.clone() if self.use_graph else x
+        x = torch.randn(shape, device=device)
+        if eta > 0.0 and self.noise_stack_bytes(shape, K) > self.max_noise_stack_bytes:
+            for j in range(K):
+                eng.sampler_step(x, steps[j], noise=torch.randn(shape, device=device))
+            return x
+        if self.use_graph:
+            x = eng.persistent("x", shape).copy_(x)
+        stack = None
+        if eta > 0.0:                     # eta == 0: sigma is 0 at every step, so x_T is the only draw
+            stack = eng.persistent("z", (K,) + shape) if self.use_graph else torch.empty((K,) + shape, device=device)
+            for j in range(K):
+                torch.randn(shape, out=stack[j])
+        eng.sampler_loop(x, steps, noise_stack=stack, use_graph=self.use_graph)
         return x.clone() if self.use_graph else x
 
     # ------------------------------------------------------------------ training objective

@@ -299,6 +299,39 @@ int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
                     int32_t use_graph, void* workspace, size_t workspace_bytes,
                     dad_stream_t stream);
 
+/* One reverse step described by its coefficients rather than by a schedule index: what a strided (DDIM) sampler over
+ * the trained schedule hands in.  In the tail kernels' operation order, per element:
+ *   x0   = c_recip * x_t - c_recipm1 * out          (or x0 = out when the model predicts x0)
+ *   x0  += guide_weight * guide_x0 * g              (only with a guide gradient g)
+ *   x0   = clamp(x0, -1, 1)                         (cfg.clip_denoised)
+ *   mean = coef_x0 * x0 + coef_xt * x_t
+ *   mean += guide_weight * guide_mean * g           (only with a guide gradient g)
+ *   x    = mean + sigma * z, then the inpainting of horizon step 0.
+ * `t` is the row of the time-embedding tables the network is evaluated at.  The ancestral step of dad_denoise_step
+ * is {t, sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t], 0, posterior_mean_coef1[t],
+ * posterior_mean_coef2[t], exp(log_var[t]), t == 0 ? 0 : exp(0.5 log_var[t])} of the loaded schedule. */
+typedef struct dad_sampler_coef {
+    int32_t t;
+    float c_recip, c_recipm1, guide_x0, coef_x0, coef_xt, guide_mean, sigma;
+} dad_sampler_coef;
+
+/* dad_denoise_step with the step's coefficients given by the caller.  DAD_E_RANGE for coef->t outside
+ * [0, n_timesteps), DAD_E_INVALID for a coefficient that is not finite or a negative sigma: checked before anything
+ * else about the model, so an unfinalised model refuses them too. */
+int dad_sampler_step(dad_model* m, float* x, const dad_sampler_coef* coef, int32_t batch, const dad_step_args* args,
+                     int32_t x_out_disabled, void* workspace, size_t workspace_bytes, dad_stream_t stream);
+
+/* dad_sample_loop over `n_steps` caller-given steps, steps[0] first: iteration j evaluates the network at steps[j].t
+ * and uses Philox draw j + 1 (or noise_stack[j]).  proj_alphas_host[n_steps] is in the same (execution) order.
+ * Refusals as dad_sampler_step for every step, and DAD_E_INVALID for n_steps < 1.  use_graph: the bytes of `steps`
+ * are part of the key of the cached graph, so every sampler is captured once and replayed by value. */
+int dad_sampler_loop(dad_model* m, float* x, const dad_sampler_coef* steps, int32_t n_steps, int32_t batch,
+                     const float* noise_stack, uint64_t seed, uint64_t row_offset,
+                     const float* cond0, int32_t cond_per_row,
+                     const dad_project_args* proj, const float* proj_alphas_host,
+                     int32_t use_graph, void* workspace, size_t workspace_bytes,
+                     dad_stream_t stream);
+
 /* Replaces: DynamicsAwarePolicy.apply_projection (guides/policies.py:409-485) for one
  * alpha (policies.py:358-383 is evaluated by the caller).  x: (B,H,od+m) IN PLACE. */
 int dad_project(const dad_project_args* p, float alpha, float* x, int32_t batch,
