@@ -10,6 +10,7 @@ import ctypes as C
 import functools
 import math
 import os
+import weakref
 from typing import Dict, Mapping, Optional, Sequence
 
 import numpy as np
@@ -125,6 +126,13 @@ ABI = {
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
     "dad_projection_violation": (C.c_int, [C.POINTER(DadProjectArgs), C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_void_p]),
+    "dad_violation_grad_workspace_bytes": (C.c_int, [C.POINTER(DadProjectArgs), C.c_int32, C.c_int32, C.c_int32,
+                                                     C.POINTER(C.c_size_t)]),
+    "dad_projection_violation_fwd": (C.c_int, [C.POINTER(DadProjectArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "dad_projection_violation_bwd": (C.c_int, [C.POINTER(DadProjectArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "dad_debug_violation_grad_plan": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32)]),
     "dad_denoise_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                    C.POINTER(DadStepArgs), C.c_int32, C.c_void_p, C.c_size_t,
                                    C.c_void_p]),
@@ -368,6 +376,37 @@ def projection_plan(state_dim: int, observation_dim: int, action_dim: int, batch
     q["form"], q["refused"] = _names("DAD_PP_FORMS")[q["form"]], bool(q["refused"])
     q["grid"] = (q.pop("gx"), q.pop("gy"))
     return q
+
+
+VIOLATION_FORMS = {None: -1, "row": 0, "gemm": 1}      # the `form` argument of dad_projection_violation_fwd / _bwd
+
+
+def _violation_form(form) -> int:
+    if form not in VIOLATION_FORMS:
+        raise ValueError(f"form must be None (planned), \"row\" or \"gemm\", got {form!r}")
+    return VIOLATION_FORMS[form]
+
+
+def violation_grad_plan(state_dim: int, observation_dim: int, action_dim: int, batch: int, horizon: int,
+                        form: Optional[str] = None) -> dict:
+    """What one dad_projection_violation_fwd / _bwd pair launches at this shape under ``form`` (None: the planner's
+    choice, "row", "gemm"), decoded by name (dad_debug_violation_grad_plan: the plan the entry points launch from; host
+    logic only).  ``form`` comes back as "row" or "gemm"; ``fwd`` and ``bwd`` each hold ``rows_per_block``, ``grid``
+    (x, y), ``lds_bytes`` and the blocks of the pass's small second launch (``sum_gx`` / ``scatter_gx``, 0 in the row
+    form); ``workspace_bytes``; ``refused`` (a forced row form whose row does not fit LDS: the calls fail)."""
+    lib = load_library()
+    out = (C.c_int32 * _fields("DAD_VG_INTS")[1])()
+    _check(lib, lib.dad_debug_violation_grad_plan(int(state_dim), int(observation_dim), int(action_dim), int(batch),
+                                                  int(horizon), _violation_form(form), out))
+    q = _decode("DAD_VG_INTS", out)
+    plan = {"form": _names("DAD_VG_FORMS")[q.pop("form")], "refused": bool(q.pop("refused")),
+            "workspace_bytes": q.pop("workspace_bytes")}
+    for side in ("fwd", "bwd"):
+        d = {k[len(side) + 1:]: q.pop(k) for k in list(q) if k.startswith(side + "_")}
+        d["grid"] = (d.pop("gx"), d.pop("gy"))
+        plan[side] = d
+    assert not q, q
+    return plan
 
 
 def optim_plan(numel: Sequence[int]) -> dict:
@@ -1080,6 +1119,46 @@ class HipEngine:
         return ms.value, n.value, fl.value
 
 
+class _WorkspaceToken:
+    """Alive as long as the autograd node that may still read a violation-gradient workspace."""
+    __slots__ = ("__weakref__",)
+
+
+class _ViolationFn(torch.autograd.Function):
+    """ProjectionState.violation_fn: dad_projection_violation_fwd keeps the residual in the workspace,
+    dad_projection_violation_bwd turns it and d L / d violation into d L / d x."""
+
+    @staticmethod
+    def forward(ctx, x, state, form):
+        xc = x.detach().contiguous().float()
+        state._check_x(xc)
+        batch, horizon = int(xc.shape[0]), int(xc.shape[1])
+        ws, token = state._grad_workspace(batch, horizon, form)
+        out = torch.empty(batch, dtype=torch.float32, device=xc.device)
+        lib = load_library()
+        with torch.cuda.device(state.device):
+            _check(lib, lib.dad_projection_violation_fwd(C.byref(state.args), xc.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                         ws.numel() * 4, batch, horizon, form,
+                                                         torch.cuda.current_stream(state.device).cuda_stream))
+        ctx.state, ctx.form, ctx.ws, ctx.token = state, form, ws, token
+        ctx.x_shape, ctx.x_dtype = tuple(x.shape), x.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_violation):
+        state, ws = ctx.state, ctx.ws
+        batch, horizon = ctx.x_shape[0], ctx.x_shape[1]
+        w = d_violation.contiguous().float()
+        d_x = torch.empty(ctx.x_shape, dtype=torch.float32, device=w.device)
+        lib = load_library()
+        with torch.cuda.device(state.device):
+            _check(lib, lib.dad_projection_violation_bwd(C.byref(state.args), w.data_ptr(), d_x.data_ptr(), ws.data_ptr(),
+                                                         ws.numel() * 4, batch, horizon, ctx.form,
+                                                         torch.cuda.current_stream(state.device).cuda_stream))
+        return d_x.to(ctx.x_dtype), None, None
+
+
 class ProjectionState:
     """Device-resident projector + normaliser statistics for dad_project."""
 
@@ -1163,6 +1242,35 @@ class ProjectionState:
                                                      int(x.shape[0]), int(x.shape[1]),
                                                      torch.cuda.current_stream(self.device).cuda_stream))
         return out
+
+    def grad_plan(self, batch: int, horizon: int, form: Optional[str] = None) -> dict:
+        """What :meth:`violation_fn` launches, forward and backward, for ``batch`` trajectories of ``horizon`` steps
+        under ``form`` (:func:`violation_grad_plan`; no device call)."""
+        a = self.args
+        return violation_grad_plan(a.state_dim, a.observation_dim, a.action_dim, batch, horizon, form)
+
+    def _grad_workspace(self, batch: int, horizon: int, form: int):
+        """(workspace, token) for one forward / backward pair.  The state keeps one workspace, grown on demand; the
+        token lives on the autograd node, and while the node of an earlier call is alive (its backward may still
+        come) a later call gets a workspace of its own instead of overwriting the residual that backward needs."""
+        lib, need = load_library(), C.c_size_t()
+        _check(lib, lib.dad_violation_grad_workspace_bytes(C.byref(self.args), batch, horizon, form, C.byref(need)))
+        floats = (need.value + 3) // 4
+        holder = getattr(self, "_vg_holder", None)
+        token = _WorkspaceToken()
+        if holder is not None and holder() is not None:
+            return torch.empty(floats, dtype=torch.float32, device=self.device), token
+        ws = getattr(self, "_vg_ws", None)
+        if ws is None or ws.numel() < floats:
+            ws = self._vg_ws = torch.empty(floats, dtype=torch.float32, device=self.device)
+        self._vg_holder = weakref.ref(token)
+        return ws, token
+
+    def violation_fn(self, x: torch.Tensor, form: Optional[str] = None) -> torch.Tensor:
+        """:meth:`violation` with a graph to ``x``: the per-row violation (B,) as one autograd node whose backward is
+        dad_projection_violation_bwd (once differentiable; the projector gets no gradient, as in the reference, where
+        it is a plain tensor).  ``form``: None lets the planner choose, "row" / "gemm" force a form (a test hook)."""
+        return _ViolationFn.apply(x, self, _violation_form(form))
 
     def apply(self, x: torch.Tensor, alpha: float) -> None:
         self._check_x(x)

@@ -137,4 +137,13 @@ constexpr int PG_KC = 64;                     // k values per staged chunk
 constexpr int PG_AS = 33;                     // LDS row stride of the staged v chunk [k][32 rows]
 DAD_HD inline size_t project_gemm_lds_floats() { return (size_t)4 * PG_KC * PG_AS + 64; }
 
+// violation_grad.hpp.  Row form, backward: VG_ROW_WAVES waves share the rows of P; a block keeps r_b and g_b.
+constexpr int VG_ROW_WAVES = 16;
+DAD_HD inline size_t vg_row_bwd_lds_bytes(int D) { return (size_t)2 * D * sizeof(float); }
+// GEMM form (PG_THREADS, PG_KC, PG_AS as project_gemm_kernel).  Backward: each wave also stages its P tile
+// [32 rows of P][PG_KC k], rows VG_PS floats apart (odd: the transposed reads of the B operand spread over the banks).
+constexpr int VG_PS = PG_KC + 1;
+DAD_HD inline size_t vg_gemm_bwd_lds_floats() { return (size_t)4 * (PG_KC * PG_AS + 32 * VG_PS); }
+constexpr int VG_TAIL_THREADS = 256;          // violation_sum_kernel, violation_scatter_kernel
+
 }  // namespace dad

@@ -25,6 +25,7 @@
 #include "conv_halo8.hpp"
 #include "conv_gn_pass.hpp"
 #include "pointwise.hpp"
+#include "violation_grad.hpp"
 #include "conv_seam.hpp"
 #include "conv_cc.hpp"
 #include "conv_ccw.hpp"
@@ -274,7 +275,9 @@ int configure_kernels() {
     std::lock_guard<std::mutex> hold(lock);
     if (done.count(dev)) return DAD_OK;
     std::vector<const void*> fns = {(const void*)dad::final_posterior_kernel, (const void*)dad::final_cc_kernel,
-                                    (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>};
+                                    (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>,
+                                    (const void*)dad::violation_bwd_row_kernel, (const void*)dad::violation_fwd_gemm_kernel,
+                                    (const void*)dad::violation_bwd_gemm_kernel};
     for (const KernelEntry& e : kernel_table()) fns.push_back(e.fn);      // every family
     for (const void* fn : fns)
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
@@ -707,6 +710,84 @@ int run_project(const dad_project_args* pa, float alpha, float* x, int batch, in
     return DAD_OK;
 }
 
+// What the two passes of the violation gradient check before anything touches the device, and the plan they launch from.
+int violation_grad_plan_of(const dad_project_args* pa, const void* workspace, size_t workspace_bytes, int batch, int horizon,
+                           int form, int& D, ViolationGradPlan& q) {
+    if (!pa || !pa->P || !pa->obs_mean || !pa->obs_std || !pa->act_mean || !pa->act_std)
+        return fail(DAD_E_INVALID, "violation gradient: projection arguments missing");
+    if (!workspace) return fail(DAD_E_INVALID, "violation gradient: null workspace");
+    const int rc = violation_grad_plan_checked(pa->state_dim, pa->observation_dim, pa->action_dim, batch, horizon, form, D, q);
+    if (rc != DAD_OK) return rc;
+    if (q.refused)
+        return fail(DAD_E_INVALID, "violation gradient: the row form at D=%d needs %zu bytes of LDS for one trajectory and its partial "
+                    "sums (a CU has %zu); the GEMM form (form 1, or -1) takes any D", D, q.fwd.lds_bytes, dad::kLdsBytes);
+    if (workspace_bytes < q.workspace_bytes)
+        return fail(DAD_E_WORKSPACE, "violation gradient: workspace of %zu bytes, %zu needed (dad_violation_grad_workspace_bytes)",
+                    workspace_bytes, q.workspace_bytes);
+    return DAD_OK;
+}
+
+int run_violation_fwd(const dad_project_args* pa, const float* x, float* violation, void* workspace, size_t workspace_bytes,
+                      int batch, int horizon, int form, hipStream_t st) {
+    if (!x || !violation) return fail(DAD_E_INVALID, "violation gradient: null pointer");
+    int D = 0;
+    ViolationGradPlan q;
+    int rc = violation_grad_plan_of(pa, workspace, workspace_bytes, batch, horizon, form, D, q);
+    if (rc != DAD_OK || (rc = configure_kernels()) != DAD_OK) return rc;
+    float* const ws = (float*)workspace;
+    dad::ViolationFwdParams f{};
+    dad::ProjParams& p = f.proj;
+    p.P = pa->P; p.obs_mean = pa->obs_mean; p.obs_std = pa->obs_std; p.act_mean = pa->act_mean; p.act_std = pa->act_std;
+    p.x = const_cast<float*>(x); p.xout = nullptr;
+    p.B = batch; p.H = horizon; p.n = pa->state_dim; p.od = pa->observation_dim; p.m = pa->action_dim; p.D = D;
+    p.alpha = 1.0f; p.one_minus_alpha = 0.0f;
+    p.violation = violation;
+    p.resid = ws + q.r_off;
+    const dim3 grid(q.fwd.gx, q.fwd.gy);
+    if (q.form == DAD_VG_ROW) {
+        if (q.fwd.rows_per_block == 1)
+            hipLaunchKernelGGL((dad::project_kernel<1, dad::PROJ_KP>), grid, dim3(64 * dad::PROJ_KP), q.fwd.lds_bytes, st, p);
+        else
+            hipLaunchKernelGGL((dad::project_kernel<4, dad::PROJ_KP>), grid, dim3(64 * dad::PROJ_KP), q.fwd.lds_bytes, st, p);
+        HIP_TRY(hipGetLastError());
+        return DAD_OK;
+    }
+    f.part = ws + q.part_off;
+    f.col_blocks = q.col_blocks;
+    hipLaunchKernelGGL(dad::violation_fwd_gemm_kernel, grid, dim3(dad::PG_THREADS), q.fwd.lds_bytes, st, f);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(dad::violation_sum_kernel, dim3(q.fwd.tail_gx), dim3(dad::VG_TAIL_THREADS), 0, st,
+                       (const float*)f.part, violation, batch, q.col_blocks);
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
+int run_violation_bwd(const dad_project_args* pa, const float* d_violation, float* d_x, void* workspace, size_t workspace_bytes,
+                      int batch, int horizon, int form, hipStream_t st) {
+    if (!d_violation || !d_x) return fail(DAD_E_INVALID, "violation gradient: null pointer");
+    int D = 0;
+    ViolationGradPlan q;
+    int rc = violation_grad_plan_of(pa, workspace, workspace_bytes, batch, horizon, form, D, q);
+    if (rc != DAD_OK || (rc = configure_kernels()) != DAD_OK) return rc;
+    float* const ws = (float*)workspace;
+    dad::ViolationBwdParams p{};
+    p.P = pa->P; p.obs_std = pa->obs_std; p.act_std = pa->act_std;
+    p.r = ws + q.r_off; p.w = d_violation; p.g = ws + q.g_off; p.dx = d_x;
+    p.B = batch; p.H = horizon; p.n = pa->state_dim; p.od = pa->observation_dim; p.m = pa->action_dim; p.D = D;
+    p.row_elems = horizon * (pa->observation_dim + pa->action_dim);
+    const dim3 grid(q.bwd.gx, q.bwd.gy);
+    if (q.form == DAD_VG_ROW) {
+        hipLaunchKernelGGL(dad::violation_bwd_row_kernel, grid, dim3(64 * dad::VG_ROW_WAVES), q.bwd.lds_bytes, st, p);
+        HIP_TRY(hipGetLastError());
+        return DAD_OK;
+    }
+    hipLaunchKernelGGL(dad::violation_bwd_gemm_kernel, grid, dim3(dad::PG_THREADS), q.bwd.lds_bytes, st, p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(dad::violation_scatter_kernel, dim3(q.bwd.tail_gx), dim3(dad::VG_TAIL_THREADS), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
 // One reverse step `s` (already checked) on the plan `f`: the body of dad_denoise_step and dad_sampler_step
 int sampler_step(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coef& s, const dad_step_args* args,
                  int x_out_disabled, void* workspace, dad_stream_t stream) {
@@ -1098,6 +1179,26 @@ int dad_projection_violation(const dad_project_args* p, const float* x, float* v
                              int32_t horizon, dad_stream_t stream) {
     if (!x || !violation || batch <= 0 || horizon <= 0) return fail(DAD_E_INVALID, "bad argument");
     return run_project(p, 1.0f, const_cast<float*>(x), batch, horizon, (hipStream_t)stream, violation);
+}
+
+int dad_violation_grad_workspace_bytes(const dad_project_args* p, int32_t batch, int32_t horizon, int32_t form, size_t* bytes) {
+    if (!p || !bytes) return fail(DAD_E_INVALID, "violation gradient: null pointer");
+    int D = 0;
+    ViolationGradPlan q;
+    const int rc = violation_grad_plan_checked(p->state_dim, p->observation_dim, p->action_dim, batch, horizon, form, D, q);
+    if (rc != DAD_OK) return rc;
+    *bytes = q.workspace_bytes;
+    return DAD_OK;
+}
+
+int dad_projection_violation_fwd(const dad_project_args* p, const float* x, float* violation, void* workspace,
+                                 size_t workspace_bytes, int32_t batch, int32_t horizon, int32_t form, dad_stream_t stream) {
+    return run_violation_fwd(p, x, violation, workspace, workspace_bytes, batch, horizon, form, (hipStream_t)stream);
+}
+
+int dad_projection_violation_bwd(const dad_project_args* p, const float* d_violation, float* d_x, void* workspace,
+                                 size_t workspace_bytes, int32_t batch, int32_t horizon, int32_t form, dad_stream_t stream) {
+    return run_violation_bwd(p, d_violation, d_x, workspace, workspace_bytes, batch, horizon, form, (hipStream_t)stream);
 }
 
 int dad_sample_loop(dad_model* m, float* x, int32_t n_steps, int32_t batch,
@@ -1896,6 +1997,12 @@ int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t a
     if (!out || state_dim <= 0 || observation_dim < state_dim || action_dim <= 0 || batch <= 0 || horizon <= 0)
         return fail(DAD_E_INVALID, "bad argument");
     return project_plan_report(state_dim, observation_dim, action_dim, batch, horizon, scratch_bytes, violation != 0, out);
+}
+
+int dad_debug_violation_grad_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
+                                  int32_t form, int32_t* out) {
+    if (!out) return fail(DAD_E_INVALID, "violation gradient: null pointer");
+    return violation_grad_plan_report(state_dim, observation_dim, action_dim, batch, horizon, form, out);
 }
 
 int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out) {

@@ -1714,6 +1714,63 @@ inline ProjectPlan plan_project(int D, int batch, size_t x_bytes, size_t scratch
     return q;
 }
 
+// ------------------------------------------------------------------ violation gradient: which form, on which grids
+// One dad_projection_violation_fwd / _bwd pair (run_violation_fwd / _bwd launch from this; dad_debug_violation_grad_plan
+// reports it).  D as above, row_elems = H (od + m): one trajectory of x, form: -1 the rule below, 0 row, 1 gemm.
+struct ViolationGradPass {
+    int rows_per_block = 1;
+    unsigned gx = 1, gy = 1;
+    size_t lds_bytes = 0;
+    unsigned tail_gx = 0;    // forward: violation_sum_kernel, backward: violation_scatter_kernel (gemm form only)
+};
+struct ViolationGradPlan {
+    int form = DAD_VG_ROW;
+    ViolationGradPass fwd, bwd;
+    int col_blocks = 0;                          // gemm: 32-column blocks of P = partial sums per trajectory
+    size_t r_off = 0, part_off = 0, g_off = 0;   // where r (B, D), the partial sums and g (B, D) start, in floats
+    size_t workspace_bytes = 0;
+    bool refused = false;    // a forced row form whose forward LDS (a row + its 16 partial sets) exceeds a CU's
+};
+// The projection's own crossover: the GEMM form from D = 512 at batches of 32+, and wherever a row does not fit LDS.
+// (Measured for this pair, DESIGN.md §3 "Violation gradient": the row form is faster at D = 196 (19.5 us against 31.0 us
+// of kernel time at B = 256) and still 6 us ahead at D = 514; the GEMM form is 3.3 x faster at D = 2183.  The crossover
+// between 514 and 2183 was not measured, so the constant is not moved.)
+constexpr int kViolationGemmMinD = 512;
+constexpr int kViolationGemmMinBatch = 32;
+inline ViolationGradPlan plan_violation_grad(int D, int batch, long row_elems, int form) {
+    ViolationGradPlan q;
+    const size_t row_lds = dad::project_row_lds_bytes(D);
+    const bool row_fits = row_lds <= dad::kLdsBytes;
+    const bool gemm = form < 0 ? (!row_fits || (D >= kViolationGemmMinD && batch >= kViolationGemmMinBatch)) : form == 1;
+    const auto round64 = [](size_t floats) { return (floats + 63) / 64 * 64; };       // sections start 256 bytes aligned
+    const size_t bd = (size_t)batch * (size_t)D;
+    if (!gemm) {
+        // forward: project_kernel's violation branch exactly as dad_projection_violation plans it (same bits), with
+        // the residual kept; backward: one block per trajectory
+        const ProjectPlan f = plan_project(D, batch, 0, 0, true);
+        q.form = DAD_VG_ROW;
+        q.fwd.rows_per_block = f.rows_per_block; q.fwd.gx = f.gx; q.fwd.gy = f.gy; q.fwd.lds_bytes = f.lds_bytes;
+        q.bwd.rows_per_block = 1; q.bwd.gx = (unsigned)batch; q.bwd.gy = 1;
+        q.bwd.lds_bytes = dad::vg_row_bwd_lds_bytes(D);
+        q.refused = f.refused || q.bwd.lds_bytes > dad::kLdsBytes;
+        q.workspace_bytes = round64(bd) * sizeof(float);
+        return q;
+    }
+    q.form = DAD_VG_GEMM;
+    q.col_blocks = (D + 31) / 32;
+    q.fwd.rows_per_block = q.bwd.rows_per_block = 32;
+    q.fwd.gx = q.bwd.gx = (unsigned)((batch + 31) / 32);
+    q.fwd.gy = q.bwd.gy = (unsigned)q.col_blocks;
+    q.fwd.lds_bytes = dad::project_gemm_lds_floats() * sizeof(float);
+    q.bwd.lds_bytes = dad::vg_gemm_bwd_lds_floats() * sizeof(float);
+    q.fwd.tail_gx = (unsigned)((batch + dad::VG_TAIL_THREADS - 1) / dad::VG_TAIL_THREADS);
+    q.bwd.tail_gx = (unsigned)(((size_t)batch * (size_t)row_elems + dad::VG_TAIL_THREADS - 1) / dad::VG_TAIL_THREADS);
+    q.part_off = round64(bd);
+    q.g_off = q.part_off + round64((size_t)batch * (size_t)q.col_blocks);
+    q.workspace_bytes = (q.g_off + round64(bd)) * sizeof(float);
+    return q;
+}
+
 // ------------------------------------------------------------------ backward pass: per-batch geometry
 // Which conv_wgrad instantiations exist, by (taps, block tile, windowed: layers longer than a chunk stages): these tap
 // counts, each on tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32 (eight) and 3 = 32 x 32 with the

@@ -26,6 +26,7 @@ constexpr const char* kReportLayouts[][kMaxReportSections] = {
     {S(DAD_OP_HEADER), S(DAD_OP_REC_INTS), S(DAD_OP_TG_MODES)},
     {S(DAD_OS_HEADER), S(DAD_OS_REC_INTS)},
     {S(DAD_KL_HEADER), S(DAD_FAMILIES)},
+    {S(DAD_VG_INTS), S(DAD_VG_FORMS)},
 };
 #undef K
 #undef S
@@ -300,6 +301,39 @@ inline int project_plan_report(int state_dim, int observation_dim, int action_di
     out[DAD_PP_GY] = (int32_t)q.gy;
     out[DAD_PP_LDS_BYTES] = (int32_t)std::min<size_t>(q.lds_bytes, INT32_MAX);
     out[DAD_PP_REFUSED] = q.refused;
+    return DAD_OK;
+}
+
+// The plan of one dad_projection_violation_fwd / _bwd pair, after the checks on the shape that every entry point of the
+// pair makes (and dad_debug_violation_grad_plan with them).  A forced row form that does not fit is planned, not refused.
+inline int violation_grad_plan_checked(int state_dim, int observation_dim, int action_dim, int batch, int horizon, int form,
+                                       int& D_out, ViolationGradPlan& q) {
+    if (batch <= 0 || horizon <= 0) return fail(DAD_E_INVALID, "violation gradient: batch=%d, horizon=%d must be positive", batch, horizon);
+    if (state_dim <= 0 || action_dim <= 0 || state_dim > observation_dim)
+        return fail(DAD_E_INVALID, "violation gradient: state_dim=%d must lie in 1 .. observation_dim=%d, action_dim=%d be positive",
+                    state_dim, observation_dim, action_dim);
+    if (form < -1 || form > 1) return fail(DAD_E_INVALID, "violation gradient: form=%d is none of -1 (planned), 0 (row), 1 (gemm)", form);
+    const long D = (long)(horizon + 1) * state_dim + (long)horizon * action_dim;
+    if (D > INT32_MAX / 64) return fail(DAD_E_INVALID, "projection dimension D=%ld too large", D);
+    D_out = (int)D;
+    q = plan_violation_grad((int)D, batch, (long)horizon * (observation_dim + action_dim), form);
+    return DAD_OK;
+}
+// dad_debug_violation_grad_plan; out[DAD_VG_INTS].
+inline int violation_grad_plan_report(int state_dim, int observation_dim, int action_dim, int batch, int horizon, int form,
+                                      int32_t* out) {
+    int D = 0;
+    ViolationGradPlan q;
+    const int rc = violation_grad_plan_checked(state_dim, observation_dim, action_dim, batch, horizon, form, D, q);
+    if (rc != DAD_OK) return rc;
+    const auto i32 = [](size_t v) { return (int32_t)std::min<size_t>(v, INT32_MAX); };
+    out[DAD_VG_FORM] = q.form;
+    out[DAD_VG_FWD_ROWS_PER_BLOCK] = q.fwd.rows_per_block; out[DAD_VG_FWD_GX] = (int32_t)q.fwd.gx; out[DAD_VG_FWD_GY] = (int32_t)q.fwd.gy;
+    out[DAD_VG_FWD_LDS_BYTES] = i32(q.fwd.lds_bytes); out[DAD_VG_FWD_SUM_GX] = (int32_t)q.fwd.tail_gx;
+    out[DAD_VG_BWD_ROWS_PER_BLOCK] = q.bwd.rows_per_block; out[DAD_VG_BWD_GX] = (int32_t)q.bwd.gx; out[DAD_VG_BWD_GY] = (int32_t)q.bwd.gy;
+    out[DAD_VG_BWD_LDS_BYTES] = i32(q.bwd.lds_bytes); out[DAD_VG_BWD_SCATTER_GX] = (int32_t)q.bwd.tail_gx;
+    out[DAD_VG_WORKSPACE_BYTES] = i32(q.workspace_bytes);
+    out[DAD_VG_REFUSED] = q.refused;
     return DAD_OK;
 }
 

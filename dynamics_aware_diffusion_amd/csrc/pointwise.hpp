@@ -224,6 +224,8 @@ struct ProjParams {
     float alpha, one_minus_alpha;
     float* violation;        // when set: x is left untouched and violation[b] = sum_d (v - vP)_d^2 in
                              // physical units (losses/__init__.py:161-186, ProjectionLoss.compute)
+    float* resid;            // with `violation`, when set: the residual r = v - vP is kept, (B, D) (what the
+                             // backward pass of violation_grad.hpp reads); null: not stored
 };
 
 // One block = RB trajectories, KP waves.  v@P is latency-bound (P = D*D*4 bytes streams through
@@ -286,6 +288,7 @@ __global__ __launch_bounds__(64 * KP) void project_kernel(const ProjParams p) {
 #pragma unroll
                     for (int q = 0; q < KP; ++q) proj += part[(q * RB + r) * D + d];
                     const float diff = v[r * D + d] - proj;
+                    if (p.resid != nullptr && b0 + r < p.B) p.resid[(long)(b0 + r) * D + d] = diff;
                     acc = fmaf(diff, diff, acc);
                 }
                 for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);

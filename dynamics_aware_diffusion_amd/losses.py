@@ -5,7 +5,10 @@
 per-row time embedding; differentiable through the engine's explicit backward pass);
 ``ProjectionLoss`` measures the dynamics violation ``mean((v - vP)^2)`` of the DATA batch in physical
 units with the projection kernel of the sampler — as in the reference it depends on no parameter, so
-it contributes a value and no gradient; ``ComposedLoss`` adds weighted terms, and
+on a data batch it contributes a value and no gradient; handed a trajectory that requires grad it is
+differentiable, as the reference's plain torch expression is (``dad_projection_violation_fwd`` / ``_bwd``).
+``PredictedProjectionLoss`` (not in the reference) is the same measure of the model's own predicted x_0,
+the projection term that trains; ``ComposedLoss`` adds weighted terms, and
 ``ComposedLoss(...)(batch)[0].backward()`` is the reference's composed training step.
 """
 from __future__ import annotations
@@ -88,11 +91,59 @@ class ProjectionLoss(BaseLoss):
         ext = torch.cat([state, state[:, -1:, :]], dim=1)
         return torch.cat([ext.reshape(state.shape[0], -1), actions.reshape(actions.shape[0], -1)], dim=1)
 
-    @torch.no_grad()
+    def violation(self, x: torch.Tensor) -> torch.Tensor:
+        """``sum_d (v - vP)^2`` per trajectory, (B,), differentiable with respect to ``x`` (normalised trajectories
+        (B, H, od + m)): what a guide negates, ``GuidedPolicy(..., guide_fn=lambda x, t: -loss.violation(x))``."""
+        return self._state.violation_fn(x)
+
     def compute(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
-        x = batch["conditions"].contiguous().float()
-        per_row = self._state.violation(x)                # sum_d (v - vP)^2 per trajectory
-        return per_row.sum() / (x.shape[0] * self._D)
+        x = batch["conditions"]
+        if torch.is_grad_enabled() and x.requires_grad:
+            # as the reference's plain torch expression under autograd (losses:161-186): the gradient reaches whatever
+            # produced the trajectory
+            return self.violation(x).sum() / (x.shape[0] * self._D)
+        with torch.no_grad():
+            x = x.contiguous().float()
+            per_row = self._state.violation(x)                # sum_d (v - vP)^2 per trajectory
+            return per_row.sum() / (x.shape[0] * self._D)
+
+
+class PredictedProjectionLoss(ProjectionLoss):
+    """The dynamics violation of the model's own predicted plan: ``mean((v - v P)^2)`` of ``x0_hat``, the x_0 the
+    denoiser implies at a random step of the forward process.
+
+    This term is NOT in the reference.  There, ``ProjectionLoss`` is evaluated on the data batch
+    (losses/__init__.py:161-186), which depends on no parameter: it is logged and never trains anything.  What the
+    project's name promises — a denoiser pushed towards plans with ``x = x P`` — needs the violation of what the model
+    predicts, and its gradient with respect to the parameters; this class is that term, built from the reference's own
+    pieces.  It draws ``t`` and ``noise`` as ``GaussianDiffusion.loss`` does (``torch.randint`` then
+    ``torch.randn_like``; diffusion.py:253-290), forms ``x_t = q_sample(x_0, t, noise)``, evaluates
+    ``out = diffusion.model(x_t, t)`` and takes ``x0_hat = out`` when the model predicts x_0, else
+    ``predict_start_from_noise(x_t, t, out)`` (diffusion.py:159-166), unclamped: a clamp would cut the gradient exactly
+    where the prediction is furthest off.  The value is ``mean_b violation(x0_hat_b) / D``, ``ProjectionLoss``'s
+    normalisation.  It is a ``BaseLoss``, so it sits in ``ComposedLoss`` beside ``DiffusionLoss``; its draws are its
+    own (a second evaluation of the denoiser per step).  With ``diffusion.fused_objective = True`` it still goes
+    through the default denoiser node: the fused objective has no x0_hat output."""
+
+    def __init__(self, diffusion_model, projection_matrix: torch.Tensor, normalizer, state_dim: int, action_dim: int,
+                 observation_dim: int, horizon: int, weight: float = 0.1, device: str = "cuda"):
+        super().__init__(projection_matrix, normalizer, state_dim, action_dim, observation_dim, horizon, weight, device)
+        self.diffusion = diffusion_model
+
+    def compute(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+        diff = self.diffusion
+        x_start = batch["conditions"]
+        diff._engine(x_start.device)              # bind schedule / options before the model call
+        t = torch.randint(0, diff.n_timesteps, (x_start.shape[0],), device=x_start.device).long()
+        noise = torch.randn_like(x_start)
+        x_t = diff.q_sample(x_start, t, noise)
+        out = diff.model(x_t, t)
+        x0_hat = diff.predict_start_from_noise(x_t, t, out) if diff.predict_epsilon else out
+        if torch.is_grad_enabled() and x0_hat.requires_grad:
+            per_row = self.violation(x0_hat)
+        else:
+            per_row = self._state.violation(x0_hat.detach().contiguous().float())
+        return per_row.sum() / (x_start.shape[0] * self._D)
 
 
 class ComposedLoss(nn.Module):
@@ -112,4 +163,4 @@ class ComposedLoss(nn.Module):
         return total, parts
 
 
-__all__ = ["BaseLoss", "DiffusionLoss", "ProjectionLoss", "ComposedLoss"]
+__all__ = ["BaseLoss", "DiffusionLoss", "ProjectionLoss", "PredictedProjectionLoss", "ComposedLoss"]

@@ -344,6 +344,32 @@ int dad_project(const dad_project_args* p, float alpha, float* x, int32_t batch,
 int dad_projection_violation(const dad_project_args* p, const float* x, float* violation, int32_t batch,
                              int32_t horizon, dad_stream_t stream);
 
+/* The same violation as a differentiable pair.  Replaces: ProjectionLoss.compute (m_diffuser/losses/__init__.py:161-186)
+ * as torch autograd sees it — the reference's expression is plain torch, so loss.backward() differentiates it with
+ * respect to whatever trajectory it is handed; here the two passes are explicit.
+ *   forward:  r_b = v_b - v_b P,  violation[b] = sum_d r_{b,d}^2;  r (B, D) stays in `workspace`
+ *   backward: g_b = 2 d_violation[b] (r_b - r_b P^T)   (P is neither symmetric nor idempotent to this code), then
+ *             d_x[b,ts,k]    = obs_std[k] (g_b[ts n + k] + (ts == H-1 ? g_b[H n + k] : 0))      k < n
+ *             d_x[b,ts,k]    = 0                                                              n <= k < od
+ *             d_x[b,ts,od+k] = act_std[k] g_b[(H+1) n + ts m + k]
+ * d_x is fully overwritten; P gets no gradient (the reference keeps it a plain tensor).  `form`: -1 lets the planner
+ * choose (plan_violation_grad, csrc/host_plan.hpp), 0 forces the row form (one trajectory per block), 1 the GEMM form
+ * (32 trajectories x 32 columns per block on v_mfma_f32_32x32x2_f32; any batch, any D) — a test hook, like
+ * dad_debug_set_tile.  The backward pass must be given the workspace, batch, horizon and form of its forward pass.
+ * Both calls are asynchronous on `stream` and allocate nothing; no floating-point atomics: the same inputs give the
+ * same bits.  Refusals come before any launch, with a message: DAD_E_INVALID for a null pointer, batch or
+ * horizon <= 0, state_dim > observation_dim, an unknown form, or a forced row form whose row does not fit LDS;
+ * DAD_E_WORKSPACE for fewer than dad_violation_grad_workspace_bytes bytes.  dad_project_args.scratch is not used. */
+int dad_violation_grad_workspace_bytes(const dad_project_args* p, int32_t batch, int32_t horizon, int32_t form,
+                                       size_t* bytes);
+int dad_projection_violation_fwd(const dad_project_args* p, const float* x, float* violation, void* workspace,
+                                 size_t workspace_bytes, int32_t batch, int32_t horizon, int32_t form,
+                                 dad_stream_t stream);
+int dad_projection_violation_bwd(const dad_project_args* p, const float* d_violation /* (B) device */,
+                                 float* d_x /* (B,H,od+m), fully overwritten */, void* workspace,
+                                 size_t workspace_bytes, int32_t batch, int32_t horizon, int32_t form,
+                                 dad_stream_t stream);
+
 /* Replaces: torch.randn(shape) for x_T (diffusion.py:241; policies.py:134) with the
  * library's counter-based generator: element e of global row r gets Philox4x32-10
  * (key = seed, counter = (draw, r*H*td + e)) -> Box-Muller.  Result is independent of how
@@ -683,6 +709,32 @@ DAD_LAYOUT(DAD_PP_INTS, 0);
 DAD_LAYOUT(DAD_PP_FORMS, 0);
 int dad_debug_project_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch, int32_t horizon,
                            size_t scratch_bytes, int32_t violation, int32_t* out);
+/* Which kernels one dad_projection_violation_fwd / _bwd pair launches for trajectories (batch, horizon,
+ * observation_dim + action_dim) under `form` (-1, 0, 1 as there), on which grids, and the workspace it needs: the plan
+ * the two entry points launch from (plan_violation_grad).  Host logic only, no device call.  out[DAD_VG_INTS].
+ * DAD_E_INVALID for batch or horizon <= 0, state_dim > observation_dim or an unknown form; a forced row form that does
+ * not fit is reported (DAD_VG_REFUSED), not refused here. */
+#define DAD_VG_INTS_LIST(F) \
+    F(DAD_VG_FORM, form, 1, "DAD_VG_ROW / DAD_VG_GEMM: the form both passes take") \
+    F(DAD_VG_FWD_ROWS_PER_BLOCK, fwd_rows_per_block, 1, "forward: trajectories per block (row: 1 or 4, as dad_projection_violation plans; gemm: 32)") \
+    F(DAD_VG_FWD_GX, fwd_gx, 1, "... grid x (blocks over the batch)") \
+    F(DAD_VG_FWD_GY, fwd_gy, 1, "... grid y (gemm: 32-column blocks of P; row: 1)") \
+    F(DAD_VG_FWD_LDS_BYTES, fwd_lds_bytes, 1, "... dynamic LDS of one block") \
+    F(DAD_VG_FWD_SUM_GX, fwd_sum_gx, 1, "... blocks of the launch that adds the column blocks' partial sums per trajectory (gemm; row: 0, no such launch)") \
+    F(DAD_VG_BWD_ROWS_PER_BLOCK, bwd_rows_per_block, 1, "backward: trajectories per block (row: 1; gemm: 32)") \
+    F(DAD_VG_BWD_GX, bwd_gx, 1, "... grid x") \
+    F(DAD_VG_BWD_GY, bwd_gy, 1, "... grid y (gemm: 32-row blocks of P; row: 1)") \
+    F(DAD_VG_BWD_LDS_BYTES, bwd_lds_bytes, 1, "... dynamic LDS of one block") \
+    F(DAD_VG_BWD_SCATTER_GX, bwd_scatter_gx, 1, "... blocks of the launch that scatters g into d_x (gemm; row: 0, the row kernel scatters itself)") \
+    F(DAD_VG_WORKSPACE_BYTES, workspace_bytes, 1, "dad_violation_grad_workspace_bytes (capped at INT32_MAX): r (B, D), and in the gemm form the partial sums (B, column blocks) and g (B, D)") \
+    F(DAD_VG_REFUSED, refused, 1, "1: the calls fail with DAD_E_INVALID (a forced row form whose forward LDS, a row and its 16 partial sets, exceeds one CU's); the other fields then describe the launches that do not fit")
+DAD_LAYOUT(DAD_VG_INTS, 0);
+#define DAD_VG_FORMS_LIST(F) \
+    F(DAD_VG_ROW, row, 1, "project_kernel's violation branch keeping r, violation_bwd_row_kernel: one trajectory per block streams P") \
+    F(DAD_VG_GEMM, gemm, 1, "violation_fwd_gemm_kernel, violation_bwd_gemm_kernel: 32 trajectories x 32 columns per block, P read once per 32 trajectories")
+DAD_LAYOUT(DAD_VG_FORMS, 0);
+int dad_debug_violation_grad_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch,
+                                  int32_t horizon, int32_t form, int32_t* out);
 /* Whether dad_sample_loop at `batch` (projection != 0: called with a projection argument) takes the seam between two
  * denoise steps as one launch (csrc/conv_seam.hpp; the rule: plan_seam in csrc/host_plan.hpp), under the model's current
  * options.  Host logic only, no device call; the model needs no weights.  out[DAD_SEAM_INTS]. */
