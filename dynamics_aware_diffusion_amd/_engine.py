@@ -620,12 +620,8 @@ class HipEngine:
                      mean_out: Optional[torch.Tensor] = None,
                      eps_out: Optional[torch.Tensor] = None, update_x: bool = True) -> None:
         """In-place reverse step on ``x`` (see dad_denoise_step in include/dad.h)."""
-        B, a = self._step_args(x, noise, seed, row_offset, draw, cond0, guide_grad, guide_weight, mean_out, eps_out)
-        ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.dad_denoise_step(
-                self._h, x.data_ptr(), int(t), B, C.byref(a), int(not update_x), ws.data_ptr(),
-                ws.numel() * 4, self._stream()))
+        self._step(self.lib.dad_denoise_step, int(t), x, noise, seed, row_offset, draw, cond0, guide_grad,
+                   guide_weight, mean_out, eps_out, update_x)
 
     def sampler_step(self, x: torch.Tensor, coef, *, noise: Optional[torch.Tensor] = None,
                      seed: int = 0, row_offset: int = 0, draw: int = 0,
@@ -638,14 +634,13 @@ class HipEngine:
         one = _steps_array(np.asarray(coef).reshape(-1), "coef")
         if one.shape[0] != 1:
             raise ValueError("sampler_step takes one step")
-        B, a = self._step_args(x, noise, seed, row_offset, draw, cond0, guide_grad, guide_weight, mean_out, eps_out)
-        ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.dad_sampler_step(
-                self._h, x.data_ptr(), one.ctypes.data, B, C.byref(a), int(not update_x), ws.data_ptr(),
-                ws.numel() * 4, self._stream()))
+        self._step(self.lib.dad_sampler_step, one.ctypes.data, x, noise, seed, row_offset, draw, cond0, guide_grad,
+                   guide_weight, mean_out, eps_out, update_x)
 
-    def _step_args(self, x, noise, seed, row_offset, draw, cond0, guide_grad, guide_weight, mean_out, eps_out):
+    def _step(self, call, which, x, noise, seed, row_offset, draw, cond0, guide_grad, guide_weight, mean_out,
+              eps_out, update_x):
+        """One reverse step through ``call``, which takes the step itself (``which``: a timestep or a coefficient
+        row) right after ``x``."""
         B = self._traj(x)
         a = DadStepArgs()
         for name, ten in (("noise", noise), ("guide_grad", guide_grad), ("mean_out", mean_out),
@@ -655,15 +650,23 @@ class HipEngine:
                     raise RuntimeError(f"{name} batch mismatch")
                 setattr(a, name, ten.data_ptr())
         a.seed, a.row_offset, a.draw = int(seed), int(row_offset), int(draw)
-        if cond0 is not None:
-            _require_device(cond0, "cond0")
-            rows = cond0.reshape(-1, self.transition_dim).shape[0]
-            if rows not in (1, B):
-                raise RuntimeError(f"cond0 must be (1, td) or (B, td), got {tuple(cond0.shape)}")
-            a.cond0 = cond0.data_ptr()
-            a.cond_per_row = int(rows == B and B > 1)
+        a.cond0, a.cond_per_row = self._cond0(cond0, B)
         a.guide_weight = float(guide_weight)
-        return B, a
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            _check(self.lib, call(
+                self._h, x.data_ptr(), which, B, C.byref(a), int(not update_x), ws.data_ptr(),
+                ws.numel() * 4, self._stream()))
+
+    def _cond0(self, cond0: Optional[torch.Tensor], B: int):
+        """(pointer, one row per trajectory?) of the horizon-step-0 condition, (1, td) or (B, td)."""
+        if cond0 is None:
+            return None, 0
+        _require_device(cond0, "cond0")
+        rows = cond0.reshape(-1, self.transition_dim).shape[0]
+        if rows not in (1, B):
+            raise RuntimeError(f"cond0 must be (1, td) or (B, td), got {tuple(cond0.shape)}")
+        return cond0.data_ptr(), int(rows == B and B > 1)
 
     def sample_loop(self, x: torch.Tensor, n_steps: int, *,
                     noise_stack: Optional[torch.Tensor] = None, seed: int = 0,
@@ -671,16 +674,11 @@ class HipEngine:
                     projection: Optional["ProjectionState"] = None,
                     proj_alphas: Optional[Sequence[float]] = None,
                     use_graph: bool = False) -> None:
-        B, cond_ptr, per_row, pa = self._loop_args(x, n_steps, noise_stack, cond0, projection)
         alphas = None
         if projection is not None:
             alphas = (C.c_float * self.n_timesteps)(*[float(a) for a in proj_alphas])
-        ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.dad_sample_loop(
-                self._h, x.data_ptr(), int(n_steps), B, _ptr(noise_stack), int(seed),
-                int(row_offset), cond_ptr, per_row, pa, alphas, int(use_graph), ws.data_ptr(),
-                ws.numel() * 4, self._stream()))
+        self._loop(self.lib.dad_sample_loop, (int(n_steps),), int(n_steps), x, noise_stack, seed, row_offset, cond0,
+                   projection, alphas, use_graph)
 
     def sampler_loop(self, x: torch.Tensor, steps, *,
                      noise_stack: Optional[torch.Tensor] = None, seed: int = 0,
@@ -692,28 +690,19 @@ class HipEngine:
         ``proj_alphas`` and ``noise_stack`` (see dad_sampler_loop in include/dad.h)."""
         arr = _steps_array(steps, "steps")
         n_steps = int(arr.shape[0])
-        B, cond_ptr, per_row, pa = self._loop_args(x, n_steps, noise_stack, cond0, projection)
         alphas = None
         if projection is not None:
             if proj_alphas is None or len(proj_alphas) != n_steps:
                 raise ValueError("proj_alphas must hold one strength per step, in execution order")
             alphas = (C.c_float * n_steps)(*[float(a) for a in proj_alphas])
-        ws = self.workspace(B)
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.dad_sampler_loop(
-                self._h, x.data_ptr(), arr.ctypes.data, n_steps, B, _ptr(noise_stack), int(seed),
-                int(row_offset), cond_ptr, per_row, pa, alphas, int(use_graph), ws.data_ptr(),
-                ws.numel() * 4, self._stream()))
+        self._loop(self.lib.dad_sampler_loop, (arr.ctypes.data, n_steps), n_steps, x, noise_stack, seed, row_offset,
+                   cond0, projection, alphas, use_graph)
 
-    def _loop_args(self, x, n_steps, noise_stack, cond0, projection):
+    def _loop(self, call, which, n_steps, x, noise_stack, seed, row_offset, cond0, projection, alphas, use_graph):
+        """One fused loop through ``call``, which takes the steps themselves (``which``: their number, or their
+        coefficients and their number) right after ``x``; ``alphas`` is the C array that call reads."""
         B = self._traj(x)
-        cond_ptr, per_row = None, 0
-        if cond0 is not None:
-            _require_device(cond0, "cond0")
-            rows = cond0.reshape(-1, self.transition_dim).shape[0]
-            if rows not in (1, B):
-                raise RuntimeError(f"cond0 must be (1, td) or (B, td), got {tuple(cond0.shape)}")
-            cond_ptr, per_row = cond0.data_ptr(), int(rows == B and B > 1)
+        cond_ptr, per_row = self._cond0(cond0, B)
         if noise_stack is not None:
             _require_device(noise_stack, "noise_stack")
             if tuple(noise_stack.shape) != (n_steps, B, self.horizon, self.transition_dim):
@@ -722,7 +711,12 @@ class HipEngine:
         if projection is not None:
             projection._check_x(x)
             pa = C.byref(projection.args)
-        return B, cond_ptr, per_row, pa
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            _check(self.lib, call(
+                self._h, x.data_ptr(), *which, B, _ptr(noise_stack), int(seed),
+                int(row_offset), cond_ptr, per_row, pa, alphas, int(use_graph), ws.data_ptr(),
+                ws.numel() * 4, self._stream()))
 
     def fill_normal(self, x: torch.Tensor, seed: int, row_offset: int = 0, draw: int = 0) -> None:
         _require_device(x, "x")

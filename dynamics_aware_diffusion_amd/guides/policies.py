@@ -60,7 +60,7 @@ class GuidedPolicy(nn.Module):
         return grad.detach().contiguous()
 
     @staticmethod
-    def _split_conditions(conditions, engine_ok_only: bool = False):
+    def _split_conditions(conditions):
         """Horizon-step-0 condition goes into the fused kernel; any other step is applied
         with torch indexing afterwards."""
         cond0, rest = None, {}
@@ -102,133 +102,18 @@ class GuidedPolicy(nn.Module):
                     verbose: bool = False, row_offset: int = 0) -> torch.Tensor:
         """x_T ~ N(0, I) -> apply conditions -> T guided/inpainted reverse steps
         (policies.py:114-149).  Under ``diffusion.set_sampler("ddim", ...)`` the steps are the K strided ones over the
-        trained schedule, on the same routes; guidance then takes its DDIM form (``_sample_loop_strided``)."""
+        trained schedule, on the same routes; guidance then takes its DDIM form.  The loop itself is the diffusion
+        model's (``GaussianDiffusion._reverse_loop``): this hands it the conditions, the guide and the projector."""
         diff = self.diffusion
         device = diff.betas.device
-        shape = (batch_size, self.horizon, self.transition_dim)
-        n_steps = int(diff.n_timesteps)
-        diff._check_step(n_steps - 1)
         eng = diff._engine(device)
-        philox = diff.sampler_rng == "philox"
-        # the replayed-graph path needs persistent (address-stable) buffers; it is taken only for
-        # the fused loop below, so decide it before anything is allocated
-        _, rest_probe = self._split_conditions(conditions)
-        graph = bool(diff.use_graph) and not self._guided() and not rest_probe
-        if philox:
-            x = eng.persistent("x", shape) if graph else \
-                torch.empty(shape, device=device, dtype=torch.float32)
-            eng.fill_normal(x, diff.seed, row_offset=row_offset, draw=0)
-        else:
-            x = torch.randn(shape, device=device)
-            if graph:
-                x = eng.persistent("x", shape).copy_(x)
         if conditions is not None:
             conditions = {k: v.to(device, torch.float32) for k, v in conditions.items()}
-            x = self.apply_conditions(x, conditions)
         cond0, rest = self._split_conditions(conditions)
-        c0 = None if cond0 is None else cond0.contiguous()
-        if graph and c0 is not None:                       # frozen pointer: stage the condition
-            c0 = eng.persistent("cond0", tuple(c0.shape)).copy_(c0)
-        projector = self._loop_projector()
-        plan = diff.sampler_plan()
-        if plan is not None:
-            return self._sample_loop_strided(eng, plan, x, c0, rest, projector, graph, row_offset)
-
-        if not self._guided() and not rest:
-            alphas = None
-            if projector is not None:
-                alphas = [self._get_projection_alpha(i) for i in range(int(diff.betas.shape[0]))]
-            if philox:
-                eng.sample_loop(x, n_steps, seed=diff.seed, row_offset=row_offset, cond0=c0,
-                                projection=projector, proj_alphas=alphas, use_graph=graph)
-            elif diff.noise_stack_bytes(shape, n_steps) > diff.max_noise_stack_bytes:
-                # the whole z stack would not be O(1) in T (1.1 GB for Door at B=128, T=1000): draw z
-                # step by step instead — the same torch.randn calls in the same order, one engine
-                # step per iteration
-                for i in reversed(range(n_steps)):
-                    eng.denoise_step(x, i, noise=torch.randn(shape, device=device), cond0=c0)
-                    if projector is not None:
-                        projector.apply(x, alphas[i])
-                return x.clone() if graph else x
-            else:
-                stack = eng.persistent("z", (n_steps,) + shape) if graph else \
-                    torch.empty((n_steps,) + shape, device=device)
-                for j in range(n_steps):
-                    torch.randn(shape, out=stack[j])
-                eng.sample_loop(x, n_steps, noise_stack=stack, cond0=c0, projection=projector,
-                                proj_alphas=alphas, use_graph=graph)
-            return x.clone() if graph else x
-
-        # guided (or multi-step-conditioned) path: one engine step per iteration, the guide
-        # gradient comes from PyTorch autograd on the user's value model.
-        for j, i in enumerate(reversed(range(n_steps))):
-            grad, gw = None, 0.0
-            if self._guided():
-                tt = torch.full((batch_size,), i, device=device, dtype=torch.long)
-                grad = self._guide_gradient(x, tt).float()
-                gw = float(self.guide_weight)
-            if philox:
-                eng.denoise_step(x, i, seed=diff.seed, row_offset=row_offset, draw=j + 1, cond0=c0,
-                                 guide_grad=grad, guide_weight=gw)
-            else:
-                eng.denoise_step(x, i, noise=torch.randn_like(x), cond0=c0, guide_grad=grad,
-                                 guide_weight=gw)
-            if rest:
-                self.apply_conditions(x, rest)
-            if projector is not None:
-                projector.apply(x, self._get_projection_alpha(i))
-        return x
-
-    def _sample_loop_strided(self, eng, plan, x, c0, rest, projector, graph: bool, row_offset: int) -> torch.Tensor:
-        """The reverse steps of ``sample_loop`` under the strided sampler, from x_T with its conditions applied.
-
-        Iteration j runs step ``steps[j]`` at timestep ``taus[j]`` (descending) with Philox draw j + 1 — or, on the
-        torch route, the j-th ``randn`` after x_T's; ``eta == 0`` draws nothing after x_T.  The projection strength is
-        ``_get_projection_alpha(tau)``.  A guide is classifier guidance in its DDIM form, eps' = eps - w sqrt(1 - abar)
-        g with g the guide's gradient at x_t: the tail kernels apply it as the shift of x0 it causes (the ancestral
-        form scales by the step's variance, which is 0 at eta == 0)."""
-        diff = self.diffusion
-        steps, taus, eta = plan
-        device, shape, K = x.device, tuple(x.shape), len(steps)
-        philox = diff.sampler_rng == "philox"
-        alphas = None if projector is None else [self._get_projection_alpha(t) for t in taus]
-
-        if not self._guided() and not rest:
-            if philox:
-                eng.sampler_loop(x, steps, seed=diff.seed, row_offset=row_offset, cond0=c0,
-                                 projection=projector, proj_alphas=alphas, use_graph=graph)
-            elif eta > 0.0 and diff.noise_stack_bytes(shape, K) > diff.max_noise_stack_bytes:
-                for j in range(K):
-                    eng.sampler_step(x, steps[j], noise=torch.randn(shape, device=device), cond0=c0)
-                    if projector is not None:
-                        projector.apply(x, alphas[j])
-            else:
-                stack = None
-                if eta > 0.0:
-                    stack = eng.persistent("z", (K,) + shape) if graph else torch.empty((K,) + shape, device=device)
-                    for j in range(K):
-                        torch.randn(shape, out=stack[j])
-                eng.sampler_loop(x, steps, noise_stack=stack, cond0=c0, projection=projector,
-                                 proj_alphas=alphas, use_graph=graph)
-            return x.clone() if graph else x
-
-        for j, t in enumerate(taus):
-            grad, gw = None, 0.0
-            if self._guided():
-                tt = torch.full((shape[0],), t, device=device, dtype=torch.long)
-                grad = self._guide_gradient(x, tt).float()
-                gw = float(self.guide_weight)
-            if philox or eta == 0.0:
-                eng.sampler_step(x, steps[j], seed=diff.seed, row_offset=row_offset, draw=j + 1, cond0=c0,
-                                 guide_grad=grad, guide_weight=gw)
-            else:
-                eng.sampler_step(x, steps[j], noise=torch.randn_like(x), cond0=c0, guide_grad=grad,
-                                 guide_weight=gw)
-            if rest:
-                self.apply_conditions(x, rest)
-            if projector is not None:
-                projector.apply(x, alphas[j])
-        return x
+        return diff._reverse_loop(eng, (batch_size, self.horizon, self.transition_dim), row_offset, cond0, rest,
+                                  guide=self._guide_gradient if self._guided() else None,
+                                  guide_weight=self.guide_weight, projector=self._loop_projector(),
+                                  alpha_of=lambda t: self._get_projection_alpha(t))
 
     def _loop_projector(self) -> Optional[ProjectionState]:
         return None

@@ -133,6 +133,50 @@ def ddim_table(alphas_cumprod, timesteps_or_K, eta: float = 0.0) -> Dict[str, np
             "guide_mean": np.zeros_like(ab), "sigma": sigma}
 
 
+class _LoopSteps:
+    """The steps one sampling loop runs, in execution order: all that differs between the samplers.
+
+    ``timesteps[j]`` is the timestep of iteration j; ``takes_noise`` says whether an iteration consumes a z;
+    ``step(eng, x, j, **kw)`` runs iteration j alone; ``loop(eng, x, alphas, **kw)`` runs all of them as the fused
+    engine loop, ``alphas`` being ``None`` or one projection strength per iteration."""
+
+    def __init__(self, timesteps, takes_noise, step, loop):
+        self.timesteps, self.takes_noise, self.step, self.loop = timesteps, takes_noise, step, loop
+
+    @classmethod
+    def ancestral(cls, n_steps: int, n_trained: int) -> "_LoopSteps":
+        """t = n_steps-1 .. 0 over the first ``n_steps`` of ``n_trained`` schedule entries; the library holds the
+        coefficients (dad_denoise_step / dad_sample_loop)."""
+        timesteps = list(reversed(range(n_steps)))
+
+        def step(eng, x, j, **kw):
+            eng.denoise_step(x, timesteps[j], **kw)
+
+        def loop(eng, x, alphas, **kw):
+            table = None
+            if alphas is not None:                 # dad_sample_loop reads its strengths by timestep, not by iteration
+                table = [0.0] * n_trained
+                for t, a in zip(timesteps, alphas):
+                    table[t] = a
+            eng.sample_loop(x, n_steps, proj_alphas=table, **kw)
+
+        return cls(timesteps, True, step, loop)
+
+    @classmethod
+    def strided(cls, plan) -> "_LoopSteps":
+        """The steps of ``GaussianDiffusion.sampler_plan()``, given by their coefficients (dad_sampler_step /
+        dad_sampler_loop); ``eta == 0`` makes sigma 0 at every step, so x_T is the only draw."""
+        steps, taus, eta = plan
+
+        def step(eng, x, j, **kw):
+            eng.sampler_step(x, steps[j], **kw)
+
+        def loop(eng, x, alphas, **kw):
+            eng.sampler_loop(x, steps, proj_alphas=alphas, **kw)
+
+        return cls(taus, eta > 0.0, step, loop)
+
+
 class GaussianDiffusion(nn.Module):
     """DDPM over trajectories (batch, horizon, observation_dim + action_dim).
 
@@ -312,59 +356,95 @@ class GaussianDiffusion(nn.Module):
         loop then walks the first ``n_timesteps`` entries of the trained schedule.  Under
         ``set_sampler("ddim", ...)`` it is the K-step strided loop over the whole trained schedule instead.
         """
-        device = self.betas.device
-        eng = self._engine(device)
+        return self._reverse_loop(self._engine(self.betas.device), tuple(shape), row_offset)
+
+    def _loop_steps(self) -> "_LoopSteps":
+        """What ``set_sampler`` chose, as the steps a loop runs."""
         plan = self.sampler_plan()
         if plan is not None:
-            return self._strided_loop(eng, plan, tuple(shape), row_offset)
-        n_steps = int(self.n_timesteps)
-        self._check_step(n_steps - 1)
-        if self.sampler_rng == "philox":
-            x = eng.persistent("x", shape) if self.use_graph else \
-                torch.empty(shape, device=device, dtype=torch.float32)
-            eng.fill_normal(x, self.seed, row_offset=row_offset, draw=0)
-            eng.sample_loop(x, n_steps, seed=self.seed, row_offset=row_offset,
-                            use_graph=self.use_graph)
-            return x.clone() if self.use_graph else x
-        x = torch.randn(shape, device=device)
-        if self.noise_stack_bytes(shape, n_steps) > self.max_noise_stack_bytes:
-            # O(1) in T: z drawn per step with the reference's own call order (diffusion.py:218)
-            for i in reversed(range(n_steps)):
-                eng.denoise_step(x, i, noise=torch.randn(tuple(shape), device=device))
-            return x
-        if self.use_graph:
-            x = eng.persistent("x", shape).copy_(x)
-        stack = eng.persistent("z", (n_steps,) + tuple(shape)) if self.use_graph else \
-            torch.empty((n_steps,) + tuple(shape), device=device)
-        for j in range(n_steps):
-            torch.randn(tuple(shape), out=stack[j])
-        eng.sample_loop(x, n_steps, noise_stack=stack, use_graph=self.use_graph)
-        return x.clone() if self.use_graph else x
+            return _LoopSteps.strided(plan)
+        self._check_step(int(self.n_timesteps) - 1)
+        return _LoopSteps.ancestral(int(self.n_timesteps), int(self.betas.shape[0]))
 
-    def _strided_loop(self, eng, plan, shape: tuple, row_offset: int) -> torch.Tensor:
-        """p_sample_loop under the strided sampler: the same routes, K steps given by their coefficients."""
-        steps, _, eta = plan
-        device, K = self.betas.device, len(steps)
-        if self.sampler_rng == "philox":
-            x = eng.persistent("x", shape) if self.use_graph else \
-                torch.empty(shape, device=device, dtype=torch.float32)
+    def _reverse_loop(self, eng, shape: tuple, row_offset: int, cond0: Optional[torch.Tensor] = None,
+                      rest: Optional[Dict[int, torch.Tensor]] = None, guide=None, guide_weight: float = 0.0,
+                      projector=None, alpha_of=None) -> torch.Tensor:
+        """Every sampling loop: x_T ~ N(0, I), the conditions, then the reverse steps of ``_loop_steps`` by the one
+        route the settings allow.  ``p_sample_loop`` is this with nothing but a shape; the policies' ``sample_loop``
+        adds the rest.
+
+        ``cond0`` / ``rest``: the condition at horizon step 0 (the engine inpaints it inside every step) and those
+        at other steps ``{k: value}`` (written with torch indexing after each step), on the device as float32.
+        ``guide(x, t_tensor) -> grad`` with its ``guide_weight``: the guide's gradient at x_t, fused into the step
+        (the ancestral step scales it by the variance; the strided one takes classifier guidance in its DDIM form,
+        eps' = eps - w sqrt(1 - abar) g, as the shift of x0 it causes).  ``projector.apply(x, alpha_of(t))`` follows
+        the step at timestep t.
+
+        Philox: x_T is draw 0 and iteration j's z is draw j + 1 of (``seed``, ``row_offset`` + row).  torch: x_T is
+        the first ``randn`` and iteration j's z the next one after it, in the reference's call order
+        (diffusion.py:241,218); a loop whose steps take no noise draws nothing after x_T."""
+        device = self.betas.device
+        steps = self._loop_steps()
+        n, rest = len(steps.timesteps), rest or {}
+        philox = self.sampler_rng == "philox"
+        # the fused engine loop knows no guide and no condition beyond horizon step 0.  Only it replays a graph, which
+        # needs persistent (address-stable) buffers and hands the result out as a copy: decided before any allocation
+        fused = guide is None and not rest
+        graph = bool(self.use_graph) and fused
+        if philox:
+            x = eng.persistent("x", shape) if graph else torch.empty(shape, device=device, dtype=torch.float32)
             eng.fill_normal(x, self.seed, row_offset=row_offset, draw=0)
-            eng.sampler_loop(x, steps, seed=self.seed, row_offset=row_offset, use_graph=self.use_graph)
-            return x.clone() if self.use_graph else x
-        x = torch.randn(shape, device=device)
-        if eta > 0.0 and self.noise_stack_bytes(shape, K) > self.max_noise_stack_bytes:
-            for j in range(K):
-                eng.sampler_step(x, steps[j], noise=torch.randn(shape, device=device))
-            return x
-        if self.use_graph:
-            x = eng.persistent("x", shape).copy_(x)
-        stack = None
-        if eta > 0.0:                     # eta == 0: sigma is 0 at every step, so x_T is the only draw
-            stack = eng.persistent("z", (K,) + shape) if self.use_graph else torch.empty((K,) + shape, device=device)
-            for j in range(K):
-                torch.randn(shape, out=stack[j])
-        eng.sampler_loop(x, steps, noise_stack=stack, use_graph=self.use_graph)
-        return x.clone() if self.use_graph else x
+        else:
+            x = torch.randn(shape, device=device)
+            if graph:
+                x = eng.persistent("x", shape).copy_(x)
+        if cond0 is not None:
+            x[:, 0] = cond0
+            cond0 = cond0.contiguous()
+            if graph:                                          # frozen pointer: stage the condition
+                cond0 = eng.persistent("cond0", tuple(cond0.shape)).copy_(cond0)
+        for k, v in rest.items():
+            x[:, k] = v
+        alphas = None if projector is None else [alpha_of(t) for t in steps.timesteps]
+
+        if fused:
+            kw = dict(cond0=cond0, projection=projector, use_graph=graph)
+            if philox:
+                steps.loop(eng, x, alphas, seed=self.seed, row_offset=row_offset, **kw)
+            elif steps.takes_noise and self.noise_stack_bytes(shape, n) > self.max_noise_stack_bytes:
+                # the whole z stack would not be O(1) in T (1.1 GB for Door at B=128, T=1000): draw z step by step
+                # instead: the same torch.randn calls in the same order, one engine step per iteration
+                for j in range(n):
+                    steps.step(eng, x, j, noise=torch.randn(shape, device=device), cond0=cond0)
+                    if projector is not None:
+                        projector.apply(x, alphas[j])
+            else:
+                stack = None
+                if steps.takes_noise:
+                    stack = eng.persistent("z", (n,) + shape) if graph else torch.empty((n,) + shape, device=device)
+                    for j in range(n):
+                        torch.randn(shape, out=stack[j])
+                # (no stack and no seed: nothing is drawn, the loop's default Philox stream is never read)
+                steps.loop(eng, x, alphas, noise_stack=stack, **kw)
+            return x.clone() if graph else x
+
+        # guided (or multi-step-conditioned) route: one engine step per iteration, the guide gradient comes from
+        # PyTorch autograd on the user's value model.
+        for j, t in enumerate(steps.timesteps):
+            grad, gw = None, 0.0
+            if guide is not None:
+                grad = guide(x, torch.full((shape[0],), t, device=device, dtype=torch.long)).float()
+                gw = float(guide_weight)
+            if philox or not steps.takes_noise:
+                steps.step(eng, x, j, seed=self.seed, row_offset=row_offset, draw=j + 1, cond0=cond0,
+                           guide_grad=grad, guide_weight=gw)
+            else:
+                steps.step(eng, x, j, noise=torch.randn_like(x), cond0=cond0, guide_grad=grad, guide_weight=gw)
+            for k, v in rest.items():
+                x[:, k] = v
+            if projector is not None:
+                projector.apply(x, alphas[j])
+        return x
 
     # ------------------------------------------------------------------ training objective
     def loss(self, x_start: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
