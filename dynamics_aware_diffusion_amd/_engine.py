@@ -80,6 +80,20 @@ class DadProjectArgs(C.Structure):
     ]
 
 
+DAD_GUIDE_MAX_LAYERS = 4
+
+
+class DadGuideArgs(C.Structure):
+    _fields_ = [
+        ("n_layers", C.c_int32), ("in_dim", C.c_int32),
+        ("widths", C.c_int32 * DAD_GUIDE_MAX_LAYERS), ("padded", C.c_int32 * DAD_GUIDE_MAX_LAYERS),
+        ("activation", C.c_int32),
+        ("w_fwd", C.c_void_p * DAD_GUIDE_MAX_LAYERS), ("w_bwd", C.c_void_p * DAD_GUIDE_MAX_LAYERS),
+        ("bias", C.c_void_p * DAD_GUIDE_MAX_LAYERS),
+        ("grad", C.c_void_p), ("grad_bytes", C.c_size_t),
+    ]
+
+
 class DadOptimTensor(C.Structure):
     _fields_ = [
         ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
@@ -147,6 +161,15 @@ ABI = {
                                    C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32,
                                    C.POINTER(DadProjectArgs), C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
+    "dad_guide_grad": (C.c_int, [C.POINTER(DadGuideArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_void_p]),
+    "dad_guided_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32,
+                                  C.POINTER(DadGuideArgs), C.c_float,
+                                  C.POINTER(DadProjectArgs), C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
+    "dad_debug_guide_plan": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.POINTER(C.c_int32)]),
     "dad_project": (C.c_int, [C.POINTER(DadProjectArgs), C.c_float, C.c_void_p, C.c_int32,
                               C.c_int32, C.c_void_p]),
     "dad_fill_normal": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
@@ -407,6 +430,32 @@ def violation_grad_plan(state_dim: int, observation_dim: int, action_dim: int, b
         plan[side] = d
     assert not q, q
     return plan
+
+
+def guide_plan(in_dim: int, widths: Sequence[int], activation, batch: int, horizon: int,
+               transition_dim: Optional[int] = None) -> dict:
+    """What one guide launch (dad_guide_grad, and every guide launch of dad_guided_loop) is for the value net
+    in_dim -> widths[0] -> ... -> widths[-1] with ``activation`` ("tanh", "relu", "mish", or the library's code) on
+    trajectories (batch, horizon, transition_dim; default in_dim), decoded by name (dad_debug_guide_plan: the plan the
+    entry points launch from and the one statement of the limits; host logic only).  ``padded``: the zero-padded in_dim
+    and hidden widths, ``rows_per_block``, ``threads``, ``grid``, ``lds_bytes``, and ``refused``: None, or the name of
+    the first limit the net misses ("layers", "width", "activation", "in_dim", "last_width", "lds")."""
+    lib = load_library()
+    acts = _names("DAD_GD_ACTS")
+    code = acts.index(activation) if activation in acts else activation if isinstance(activation, int) else -1
+    n = len(widths)
+    w = (C.c_int32 * max(n, 1))(*[int(v) for v in widths])
+    out = (C.c_int32 * _fields("DAD_GD_INTS")[1])()
+    _check(lib, lib.dad_debug_guide_plan(int(in_dim), w, n, int(code), int(batch), int(horizon),
+                                         int(in_dim if transition_dim is None else transition_dim), out))
+    q = _decode("DAD_GD_INTS", out)
+    hidden = max(min(n, DAD_GUIDE_MAX_LAYERS) - 1, 0)
+    q["padded"] = [q.pop("padded_in")] + [q.pop(f"padded_{i}") for i in (1, 2, 3)][:hidden]
+    for k in ("padded_1", "padded_2", "padded_3"):
+        q.pop(k, None)
+    q["grid"] = q.pop("gx")
+    q["refused"] = None if q["refused"] == 0 else _names("DAD_GD_REFUSALS")[q["refused"]]
+    return q
 
 
 def optim_plan(numel: Sequence[int]) -> dict:
@@ -673,7 +722,14 @@ class HipEngine:
                     row_offset: int = 0, cond0: Optional[torch.Tensor] = None,
                     projection: Optional["ProjectionState"] = None,
                     proj_alphas: Optional[Sequence[float]] = None,
-                    use_graph: bool = False) -> None:
+                    use_graph: bool = False, guide: Optional["GuideState"] = None, guide_weight: float = 0.0) -> None:
+        """``guide`` (a :class:`GuideState`) with a positive ``guide_weight``: the same loop with the guide evaluated
+        inside it (:meth:`guided_loop`)."""
+        if guide is not None and guide_weight > 0:
+            order = None if projection is None else [float(proj_alphas[t]) for t in reversed(range(int(n_steps)))]
+            return self.guided_loop(x, guide, guide_weight, n_steps=int(n_steps), noise_stack=noise_stack, seed=seed,
+                                    row_offset=row_offset, cond0=cond0, projection=projection, proj_alphas=order,
+                                    use_graph=use_graph)
         alphas = None
         if projection is not None:
             alphas = (C.c_float * self.n_timesteps)(*[float(a) for a in proj_alphas])
@@ -685,9 +741,14 @@ class HipEngine:
                      row_offset: int = 0, cond0: Optional[torch.Tensor] = None,
                      projection: Optional["ProjectionState"] = None,
                      proj_alphas: Optional[Sequence[float]] = None,
-                     use_graph: bool = False) -> None:
+                     use_graph: bool = False, guide: Optional["GuideState"] = None, guide_weight: float = 0.0) -> None:
         """``sample_loop`` over caller-given steps: ``steps`` is ``pack_sampler_steps`` in execution order, and so are
-        ``proj_alphas`` and ``noise_stack`` (see dad_sampler_loop in include/dad.h)."""
+        ``proj_alphas`` and ``noise_stack`` (see dad_sampler_loop in include/dad.h).  ``guide`` / ``guide_weight`` as
+        :meth:`sample_loop`."""
+        if guide is not None and guide_weight > 0:
+            return self.guided_loop(x, guide, guide_weight, steps=steps, noise_stack=noise_stack, seed=seed,
+                                    row_offset=row_offset, cond0=cond0, projection=projection, proj_alphas=proj_alphas,
+                                    use_graph=use_graph)
         arr = _steps_array(steps, "steps")
         n_steps = int(arr.shape[0])
         alphas = None
@@ -698,9 +759,40 @@ class HipEngine:
         self._loop(self.lib.dad_sampler_loop, (arr.ctypes.data, n_steps), n_steps, x, noise_stack, seed, row_offset,
                    cond0, projection, alphas, use_graph)
 
-    def _loop(self, call, which, n_steps, x, noise_stack, seed, row_offset, cond0, projection, alphas, use_graph):
+    def guided_loop(self, x: torch.Tensor, guide: "GuideState", guide_weight: float, *, steps=None,
+                    n_steps: Optional[int] = None, noise_stack: Optional[torch.Tensor] = None, seed: int = 0,
+                    row_offset: int = 0, cond0: Optional[torch.Tensor] = None,
+                    projection: Optional["ProjectionState"] = None,
+                    proj_alphas: Optional[Sequence[float]] = None, use_graph: bool = False) -> None:
+        """The fused loop with a library guide inside it (see dad_guided_loop in include/dad.h): ``steps`` as
+        :meth:`sampler_loop` takes them, or None for the ``n_steps`` ancestral steps of the loaded schedule;
+        ``proj_alphas`` in execution order either way.  The gradient scratch the guide launch hands to the step's
+        tail is the guide's own, or under ``use_graph`` a persistent buffer of this engine (a frozen pointer)."""
+        arr = None
+        if steps is not None:
+            arr = _steps_array(steps, "steps")
+            n_steps = int(arr.shape[0])
+        if n_steps is None:
+            raise ValueError("guided_loop needs steps or n_steps")
+        alphas = None
+        if projection is not None:
+            if proj_alphas is None or len(proj_alphas) != n_steps:
+                raise ValueError("proj_alphas must hold one strength per step, in execution order")
+            alphas = (C.c_float * n_steps)(*[float(a) for a in proj_alphas])
+        self._traj(x)
+        ga = None
+        if guide is not None and guide_weight > 0:
+            guide.refresh()
+            guide.bind_scratch(self.persistent("guide_grad", tuple(x.shape)) if use_graph else None, x)
+            ga = C.byref(guide.args)
+        self._loop(self.lib.dad_guided_loop, (None if arr is None else arr.ctypes.data, int(n_steps)), int(n_steps), x,
+                   noise_stack, seed, row_offset, cond0, projection, alphas, use_graph, (ga, float(guide_weight)))
+
+    def _loop(self, call, which, n_steps, x, noise_stack, seed, row_offset, cond0, projection, alphas, use_graph,
+              guide=()):
         """One fused loop through ``call``, which takes the steps themselves (``which``: their number, or their
-        coefficients and their number) right after ``x``; ``alphas`` is the C array that call reads."""
+        coefficients and their number) right after ``x``; ``alphas`` is the C array that call reads; ``guide``: the
+        two arguments dad_guided_loop takes after the condition."""
         B = self._traj(x)
         cond_ptr, per_row = self._cond0(cond0, B)
         if noise_stack is not None:
@@ -715,7 +807,7 @@ class HipEngine:
         with torch.cuda.device(self.device):
             _check(self.lib, call(
                 self._h, x.data_ptr(), *which, B, _ptr(noise_stack), int(seed),
-                int(row_offset), cond_ptr, per_row, pa, alphas, int(use_graph), ws.data_ptr(),
+                int(row_offset), cond_ptr, per_row, *guide, pa, alphas, int(use_graph), ws.data_ptr(),
                 ws.numel() * 4, self._stream()))
 
     def fill_normal(self, x: torch.Tensor, seed: int, row_offset: int = 0, draw: int = 0) -> None:
@@ -1273,3 +1365,148 @@ class ProjectionState:
             _check(lib, lib.dad_project(C.byref(self.args), float(alpha), x.data_ptr(),
                                         int(x.shape[0]), int(x.shape[1]),
                                         torch.cuda.current_stream(self.device).cuda_stream))
+
+
+GUIDE_ACTIVATIONS = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu", torch.nn.Mish: "mish"}
+
+
+class GuideState:
+    """A value model the library evaluates itself (dad_guide_grad, dad_guided_loop): an ``nn.Sequential`` of 2 to 4
+    ``nn.Linear`` alternating with one of ``nn.Tanh`` / ``nn.ReLU`` / ``nn.Mish`` (the same throughout), ending in
+    ``Linear(., 1)``, applied to the first ``in_dim`` channels of every horizon step and summed over the horizon
+    (guides/policies.py:243-271).  Holds the zero-padded weight images, each in both orientations, and the
+    ``dad_guide_args`` that point at them; :meth:`compile` builds one, :meth:`refresh` follows the module's parameters.
+    """
+
+    def __init__(self):
+        raise TypeError("GuideState.compile(module, in_dim, device) builds a GuideState")
+
+    @staticmethod
+    def recognise(module, in_dim: int):
+        """((Linear, ...), activation name) of a module of the supported form, or (None, why not)."""
+        nn = torch.nn
+        if not isinstance(module, nn.Sequential):
+            return None, f"the value model is a {type(module).__name__}, not an nn.Sequential"
+        mods = list(module)
+        if len(mods) % 2 == 0 or not all(isinstance(m, nn.Linear) for m in mods[0::2]):
+            return None, "the value model does not alternate nn.Linear with an activation, ending in nn.Linear"
+        linears, acts = mods[0::2], mods[1::2]
+        if not acts:
+            return None, "the value model has no hidden layer"
+        kinds = {type(a) for a in acts}
+        if len(kinds) != 1 or next(iter(kinds)) not in GUIDE_ACTIVATIONS:
+            return None, ("the activations are " + ", ".join(sorted(k.__name__ for k in kinds)) +
+                          ": one of nn.Tanh, nn.ReLU, nn.Mish throughout is needed")
+        if linears[0].in_features != int(in_dim):
+            return None, f"the first layer reads {linears[0].in_features} features, the guide is given {int(in_dim)}"
+        for a, b in zip(linears, linears[1:]):
+            if b.in_features != a.out_features:
+                return None, f"layer widths do not chain ({a.out_features} -> {b.in_features})"
+        if linears[-1].out_features != 1:
+            return None, f"the last layer has {linears[-1].out_features} outputs, not 1"
+        for p in module.parameters():
+            if p.dtype != torch.float32:
+                return None, f"a parameter is {p.dtype}, not float32"
+        return tuple(linears), GUIDE_ACTIVATIONS[next(iter(kinds))]
+
+    @classmethod
+    def compile(cls, module, in_dim: int, device=None, *, host: bool = False):
+        """``(state, None)``, or ``(None, reason)`` for a module the library does not evaluate.  ``device``: where the
+        engine runs; the parameters must live there.  ``host``: recognise and plan only, no device (CPU modules):
+        enough for :meth:`plan`."""
+        linears, act = cls.recognise(module, in_dim)
+        if linears is None:
+            return None, act
+        widths = [int(l.out_features) for l in linears]
+        plan = guide_plan(in_dim, widths, act, 1, 1)
+        if plan["refused"] is not None:
+            return None, f"the planner refuses the net: {plan['refused']} (in_dim {in_dim}, widths {widths}, {act})"
+        dev = None
+        if not host:
+            dev = torch.device(device)
+            if dev.type != "cuda":
+                raise RuntimeError("the guide kernel needs a ROCm device; there is no CPU path")
+            for p in module.parameters():
+                if p.device != dev:
+                    return None, f"a parameter lives on {p.device}, the engine on {dev}"
+        self = cls.__new__(cls)
+        self.module, self.linears, self.activation = module, linears, act
+        self.in_dim, self.widths, self.padded = int(in_dim), widths, plan["padded"]
+        self.device, self._dirty, self._key, self._scratch = dev, True, None, None
+        a = DadGuideArgs()
+        a.n_layers, a.in_dim = len(widths), int(in_dim)
+        a.activation = _names("DAD_GD_ACTS").index(act)
+        for i, w in enumerate(widths):
+            a.widths[i] = w
+        for i, w in enumerate(self.padded):
+            a.padded[i] = w
+        self.args = a
+        self._images = None
+        if not host:
+            L, pad = len(widths), self.padded
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+            self._images = [(z(pad[i], pad[i + 1]), z(pad[i + 1], pad[i]), z(pad[i + 1])) for i in range(L - 1)]
+            self._images.append((z(pad[L - 1]), None, z(1)))
+            for i, (wf, wb, b) in enumerate(self._images):
+                a.w_fwd[i], a.w_bwd[i], a.bias[i] = wf.data_ptr(), _ptr(wb), b.data_ptr()
+            self.refresh()
+        return self, None
+
+    def _param_key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.module.parameters())
+
+    def mark_changed(self) -> None:
+        """Tell the state that parameter values changed without their versions (a ``.data`` update), as
+        ``TemporalUnet.mark_weights_changed`` does for the denoiser."""
+        self._dirty = True
+
+    def refresh(self) -> None:
+        """Rebuild the padded images, in place (captured loops keep their pointers and follow the values), when any
+        parameter's (data_ptr, _version) changed or :meth:`mark_changed` was called."""
+        if self._images is None:
+            return
+        key = self._param_key()
+        if not self._dirty and key == self._key:
+            return
+        with torch.no_grad():
+            L = len(self.linears)
+            for i, (lin, (wf, wb, b)) in enumerate(zip(self.linears, self._images)):
+                n, k = lin.weight.shape
+                if i < L - 1:
+                    wf[:k, :n].copy_(lin.weight.detach().t())
+                    wb[:n, :k].copy_(lin.weight.detach())
+                    b[:n].copy_(lin.bias.detach()) if lin.bias is not None else b.zero_()
+                else:
+                    wf[:k].copy_(lin.weight.detach()[0])
+                    b.copy_(lin.bias.detach()) if lin.bias is not None else b.zero_()
+        self._key, self._dirty = key, False
+
+    def plan(self, batch: int, horizon: int, transition_dim: Optional[int] = None) -> dict:
+        """What one guide launch is for ``batch`` trajectories of ``horizon`` steps (:func:`guide_plan`; no device)."""
+        return guide_plan(self.in_dim, self.widths, self.activation, batch, horizon, transition_dim)
+
+    def bind_scratch(self, scratch: Optional[torch.Tensor], x: torch.Tensor) -> None:
+        """Point ``dad_guide_args.grad`` at ``scratch`` (as large as ``x``), or at a buffer of the state's own."""
+        if scratch is None:
+            if self._scratch is None or self._scratch.numel() < x.numel():
+                self._scratch = torch.empty(x.numel(), dtype=torch.float32, device=self.device)
+            scratch = self._scratch
+        self.args.grad, self.args.grad_bytes = scratch.data_ptr(), scratch.numel() * 4
+
+    def grad(self, x: torch.Tensor, value_rows: bool = False):
+        """d/dx of sum over the horizon of the value model on ``x[..., :in_dim]``, (B, H, td) (dad_guide_grad: one
+        launch, asynchronous); with ``value_rows`` also the per-row values (B, H)."""
+        _require_device(x, "x")
+        if x.dim() != 3 or x.shape[2] < self.in_dim:
+            raise RuntimeError(f"x must be (B, H, td >= {self.in_dim}), got {tuple(x.shape)}")
+        if x.device != self.device:
+            raise RuntimeError(f"x is on {x.device}, the guide on {self.device}")
+        self.refresh()
+        g = torch.empty_like(x)
+        v = torch.empty(x.shape[:2], dtype=torch.float32, device=x.device) if value_rows else None
+        lib = load_library()
+        with torch.cuda.device(self.device):
+            _check(lib, lib.dad_guide_grad(C.byref(self.args), x.data_ptr(), g.data_ptr(), _ptr(v), int(x.shape[0]),
+                                           int(x.shape[1]), int(x.shape[2]),
+                                           torch.cuda.current_stream(self.device).cuda_stream))
+        return (g, v) if value_rows else g

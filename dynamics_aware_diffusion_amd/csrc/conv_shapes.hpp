@@ -146,4 +146,21 @@ constexpr int VG_PS = PG_KC + 1;
 DAD_HD inline size_t vg_gemm_bwd_lds_floats() { return (size_t)4 * (PG_KC * PG_AS + 32 * VG_PS); }
 constexpr int VG_TAIL_THREADS = 256;          // violation_sum_kernel, violation_scatter_kernel
 
+// guide_mlp.hpp: one block owns GM_ROWS consecutive rows of B * H; every kept tensor is [width][GM_AS] in LDS (the
+// row index contiguous: the A operand's layout, odd stride).  The limits of the value nets the library evaluates
+// are stated here and nowhere else (plan_guide reads them; the binding and the tests read plan_guide).
+constexpr int GM_THREADS = 256;
+constexpr int GM_ROWS = 32;
+constexpr int GM_AS = 33;
+constexpr int GM_MIN_LAYERS = 2, GM_MAX_LAYERS = 4;        // Linear layers, the last one with a single output
+constexpr int GM_MAX_WIDTH = 512;                          // hidden units of one layer
+DAD_HD inline int guide_pad(int width) { return (width + 31) / 32 * 32; }      // whole 32-column MFMA tiles (and even K)
+// LDS floats: the input tile and every hidden activation (later overwritten by its delta), each zero-padded to whole
+// tiles; `keeps_derivative` (Mish): act'(a) of every hidden layer as well, since h alone does not give it
+DAD_HD inline size_t guide_lds_floats(int in_dim, const int* widths, int n_layers, bool keeps_derivative) {
+    size_t cols = (size_t)guide_pad(in_dim);
+    for (int i = 0; i + 1 < n_layers; ++i) cols += (size_t)guide_pad(widths[i]) * (keeps_derivative ? 2 : 1);
+    return cols * GM_AS;
+}
+
 }  // namespace dad

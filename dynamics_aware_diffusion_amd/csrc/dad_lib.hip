@@ -32,6 +32,7 @@
 #include "train_bwd.hpp"
 #include "train_objective.hpp"
 #include "optim_step.hpp"
+#include "guide_mlp.hpp"
 
 using namespace dadhost;
 
@@ -54,6 +55,9 @@ struct GraphKey {
     const void* x; const void* noise; const void* cond; const void* ws;
     const void* P; const void* obs_mean; const void* obs_std; const void* act_mean; const void* act_std;
     const void* proj_scratch;
+    const void* guide_ptrs[3 * DAD_GUIDE_MAX_LAYERS + 1];    // the guide's weight images, biases and gradient scratch
+    int guide_shape[2 * DAD_GUIDE_MAX_LAYERS + 3];           //   its layers, widths and activation
+    float guide_weight;
     int n_steps, batch, cond_per_row, state_dim, observation_dim, action_dim;
     int force_tile, flags;    // tile / split-K / fusion hooks change the captured launches
     uint64_t row_offset;
@@ -277,7 +281,10 @@ int configure_kernels() {
     std::vector<const void*> fns = {(const void*)dad::final_posterior_kernel, (const void*)dad::final_cc_kernel,
                                     (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>,
                                     (const void*)dad::violation_bwd_row_kernel, (const void*)dad::violation_fwd_gemm_kernel,
-                                    (const void*)dad::violation_bwd_gemm_kernel};
+                                    (const void*)dad::violation_bwd_gemm_kernel,
+                                    (const void*)dad::guide_mlp_kernel<dad::GUIDE_TANH>,
+                                    (const void*)dad::guide_mlp_kernel<dad::GUIDE_RELU>,
+                                    (const void*)dad::guide_mlp_kernel<dad::GUIDE_MISH>};
     for (const KernelEntry& e : kernel_table()) fns.push_back(e.fn);      // every family
     for (const void* fn : fns)
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
@@ -598,10 +605,61 @@ int launch_seam(dad_model* m, const FwdPlan& f, const SeamCall& sc, int t_conv, 
     return DAD_OK;
 }
 
+// A library guide (guide_mlp.hpp) on trajectories of one shape: what dad_guide_grad and dad_guided_loop check before
+// anything is launched, and the launch itself.
+static_assert(dad::GUIDE_TANH == DAD_GD_TANH && dad::GUIDE_RELU == DAD_GD_RELU && dad::GUIDE_MISH == DAD_GD_MISH, "DAD_GD_ACTS");
+static_assert(dad::GM_MAX_LAYERS == DAD_GUIDE_MAX_LAYERS, "dad_guide_args");
+struct GuideCall {
+    dad::GuideParams p;
+    int activation;
+    GuidePlan plan;
+};
+int guide_call_checked(const dad_guide_args* g, const float* x, float* grad, float* value_rows, int batch, int horizon,
+                       int td, GuideCall& c) {
+    if (!g) return fail(DAD_E_INVALID, "guide: arguments missing");
+    if (!x || !grad) return fail(DAD_E_INVALID, "guide: null pointer");
+    int rc = guide_shape_checked(batch, horizon, td);
+    if (rc != DAD_OK) return rc;
+    const int L = g->n_layers;
+    c.plan = plan_guide(g->in_dim, L >= 0 && L <= DAD_GUIDE_MAX_LAYERS ? g->widths : nullptr, L, g->activation, batch, horizon, td);
+    if (c.plan.refused != DAD_GD_OK)
+        return fail(DAD_E_INVALID, "guide refused (%d layers, in_dim=%d, transition_dim=%d, activation=%d): %s", L, g->in_dim,
+                    td, g->activation, guide_refusal(c.plan.refused));
+    for (int i = 0; i < L; ++i)
+        if (g->padded[i] != c.plan.padded[i])
+            return fail(DAD_E_INVALID, "guide: padded[%d]=%d, the plan pads it to %d (dad_debug_guide_plan)", i, g->padded[i],
+                        c.plan.padded[i]);
+    for (int i = 0; i < L; ++i)
+        if (!g->w_fwd[i] || !g->bias[i] || (i + 1 < L && !g->w_bwd[i]))
+            return fail(DAD_E_INVALID, "guide: layer %d has a null weight image or bias", i);
+    dad::GuideParams& p = c.p;
+    p = dad::GuideParams{};
+    p.x = x; p.grad = grad; p.value_rows = value_rows;
+    for (int i = 0; i + 1 < L; ++i) { p.wf[i] = g->w_fwd[i]; p.wb[i] = g->w_bwd[i]; p.bias[i] = g->bias[i]; }
+    p.w_last = g->w_fwd[L - 1]; p.b_last = g->bias[L - 1];
+    p.rows = batch * horizon; p.td = td; p.in_dim = g->in_dim; p.hidden = L - 1;
+    for (int i = 0; i < L; ++i) p.pad[i] = c.plan.padded[i];
+    c.activation = g->activation;
+    return DAD_OK;
+}
+int launch_guide(const GuideCall& c, hipStream_t st) {
+    const dim3 grid(c.plan.gx), block(c.plan.threads);
+    switch (c.activation) {
+        case DAD_GD_TANH: hipLaunchKernelGGL(dad::guide_mlp_kernel<dad::GUIDE_TANH>, grid, block, c.plan.lds_bytes, st, c.p); break;
+        case DAD_GD_RELU: hipLaunchKernelGGL(dad::guide_mlp_kernel<dad::GUIDE_RELU>, grid, block, c.plan.lds_bytes, st, c.p); break;
+        default: hipLaunchKernelGGL(dad::guide_mlp_kernel<dad::GUIDE_MISH>, grid, block, c.plan.lds_bytes, st, c.p); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
 // One denoiser evaluation up to final_conv[0]: the launches of `f`, nothing else.  `seam`: the first of them goes out
 // as the seam launch, which also carries the previous step's posterior update (counted as that first launch)
+// `guide`: the launch of a library guide on x goes out after the evaluation's first launch — after the seam launch where
+// there is one: it reads the previous step's gradient and writes the x this step's guide is taken at.
 int run_unet(dad_model* m, const FwdPlan& f, const float* x, int t, float* ws, hipStream_t st,
-             const int32_t* trow = nullptr, const float* temb_rows = nullptr, const SeamCall* seam = nullptr) {
+             const int32_t* trow = nullptr, const float* temb_rows = nullptr, const SeamCall* seam = nullptr,
+             const GuideCall* guide = nullptr) {
     // Profiling brackets the whole run of conv-GEMM launches of one denoiser evaluation with
     // ONE pair of HIP events on the launch stream (events between individual launches would
     // break the back-to-back dispatch they are meant to time).
@@ -618,15 +676,24 @@ int run_unet(dad_model* m, const FwdPlan& f, const float* x, int t, float* ws, h
         ++m->ev_used;
         HIP_TRY(hipEventRecord(e0, st));
     }
+    bool guide_due = guide != nullptr;
     for (size_t i = 0; f.cc.ok && i < f.cc.ops.size(); ++i) {        // small batch: consumer-combine kernels
         if (!f.cc.ops[i].launched) continue;
-        const int rc = run_conv_cc(m, f.cc, (int)i, x, ws, f.batch, t, st);
+        int rc = run_conv_cc(m, f.cc, (int)i, x, ws, f.batch, t, st);
         if (rc != DAD_OK) return rc;
+        if (guide_due && seam == nullptr) {
+            guide_due = false;
+            if ((rc = launch_guide(*guide, st)) != DAD_OK) return rc;
+        }
     }
     for (const FwdLaunch& l : f.launches) {
-        const int rc = (seam != nullptr && &l == &f.launches[0]) ? launch_seam(m, f, *seam, t, ws, st)
-                                                                 : run_conv(m, f, l, x, ws, t, st, trow, temb_rows);
+        const bool seam_launch = seam != nullptr && &l == &f.launches[0];
+        int rc = seam_launch ? launch_seam(m, f, *seam, t, ws, st) : run_conv(m, f, l, x, ws, t, st, trow, temb_rows);
         if (rc != DAD_OK) return rc;
+        if (guide_due && (seam == nullptr || seam_launch)) {
+            guide_due = false;
+            if ((rc = launch_guide(*guide, st)) != DAD_OK) return rc;
+        }
     }
     if (m->profile) {                 // (a riding 1x1 residual conv counts its flops, not a launch)
         for (const ConvOp& op : m->plan.convs) m->prof_flops += op.flops_per_sample * f.batch;
@@ -804,10 +871,22 @@ int sampler_step(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coe
 int sampler_loop(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coef* steps, int n_steps, int batch,
                  const float* noise_stack, uint64_t seed, uint64_t row_offset, const float* cond0, int cond_per_row,
                  const dad_project_args* proj, const float* proj_alphas, int use_graph, void* workspace,
-                 dad_stream_t stream) {
+                 dad_stream_t stream, const dad_guide_args* guide = nullptr, float guide_weight = 0.0f) {
     int rc;
     if (!x || !workspace) return fail(DAD_E_INVALID, "null pointer");
     if (proj && !proj_alphas) return fail(DAD_E_INVALID, "projection needs per-step alphas");
+    // a library guide: its launch per iteration writes guide->grad, which the step's tail (or the seam that carries it) reads
+    const bool guided = guide != nullptr && guide_weight > 0.0f;
+    GuideCall gc;
+    if (guided) {
+        const long need = (long)batch * traj_horizon(*m) * m->cfg.transition_dim * (long)sizeof(float);
+        if (!guide->grad || (long)std::min<size_t>(guide->grad_bytes, (size_t)INT64_MAX) < need)
+            return fail(DAD_E_INVALID, "guide: dad_guide_args.grad must hold batch * H * td = %ld bytes (got %zu)", need,
+                        guide->grad ? guide->grad_bytes : (size_t)0);
+        if ((rc = guide_call_checked(guide, x, guide->grad, nullptr, batch, traj_horizon(*m), m->cfg.transition_dim, gc)) != DAD_OK)
+            return rc;
+        if ((rc = configure_kernels()) != DAD_OK) return rc;
+    }
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_tables(m, st)) != DAD_OK) return rc;      // (before any capture: the replayed loop reads the tables)
     const long step_elems = (long)batch * traj_horizon(*m) * m->cfg.transition_dim;
@@ -826,8 +905,10 @@ int sampler_loop(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coe
             a.noise = noise_stack ? noise_stack + (long)j * step_elems : nullptr;
             a.seed = seed; a.row_offset = row_offset; a.draw = (uint64_t)(j + 1);
             a.cond0 = cond0; a.cond_per_row = cond_per_row;
+            if (guided) { a.guide_grad = guide->grad; a.guide_weight = guide_weight; }
             const SeamCall sc{&seam, x, j > 0 ? &steps[j - 1] : nullptr, &prev, seed_dev};
-            int r = run_unet(m, f, x, t, (float*)workspace, st, nullptr, nullptr, seamed && j > 0 ? &sc : nullptr);
+            int r = run_unet(m, f, x, t, (float*)workspace, st, nullptr, nullptr, seamed && j > 0 ? &sc : nullptr,
+                             guided ? &gc : nullptr);
             if (r != DAD_OK) return r;
             prev = a;
             if (seamed && j + 1 < n_steps) continue;
@@ -856,6 +937,16 @@ int sampler_loop(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coe
         key.proj_scratch = proj->scratch;
         key.state_dim = proj->state_dim; key.observation_dim = proj->observation_dim;
         key.action_dim = proj->action_dim;
+    }
+    if (guided) {
+        for (int i = 0; i < guide->n_layers; ++i) {
+            key.guide_ptrs[3 * i] = guide->w_fwd[i]; key.guide_ptrs[3 * i + 1] = guide->w_bwd[i];
+            key.guide_ptrs[3 * i + 2] = guide->bias[i];
+            key.guide_shape[3 + i] = guide->widths[i]; key.guide_shape[3 + DAD_GUIDE_MAX_LAYERS + i] = guide->padded[i];
+        }
+        key.guide_ptrs[3 * DAD_GUIDE_MAX_LAYERS] = guide->grad;
+        key.guide_shape[0] = guide->n_layers; key.guide_shape[1] = guide->in_dim; key.guide_shape[2] = guide->activation;
+        key.guide_weight = guide_weight;
     }
     key.n_steps = n_steps; key.batch = batch; key.cond_per_row = cond_per_row;
     key.force_tile = m->force_tile;
@@ -1234,6 +1325,37 @@ int dad_sampler_loop(dad_model* m, float* x, const dad_sampler_coef* steps, int3
     if ((rc = check_ready(m, batch, steps[0].t, workspace_bytes, true, f)) != DAD_OK) return rc;
     return sampler_loop(m, f, x, steps, n_steps, batch, noise_stack, seed, row_offset, cond0, cond_per_row, proj,
                         proj_alphas_host, use_graph, workspace, stream);
+}
+
+int dad_guide_grad(const dad_guide_args* guide, const float* x, float* grad_out, float* value_rows_out, int32_t batch,
+                   int32_t horizon, int32_t transition_dim, dad_stream_t stream) {
+    GuideCall gc;
+    int rc = guide_call_checked(guide, x, grad_out, value_rows_out, batch, horizon, transition_dim, gc);
+    if (rc != DAD_OK || (rc = configure_kernels()) != DAD_OK) return rc;
+    return launch_guide(gc, (hipStream_t)stream);
+}
+
+int dad_guided_loop(dad_model* m, float* x, const dad_sampler_coef* steps, int32_t n_steps, int32_t batch,
+                    const float* noise_stack, uint64_t seed, uint64_t row_offset,
+                    const float* cond0, int32_t cond_per_row, const dad_guide_args* guide, float guide_weight,
+                    const dad_project_args* proj, const float* proj_alphas_host, int32_t use_graph, void* workspace,
+                    size_t workspace_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (n_steps < 1) return fail(DAD_E_INVALID, "n_steps must be positive");
+    std::vector<dad_sampler_coef> ancestral;
+    int rc;
+    if (steps != nullptr) {
+        if ((rc = check_sampler_steps(steps, n_steps, m->cfg.n_timesteps)) != DAD_OK) return rc;
+    }
+    FwdPlan f;
+    if ((rc = check_ready(m, batch, steps ? steps[0].t : n_steps - 1, workspace_bytes, true, f)) != DAD_OK) return rc;
+    if (steps == nullptr) {                 // the ancestral sampler over the first n_steps entries of the loaded schedule
+        ancestral.resize((size_t)n_steps);
+        for (int j = 0; j < n_steps; ++j) ancestral[j] = schedule_step(m, n_steps - 1 - j);
+        steps = ancestral.data();
+    }
+    return sampler_loop(m, f, x, steps, n_steps, batch, noise_stack, seed, row_offset, cond0, cond_per_row, proj,
+                        proj_alphas_host, use_graph, workspace, stream, guide, guide_weight);
 }
 
 // ---------------------------------------------------------------------------------- training
@@ -2008,6 +2130,12 @@ int dad_debug_violation_grad_plan(int32_t state_dim, int32_t observation_dim, in
 int dad_debug_seam_plan(dad_model* m, int32_t batch, int32_t projection, int32_t* out) {
     if (!m || !out || batch <= 0) return fail(DAD_E_INVALID, "bad argument");
     return seam_plan_report(*m, batch, projection != 0, out);
+}
+
+int dad_debug_guide_plan(int32_t in_dim, const int32_t* widths, int32_t n_layers, int32_t activation, int32_t batch,
+                         int32_t horizon, int32_t transition_dim, int32_t* out) {
+    if (!out || (!widths && n_layers > 0)) return fail(DAD_E_INVALID, "guide: null pointer");
+    return guide_plan_report(in_dim, widths, n_layers, activation, batch, horizon, transition_dim, out);
 }
 
 const char* dad_debug_seam_reason(int32_t reason) { return seam_reason(reason); }

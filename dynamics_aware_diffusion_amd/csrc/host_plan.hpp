@@ -1771,6 +1771,56 @@ inline ViolationGradPlan plan_violation_grad(int D, int batch, long row_elems, i
     return q;
 }
 
+// ------------------------------------------------------------------ library guide: which nets, on which grid
+// One launch of guide_mlp_kernel (guide_mlp.hpp): dad_guide_grad and every guide launch of dad_guided_loop launch
+// from this, dad_debug_guide_plan reports it.  The net is in_dim -> widths[0] -> ... -> widths[n_layers - 1]; the
+// limits are the GM_* constants of conv_shapes.hpp and a CU's LDS, in the order of DAD_GD_REFUSALS.
+struct GuidePlan {
+    int n_layers = 0;
+    int padded[dad::GM_MAX_LAYERS] = {0, 0, 0, 0};    // padded[0]: in_dim; padded[i + 1]: hidden widths[i]
+    int rows_per_block = dad::GM_ROWS;
+    int threads = dad::GM_THREADS;
+    unsigned gx = 0;
+    size_t lds_bytes = 0;
+    int refused = DAD_GD_OK;
+};
+inline GuidePlan plan_guide(int in_dim, const int* widths, int n_layers, int activation, int batch, int horizon, int td) {
+    GuidePlan q;
+    q.n_layers = n_layers;
+    q.gx = (unsigned)(((long)batch * horizon + dad::GM_ROWS - 1) / dad::GM_ROWS);
+    q.padded[0] = in_dim > 0 ? dad::guide_pad(in_dim) : 0;
+    const auto no = [&](int why) { q.refused = why; return q; };
+    if (n_layers < dad::GM_MIN_LAYERS || n_layers > dad::GM_MAX_LAYERS || widths == nullptr) return no(DAD_GD_BAD_LAYERS);
+    for (int i = 0; i < n_layers; ++i)
+        if (widths[i] < 1 || widths[i] > dad::GM_MAX_WIDTH) return no(DAD_GD_BAD_WIDTH);
+    for (int i = 0; i + 1 < n_layers; ++i) q.padded[i + 1] = dad::guide_pad(widths[i]);
+    if (activation != DAD_GD_TANH && activation != DAD_GD_RELU && activation != DAD_GD_MISH) return no(DAD_GD_BAD_ACT);
+    if (in_dim < 1 || in_dim > td) return no(DAD_GD_BAD_IN_DIM);
+    if (widths[n_layers - 1] != 1) return no(DAD_GD_BAD_LAST);
+    q.lds_bytes = dad::guide_lds_floats(in_dim, widths, n_layers, activation == DAD_GD_MISH) * sizeof(float);
+    if (q.lds_bytes > dad::kLdsBytes) return no(DAD_GD_BAD_LDS);
+    return q;
+}
+// The checks on the shape every entry point of the guide makes before it plans
+inline int guide_shape_checked(int batch, int horizon, int td) {
+    if (batch <= 0 || horizon <= 0 || td <= 0)
+        return fail(DAD_E_INVALID, "guide: batch=%d, horizon=%d, transition_dim=%d must be positive", batch, horizon, td);
+    if ((long)batch * horizon * td > (long)INT32_MAX)
+        return fail(DAD_E_INVALID, "guide: batch=%d x horizon=%d x transition_dim=%d exceeds 2^31 elements", batch, horizon, td);
+    return DAD_OK;
+}
+inline const char* guide_refusal(int why) {
+    switch (why) {
+        case DAD_GD_BAD_LAYERS: return "the net must have 2 to 4 Linear layers";
+        case DAD_GD_BAD_WIDTH: return "every width must lie in 1 .. 512";
+        case DAD_GD_BAD_ACT: return "unknown activation (DAD_GD_TANH, DAD_GD_RELU, DAD_GD_MISH)";
+        case DAD_GD_BAD_IN_DIM: return "in_dim must lie in 1 .. transition_dim";
+        case DAD_GD_BAD_LAST: return "the last layer must have one output";
+        case DAD_GD_BAD_LDS: return "the kept tensors of 32 rows exceed one CU's LDS";
+    }
+    return "";
+}
+
 // ------------------------------------------------------------------ backward pass: per-batch geometry
 // Which conv_wgrad instantiations exist, by (taps, block tile, windowed: layers longer than a chunk stages): these tap
 // counts, each on tile 0 = 64 x 64 (two K-groups), 1 = 64 x 32 (four), 2 = 32 x 32 (eight) and 3 = 32 x 32 with the

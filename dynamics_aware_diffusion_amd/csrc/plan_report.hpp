@@ -27,6 +27,7 @@ constexpr const char* kReportLayouts[][kMaxReportSections] = {
     {S(DAD_OS_HEADER), S(DAD_OS_REC_INTS)},
     {S(DAD_KL_HEADER), S(DAD_FAMILIES)},
     {S(DAD_VG_INTS), S(DAD_VG_FORMS)},
+    {S(DAD_GD_INTS), S(DAD_GD_ACTS), S(DAD_GD_REFUSALS)},
 };
 #undef K
 #undef S
@@ -334,6 +335,23 @@ inline int violation_grad_plan_report(int state_dim, int observation_dim, int ac
     out[DAD_VG_BWD_LDS_BYTES] = i32(q.bwd.lds_bytes); out[DAD_VG_BWD_SCATTER_GX] = (int32_t)q.bwd.tail_gx;
     out[DAD_VG_WORKSPACE_BYTES] = i32(q.workspace_bytes);
     out[DAD_VG_REFUSED] = q.refused;
+    return DAD_OK;
+}
+
+// dad_debug_guide_plan: plan_guide for this net on trajectories of this shape; out[DAD_GD_INTS].
+inline int guide_plan_report(int in_dim, const int32_t* widths, int n_layers, int activation, int batch, int horizon, int td,
+                             int32_t* out) {
+    const int rc = guide_shape_checked(batch, horizon, td);
+    if (rc != DAD_OK) return rc;
+    const GuidePlan q = plan_guide(in_dim, widths, n_layers, activation, batch, horizon, td);
+    out[DAD_GD_LAYERS] = n_layers;
+    out[DAD_GD_PADDED_IN] = q.padded[0]; out[DAD_GD_PADDED_1] = q.padded[1];
+    out[DAD_GD_PADDED_2] = q.padded[2]; out[DAD_GD_PADDED_3] = q.padded[3];
+    out[DAD_GD_ROWS_PER_BLOCK] = q.rows_per_block;
+    out[DAD_GD_THREADS] = q.threads;
+    out[DAD_GD_GX] = (int32_t)q.gx;
+    out[DAD_GD_LDS_BYTES] = (int32_t)std::min<size_t>(q.lds_bytes, INT32_MAX);
+    out[DAD_GD_REFUSED] = q.refused;
     return DAD_OK;
 }
 

@@ -21,12 +21,18 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .._engine import ProjectionState
+from .._engine import GuideState, ProjectionState
 from ..models.temporal_unet import TemporalUnet
 
 
 class GuidedPolicy(nn.Module):
-    """Conditioned (inpainting) sampler with optional guide and an action FIFO."""
+    """Conditioned (inpainting) sampler with optional guide and an action FIFO.
+
+    ``fused_guide = True`` (opt-in, an attribute like ``GaussianDiffusion.fused_objective``) lets ``sample_loop`` and
+    what is built on it evaluate a value guide inside the fused engine loop where ``guide_route`` says "library";
+    False changes nothing."""
+
+    fused_guide = False
 
     def __init__(self, diffusion_model, normalizer, guide_fn: Optional[Callable] = None,
                  guide_weight: float = 1.0, action_horizon: Optional[int] = None):
@@ -58,6 +64,31 @@ class GuidedPolicy(nn.Module):
             score = self.guide_fn(probe, t)
             (grad,) = torch.autograd.grad(score.sum(), probe)
         return grad.detach().contiguous()
+
+    def _library_guide(self):
+        """(GuideState, None) where the library can evaluate this policy's guide itself, else (None, why not)."""
+        return None, "only ValueGuidedPolicy's guide has a library form"
+
+    def guide_route(self, conditions: Optional[Dict[int, torch.Tensor]] = None, batch_size: int = 1):
+        """Which route a ``sample_loop(batch_size, conditions)`` call would take for the guide, and why:
+        ``("unguided", why)``, ``("autograd", why)`` — one engine step per iteration around torch autograd through the
+        guide — or ``("library", why)`` — the guide evaluated inside the one fused engine loop (dad_guided_loop)."""
+        return self._guide_route(conditions, batch_size)[:2]
+
+    def _guide_route(self, conditions, batch_size):
+        if not self._guided():
+            return "unguided", "no guide, or guide_weight <= 0", None
+        if not self.fused_guide:
+            return "autograd", "fused_guide is off", None
+        state, why = self._library_guide()
+        if state is None:
+            return "autograd", why, None
+        plan = state.plan(batch_size, self.horizon, self.transition_dim)
+        if plan["refused"] is not None:
+            return "autograd", f"the planner refuses the net at this shape: {plan['refused']}", None
+        if conditions and any(k != 0 for k in conditions):
+            return "autograd", "a condition beyond horizon step 0 is written between the steps", None
+        return "library", "the value model compiles and nothing is conditioned beyond horizon step 0", state
 
     @staticmethod
     def _split_conditions(conditions):
@@ -110,10 +141,13 @@ class GuidedPolicy(nn.Module):
         if conditions is not None:
             conditions = {k: v.to(device, torch.float32) for k, v in conditions.items()}
         cond0, rest = self._split_conditions(conditions)
+        extra = {}
+        if self.fused_guide:                       # (opt-in: without it the call below is what it always was)
+            extra["library_guide"] = self._guide_route(conditions, batch_size)[2]
         return diff._reverse_loop(eng, (batch_size, self.horizon, self.transition_dim), row_offset, cond0, rest,
                                   guide=self._guide_gradient if self._guided() else None,
                                   guide_weight=self.guide_weight, projector=self._loop_projector(),
-                                  alpha_of=lambda t: self._get_projection_alpha(t))
+                                  alpha_of=lambda t: self._get_projection_alpha(t), **extra)
 
     def _loop_projector(self) -> Optional[ProjectionState]:
         return None
@@ -212,6 +246,18 @@ class ValueGuidedPolicy(GuidedPolicy):
 
         super().__init__(diffusion_model, normalizer, guide_fn, guide_weight, action_horizon)
         self.value_model = value_model
+
+    def _library_guide(self):
+        """The value model as a ``GuideState`` on the diffusion model's device, compiled once per (module, device);
+        the state itself follows the parameters' values."""
+        device = self.diffusion.betas.device
+        key = (id(self.value_model), str(device))
+        cached = self.__dict__.get("_guide_state")
+        if cached is None or cached[0] != key:
+            cached = (key,) + tuple(GuideState.compile(self.value_model, self.observation_dim, device,
+                                                       host=device.type != "cuda"))
+            self.__dict__["_guide_state"] = cached
+        return cached[1], cached[2]
 
 
 class DynamicsAwarePolicy(GuidedPolicy):

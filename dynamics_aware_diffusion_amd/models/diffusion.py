@@ -368,7 +368,7 @@ class GaussianDiffusion(nn.Module):
 
     def _reverse_loop(self, eng, shape: tuple, row_offset: int, cond0: Optional[torch.Tensor] = None,
                       rest: Optional[Dict[int, torch.Tensor]] = None, guide=None, guide_weight: float = 0.0,
-                      projector=None, alpha_of=None) -> torch.Tensor:
+                      projector=None, alpha_of=None, library_guide=None) -> torch.Tensor:
         """Every sampling loop: x_T ~ N(0, I), the conditions, then the reverse steps of ``_loop_steps`` by the one
         route the settings allow.  ``p_sample_loop`` is this with nothing but a shape; the policies' ``sample_loop``
         adds the rest.
@@ -378,7 +378,9 @@ class GaussianDiffusion(nn.Module):
         ``guide(x, t_tensor) -> grad`` with its ``guide_weight``: the guide's gradient at x_t, fused into the step
         (the ancestral step scales it by the variance; the strided one takes classifier guidance in its DDIM form,
         eps' = eps - w sqrt(1 - abar) g, as the shift of x0 it causes).  ``projector.apply(x, alpha_of(t))`` follows
-        the step at timestep t.
+        the step at timestep t.  ``library_guide``: the same guide as a ``GuideState`` the library evaluates inside
+        the fused loop (dad_guided_loop); with it a guided loop without ``rest`` is one engine call, and ``guide`` is
+        not called.
 
         Philox: x_T is draw 0 and iteration j's z is draw j + 1 of (``seed``, ``row_offset`` + row).  torch: x_T is
         the first ``randn`` and iteration j's z the next one after it, in the reference's call order
@@ -387,9 +389,12 @@ class GaussianDiffusion(nn.Module):
         steps = self._loop_steps()
         n, rest = len(steps.timesteps), rest or {}
         philox = self.sampler_rng == "philox"
-        # the fused engine loop knows no guide and no condition beyond horizon step 0.  Only it replays a graph, which
-        # needs persistent (address-stable) buffers and hands the result out as a copy: decided before any allocation
-        fused = guide is None and not rest
+        # the fused engine loop knows no guide but a library guide and no condition beyond horizon step 0.  Only it
+        # replays a graph, which needs persistent (address-stable) buffers and hands the result out as a copy: decided
+        # before any allocation
+        if guide is None or not guide_weight > 0:
+            library_guide = None
+        fused = (guide is None or library_guide is not None) and not rest
         graph = bool(self.use_graph) and fused
         if philox:
             x = eng.persistent("x", shape) if graph else torch.empty(shape, device=device, dtype=torch.float32)
@@ -409,13 +414,18 @@ class GaussianDiffusion(nn.Module):
 
         if fused:
             kw = dict(cond0=cond0, projection=projector, use_graph=graph)
+            if library_guide is not None:          # (extra keywords only here: an engine without the guide never sees them)
+                kw.update(guide=library_guide, guide_weight=float(guide_weight))
             if philox:
                 steps.loop(eng, x, alphas, seed=self.seed, row_offset=row_offset, **kw)
             elif steps.takes_noise and self.noise_stack_bytes(shape, n) > self.max_noise_stack_bytes:
                 # the whole z stack would not be O(1) in T (1.1 GB for Door at B=128, T=1000): draw z step by step
                 # instead: the same torch.randn calls in the same order, one engine step per iteration
                 for j in range(n):
-                    steps.step(eng, x, j, noise=torch.randn(shape, device=device), cond0=cond0)
+                    gkw = {}
+                    if library_guide is not None:
+                        gkw = dict(guide_grad=library_guide.grad(x), guide_weight=float(guide_weight))
+                    steps.step(eng, x, j, noise=torch.randn(shape, device=device), cond0=cond0, **gkw)
                     if projector is not None:
                         projector.apply(x, alphas[j])
             else:

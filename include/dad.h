@@ -370,6 +370,59 @@ int dad_projection_violation_bwd(const dad_project_args* p, const float* d_viola
                                  size_t workspace_bytes, int32_t batch, int32_t horizon, int32_t form,
                                  dad_stream_t stream);
 
+/* A value guide the library evaluates itself.  Replaces: ValueGuidedPolicy's guide, sum over the horizon of
+ * value_model(observations) (guides/policies.py:243-271), and its gradient at x_t as p_sample_with_guidance takes it
+ * (guides/policies.py:87-97), for value models that are a small MLP applied to each horizon step's observation:
+ *   h_0 = x[b, l, :in_dim],  a_i = W_i h_{i-1} + b_i,  h_i = act(a_i),  V = w_L . h_{L-1} + b_L        (per row (b, l))
+ *   d V / d x[b, l, :in_dim] = W_1^T (act'(a_1) * W_2^T ( ... (act'(a_{L-1}) * w_L))),  0 on the channels from in_dim on.
+ * A plain struct, no library-side state.  n_layers Linear layers (2 .. 4, the last with one output), one activation
+ * (DAD_GD_ACTS) between them; widths[i] is the output width of layer i, padded[0] the zero-padded in_dim and
+ * padded[i + 1] the zero-padded widths[i] of a hidden layer, exactly as dad_debug_guide_plan reports them.  Layer i
+ * (0-based) of a hidden layer travels as two zero-padded device images, so that both passes read their MFMA B operand
+ * contiguously: w_fwd[i] = W^T as [padded[i]][padded[i + 1]], w_bwd[i] = W as [padded[i + 1]][padded[i]]; bias[i] is
+ * [padded[i + 1]] (a missing bias: zeros).  The last layer: w_fwd[L - 1] = its weight row as [padded[L - 1]],
+ * w_bwd[L - 1] unused, bias[L - 1] one float.  grad: caller-owned scratch of batch * H * td floats, the gradient
+ * dad_guided_loop hands from its guide launch to the step's tail. */
+#define DAD_GUIDE_MAX_LAYERS 4
+typedef struct dad_guide_args {
+    int32_t n_layers, in_dim;
+    int32_t widths[DAD_GUIDE_MAX_LAYERS];
+    int32_t padded[DAD_GUIDE_MAX_LAYERS];
+    int32_t activation;
+    const float* w_fwd[DAD_GUIDE_MAX_LAYERS];
+    const float* w_bwd[DAD_GUIDE_MAX_LAYERS];
+    const float* bias[DAD_GUIDE_MAX_LAYERS];
+    float* grad;
+    size_t grad_bytes;
+} dad_guide_args;
+
+/* The stand-alone gradient of that guide (guides/policies.py:243-271 differentiated as :87-97 does): grad_out
+ * (B, H, td) fully overwritten, value_rows_out (B * H) the per-row V, or NULL.  x: (B, H, td) device fp32, read only.
+ * One launch of guide_mlp_kernel (csrc/guide_mlp.hpp) on `stream`: asynchronous, allocates nothing, no atomics (the
+ * same inputs give the same bits).  dad_guide_args.grad is not used.  Refusals come before any launch, each with a
+ * message: DAD_E_INVALID for a null pointer, batch, horizon or transition_dim <= 0, a net plan_guide refuses
+ * (DAD_GD_REFUSALS) or `padded` other than the plan's. */
+int dad_guide_grad(const dad_guide_args* guide, const float* x, float* grad_out, float* value_rows_out, int32_t batch,
+                   int32_t horizon, int32_t transition_dim, dad_stream_t stream);
+
+/* dad_sampler_loop with that guide inside it.  Replaces: GuidedPolicy.sample_loop with a value guide
+ * (guides/policies.py:114-149 with :243-271 as the guide and :87-97 as the step), as one library call.  steps == NULL
+ * runs the ancestral steps t = n_steps-1 .. 0 of the loaded schedule (dad_sample_loop's); proj_alphas_host[n_steps] is
+ * in EXECUTION order either way.  Per iteration the guide launch goes out after the evaluation's first launch — on
+ * a seamed loop the seam, which reads the previous step's gradient and writes the x this one is taken at — and before
+ * the step's tail, which gets guide->grad and guide_weight (dad_step_args).  Everything stays on the one stream.
+ * guide == NULL or guide_weight <= 0 is the unguided loop, launch for launch.  use_graph: the guide's pointers, shape,
+ * activation and guide_weight are part of the graph's key; its weights are read at replay, so values changed in place
+ * are followed.  Refusals as dad_sampler_loop and dad_guide_grad, and DAD_E_INVALID for a guide whose `grad` is null
+ * or holds fewer than batch * H * td floats; all before any launch. */
+int dad_guided_loop(dad_model* m, float* x, const dad_sampler_coef* steps, int32_t n_steps, int32_t batch,
+                    const float* noise_stack, uint64_t seed, uint64_t row_offset,
+                    const float* cond0, int32_t cond_per_row,
+                    const dad_guide_args* guide, float guide_weight,
+                    const dad_project_args* proj, const float* proj_alphas_host,
+                    int32_t use_graph, void* workspace, size_t workspace_bytes,
+                    dad_stream_t stream);
+
 /* Replaces: torch.randn(shape) for x_T (diffusion.py:241; policies.py:134) with the
  * library's counter-based generator: element e of global row r gets Philox4x32-10
  * (key = seed, counter = (draw, r*H*td + e)) -> Box-Muller.  Result is independent of how
@@ -735,6 +788,41 @@ DAD_LAYOUT(DAD_VG_INTS, 0);
 DAD_LAYOUT(DAD_VG_FORMS, 0);
 int dad_debug_violation_grad_plan(int32_t state_dim, int32_t observation_dim, int32_t action_dim, int32_t batch,
                                   int32_t horizon, int32_t form, int32_t* out);
+/* What one dad_guide_grad call (and every guide launch of dad_guided_loop) launches for a value net of `n_layers`
+ * Linear layers in_dim -> widths[0] -> ... -> widths[n_layers - 1] with `activation` (DAD_GD_ACTS) between them, on
+ * trajectories (batch, horizon, transition_dim): plan_guide of csrc/host_plan.hpp, the one statement of the limits
+ * on the value models (guides/policies.py:243-271) whose gradient (guides/policies.py:87-97) the library takes itself.
+ * Host logic only, no device call.  out[DAD_GD_INTS].  DAD_E_INVALID for a null pointer or batch, horizon or
+ * transition_dim <= 0 (or more than 2^31 elements); a net the library does not evaluate is reported
+ * (DAD_GD_REFUSED), not refused here. */
+#define DAD_GD_INTS_LIST(F) \
+    F(DAD_GD_LAYERS, layers, 1, "Linear layers, as given") \
+    F(DAD_GD_PADDED_IN, padded_in, 1, "in_dim zero-padded to whole 32-column MFMA tiles: dad_guide_args.padded[0]") \
+    F(DAD_GD_PADDED_1, padded_1, 1, "widths[0] padded likewise (padded[1]); 0 where refused before the widths were read") \
+    F(DAD_GD_PADDED_2, padded_2, 1, "widths[1] padded, 0 unless it is a hidden layer") \
+    F(DAD_GD_PADDED_3, padded_3, 1, "widths[2] padded, 0 unless it is a hidden layer") \
+    F(DAD_GD_ROWS_PER_BLOCK, rows_per_block, 1, "rows of batch * horizon one block owns: 32") \
+    F(DAD_GD_THREADS, threads, 1, "threads of a block") \
+    F(DAD_GD_GX, gx, 1, "grid x: blocks over the rows, each row in exactly one") \
+    F(DAD_GD_LDS_BYTES, lds_bytes, 1, "dynamic LDS of one block: 33 floats per kept column (the padded input, every padded hidden width, twice under Mish)") \
+    F(DAD_GD_REFUSED, refused, 1, "DAD_GD_REFUSALS: 0, or the first limit the net misses (the calls then fail with DAD_E_INVALID)")
+DAD_LAYOUT(DAD_GD_INTS, 0);
+#define DAD_GD_ACTS_LIST(F) \
+    F(DAD_GD_TANH, tanh, 1, "nn.Tanh") \
+    F(DAD_GD_RELU, relu, 1, "nn.ReLU (derivative 0 at 0, as torch)") \
+    F(DAD_GD_MISH, mish, 1, "nn.Mish, through the conv epilogue's device function")
+DAD_LAYOUT(DAD_GD_ACTS, 0);
+#define DAD_GD_REFUSALS_LIST(F) \
+    F(DAD_GD_OK, ok, 1, "the net is evaluated") \
+    F(DAD_GD_BAD_LAYERS, layers, 1, "fewer than 2 or more than 4 Linear layers") \
+    F(DAD_GD_BAD_WIDTH, width, 1, "a width below 1 or above 512") \
+    F(DAD_GD_BAD_ACT, activation, 1, "an activation that is none of DAD_GD_ACTS") \
+    F(DAD_GD_BAD_IN_DIM, in_dim, 1, "in_dim below 1 or above transition_dim") \
+    F(DAD_GD_BAD_LAST, last_width, 1, "the last layer has more than one output") \
+    F(DAD_GD_BAD_LDS, lds, 1, "the kept tensors of 32 rows exceed one CU's LDS")
+DAD_LAYOUT(DAD_GD_REFUSALS, 0);
+int dad_debug_guide_plan(int32_t in_dim, const int32_t* widths, int32_t n_layers, int32_t activation, int32_t batch,
+                         int32_t horizon, int32_t transition_dim, int32_t* out);
 /* Whether dad_sample_loop at `batch` (projection != 0: called with a projection argument) takes the seam between two
  * denoise steps as one launch (csrc/conv_seam.hpp; the rule: plan_seam in csrc/host_plan.hpp), under the model's current
  * options.  Host logic only, no device call; the model needs no weights.  out[DAD_SEAM_INTS]. */
