@@ -1167,15 +1167,17 @@ class HipEngine:
         small-batch plan is taken), ``final`` (grid x, grid y, kernel name or None) and ``launches``: one dict per
         launch with the fields of DAD_FP_REC_* (``flags``: the flag word of kernel_registered_f) or, with ``small``,
         of DAD_FP_CC_*; each has ``key``, the instantiation it runs: ("gemm", cfg, taps, stride, flags),
-        ("halo8", cfg, ride) — conv_halo8_f32 on tile cfg —, ("cc", taps, stride, ride, big, rows, windowed) or
+        ("halo8", cfg, ride) — conv_halo8_f32 on tile cfg, or with ``wreg`` true its register-weight form
+        conv_halo8w_f32 (option "halo8_wreg") —, ("cc", taps, stride, ride, big, rows, windowed) or
         ("ccw", taps, stride, ride, ride_in, rows)."""
         head, launches = decode_report(_fetch(self.lib.dad_debug_forward_plan, self._h, int(batch), int(mode)), "DAD_FP_HEADER",
                                        lambda head, at: "DAD_FP_CC_INTS" if head["small"] else "DAD_FP_REC_INTS")
         assert head["records"] == len(launches)
         small, families = bool(head["small"]), _names("DAD_FP_FAMILIES")
         for q in launches:
-            if not small and families[q["family"]] == "halo8":
+            if not small and families[q["family"]] in ("halo8", "halo8w"):
                 q["key"] = ("halo8", q["cfg"], (q["flags"] >> FP_FLAGS.index("res")) & 1)
+                q["wreg"] = families[q["family"]] == "halo8w"
             elif not small:
                 q["key"] = ("gemm", q["cfg"], q["taps"], q["stride"], q["flags"])
             elif q["wide"]:

@@ -25,6 +25,10 @@
 // (ds_read_b128 fragments — a 16-channel unit — cannot be made conflict-free here: its 16-lane groups mix two kq
 // values, which forces all 16 rows of a block onto even 16-byte slots, and rows KC + 4 floats apart alternate.)
 //
+// Two forms of the same sum: conv_halo8_f32 stages the weights in LDS (32 x 32 wave tiles share a fragment along N);
+// conv_halo8w_f32, below it, gives a wave 16 output channels x all 64 columns and reads its weights straight into the
+// MFMA's registers.  Bit-identical; the planner picks per (tile, ride) (host_plan.hpp choose_halo8, halo8w_faster).
+//
 // Not built: L = 16 (a 64-row tile holds 4 samples: no 16-column block is all halo), L = 4, the
 // split-f16, direct-B, ragged, padded and windowed forms, the training forward, grid split-K.
 #pragma once
@@ -361,6 +365,367 @@ __global__ __launch_bounds__(64 * (BM / 32) * 2 * SK) void conv_halo8_f32(const 
         }
     }
 #undef DAD8_DROP
+#pragma unroll
+    for (int k = 0; k < F4PL; ++k) {
+        y[k][0] += bias4[k].x; y[k][1] += bias4[k].y; y[k][2] += bias4[k].z; y[k][3] += bias4[k].w;
+    }
+
+    if (has_gn) {
+        const float inv_cnt = 1.0f / (float)(cnt4 * 4);
+        const int width = lpp < 64 ? lpp : 64;
+        const int wpp = lpp >> 6;                // waves per pair when a pair spans waves
+        auto pair_sum = [&](float v, int slot) -> float {
+            if (width >= 2) v += dpp_f32<0xB1>(v);
+            if (width >= 4) v += dpp_f32<0x4E>(v);
+            if (width >= 8) v += dpp_f32<0x141>(v);
+            if (width >= 16) v += dpp_f32<0x140>(v);
+            if (width >= 32) v = rows_sum(v, width, lane);
+            if (wpp > 1) {                       // block-uniform branch
+                if (lane == 0) red[slot * 16 + wave] = v;
+                __syncthreads();
+                const int w0 = (wave / wpp) * wpp;
+                v = 0.0f;
+                for (int w = 0; w < wpp; ++w) v += red[slot * 16 + w0 + w];
+            }
+            return v;
+        };
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < F4PL; ++k) sum += (y[k][0] + y[k][1]) + (y[k][2] + y[k][3]);
+        const float mean = pair_sum(sum, 0) * inv_cnt;
+        float sq = 0.0f;
+#pragma unroll
+        for (int k = 0; k < F4PL; ++k)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { const float d = y[k][c] - mean; sq += d * d; }
+        const float rstd = 1.0f / sqrtf(pair_sum(sq, 1) * inv_cnt + 1e-5f);
+#pragma unroll
+        for (int k = 0; k < F4PL; ++k) {
+            y[k][0] = mish_fast_f32((y[k][0] - mean) * rstd * gam4[k].x + bet4[k].x);
+            y[k][1] = mish_fast_f32((y[k][1] - mean) * rstd * gam4[k].y + bet4[k].y);
+            y[k][2] = mish_fast_f32((y[k][2] - mean) * rstd * gam4[k].z + bet4[k].z);
+            y[k][3] = mish_fast_f32((y[k][3] - mean) * rstd * gam4[k].w + bet4[k].w);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < F4PL; ++k) {
+        if (eoff[k] < 0) continue;
+        const float4 t4 = has_temb ? temb4[k] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 r4 = has_res ? res4[k] : make_float4(0.f, 0.f, 0.f, 0.f);
+        store_f4_sc1(p.dst + eoff[k], make_float4(y[k][0] + (t4.x + r4.x), y[k][1] + (t4.y + r4.y),
+                                                  y[k][2] + (t4.z + r4.z), y[k][3] + (t4.w + r4.w)));
+    }
+}
+
+// ---- the register-weight form -------------------------------------------------------------------------------------
+// The same tile, arithmetic and summation order with the block cut into wave tiles the other way: a wave owns one
+// M block of 16 output channels and all four column blocks (BM / 16 M blocks x SK K slices = 8 waves on both tiles).
+// A weight fragment is then used by exactly one wave, so it needs no LDS: each lane reads its float2 (output channel
+// tm * 16 + i16, channels 2kq, 2kq + 1 of an 8-channel unit) from the packed image straight into the register the
+// MFMA takes it from — 16 rows x 32 bytes per load instruction, the other half of every 64-byte row by the wave's
+// other unit or its K-slice neighbour — and every weight byte is still fetched once per block.  The stage holds the
+// X rows alone (halo8w_lds_floats: the exchange tile of the epilogue is now the larger need).
+//
+// Summation order: blocks 0 and 1 walk the taps upwards and blocks 2 and 3 downwards, as wave tiles 0 and 1 of
+// conv_halo8_f32 do, here as a compile-time choice per block: unit (tap index t, group) multiplies blocks 0, 1 with
+// tap t and blocks 2, 3 with tap 4 - t, so both all-halo products — (tap 0, block 0), (tap 4, block 3) — fall on tap
+// index 0 of every wave.  The k-step chains, the K slices and the exchange are the same: every output element adds
+// the same products in the same order, and the result is bit-identical to conv_halo8_f32's.
+//
+// A tap's weights are used at two units of a chunk (t and 4 - t), so a wave holds its whole chunk of fragments
+// (WTAPS x GW float2) and loads the next chunk's into a second set while it multiplies: unconditional loads in the
+// first half of the units, the X row's store and reload after them, one register copy per fragment at the chunk's end
+// (v_mov in the shadow of the last MFMAs) — the oldest outstanding load is always the one waited for.
+template <int BM, int SK, bool RES>
+__global__ __launch_bounds__(64 * (BM / 16) * SK) void conv_halo8w_f32(const ConvParams p) {
+    constexpr int BN = 64, KC = 32, TAPS = 5, PAD = TAPS / 2, L = 8, LSH = 3;
+    constexpr int TMW = BM / 16, NT = 64 * TMW * SK;
+    constexpr int WTAPS = TAPS + (RES ? 1 : 0);
+    constexpr int KP = KC + 4;
+    constexpr int KU = 8;                        // channels per unit: 2 k-steps of v_mfma_f32_16x16x4_f32
+    constexpr int G = KC / KU, GW = G / SK;
+    constexpr int KG = 16, NSUB = KC / KG;
+    constexpr int SPT = BN / L, SEG = L + 2 * PAD, XROWS = SPT * SEG;
+    constexpr int STAGE = XROWS * KP + kXSwzPad; // floats per stage: the X rows
+    constexpr int STAGE4 = STAGE / 4, STAGE2 = STAGE / 2;
+    static_assert(BM % 16 == 0 && G % SK == 0 && GW >= 1 && STAGE % 4 == 0 && NT == 512, "tile shape");
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float4* const smem4 = reinterpret_cast<float4*>(smem);
+    float2* const smem2 = reinterpret_cast<float2*>(smem);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tm = wave % TMW;                   // M block (16 output channels) of this wave
+    const int ks = wave / TMW;                   // split-K slice of this wave
+    const int i16 = lane & 15;
+    const int kq = lane >> 4;
+
+    int mt = blockIdx.y;
+    int nt = blockIdx.z;
+    if (p.xcd_gn > 0) {                          // XCD-aware tile order, as conv_gemm_f32
+        const int wg = blockIdx.y, c = wg & 7, j = wg >> 3;
+        const int im = c / p.xcd_gn, in = c - im * p.xcd_gn;
+        mt = (im << p.xcd_mts) + (j & ((1 << p.xcd_mts) - 1));
+        nt = in * p.xcd_ntn + (j >> p.xcd_mts);
+    }
+    const int s0 = nt * SPT;                     // first sample of this tile
+    const int m0 = mt * BM;                      // first output channel of this tile
+    const int M = p.M;
+    const int nvalid = min(SPT, p.B - s0);
+
+    // A operand (activations): the lane's (sample, position) of block 0 at tap 0; block q is 2q rows further
+    const int asmp = halo8_sample(i16);
+    const int koff = ks * (GW * KU) + 2 * kq;    // this wave's channels of a chunk, this lane's pair of a unit
+    const int afrag2 = ((asmp * SEG + halo8_pos(i16, 0)) * KP + (int)((p.xswz >> (4 * asmp)) & 15) * 4 + koff) >> 1;
+    // B operand (weights): the lane's float2 of (slot 0, group 0) in the image [ci / 16][slot][M][ci % 16]
+    const float* const wsrc = p.w + ((long)(m0 + tm * 16 + i16) * KG + 2 * kq);
+    const long w_chunk_stride = (long)NSUB * p.wtaps * M * KG;
+    auto w_load = [&](int k, int chunk) -> float2 {
+        const int slot = k / GW, gw = k - slot * GW;
+        const int c8 = (ks * GW + gw) * KU;      // wave-uniform: first channel of the unit within the chunk
+        return *reinterpret_cast<const float2*>(wsrc + chunk * w_chunk_stride + (long)(((c8 / KG) * p.wtaps + slot) * M) * KG + c8 % KG);
+    };
+
+    // two accumulation chains (one per k-step of a unit) for each of the four blocks of 16 x 16
+    f32x4 acc[2][4];                             // [k-step][block]
+    f32x4 accr[2][4];                            // RES: the riding 1x1 conv
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { acc[s][q][r] = 0.0f; accr[s][q][r] = 0.0f; }
+
+    const int nchunks = (p.cin0 + p.cin1) / KC;  // whole chunks (host-checked), no grid split-K
+
+    // ---- X staging: global -> registers (prefetch) -> LDS, as conv_halo8_f32 -------------------------------------
+    constexpr int NW = WTAPS * GW;               // weight fragments of this wave per chunk
+    constexpr int KQ = KC / 4;                   // float4 per row
+    constexpr int X_PER_T = BN * KQ / NT;
+    static_assert(X_PER_T == 1, "every thread stages one X item");
+    float2 wcur[NW], wnxt[NW];
+    float4 xreg;
+    int x_grow, x_q4, x_loff;
+    {
+        const int row = tid / KQ;                // s*L + l
+        const int q = tid - row * KQ;
+        const int s = row >> LSH;
+        const int l = row - (s << LSH);
+        x_grow = s < nvalid ? s0 * L + row : -1;
+        x_q4 = q * 4;
+        x_loff = ((s * SEG + PAD + l) * KP + q * 4 + (int)((p.xswz >> (4 * s)) & 15) * 4) >> 2;
+    }
+    auto x_store = [&](int stage) {
+        float4 v = xreg;
+        if (x_grow < 0) v = make_float4(0.f, 0.f, 0.f, 0.f);          // no such sample
+        smem4[stage * STAGE4 + x_loff] = v;
+    };
+    auto x_load = [&](int chunk) {
+        const int c0 = chunk * KC;
+        // whole chunk inside one source: one pointer per chunk, unconditional load (rows that do not exist read
+        // row 0 and are zeroed at the store)
+        const bool second = c0 >= p.cin0;
+        const float* xsrc = second ? p.src1 : p.src0;
+        const int cs = second ? p.cin1 : p.cin0;
+        const int cb = second ? c0 - p.cin0 : c0;
+        xreg = *reinterpret_cast<const float4*>(xsrc + (long)max(x_grow, 0) * cs + cb + x_q4);
+    };
+
+    // ---- MFMA operand fragments: unit u = (tap index, 8-channel group of this wave) ---------------------------
+    constexpr int UW = WTAPS * GW;
+    auto frag_a = [&](int stage, int u, int q) -> float2 {
+        const int wtap = u / GW, gw = u - wtap * GW;
+        const int tap = (RES && wtap == TAPS) ? PAD : (q < 2 ? wtap : TAPS - 1 - wtap);   // the 1x1 ride reads the centre rows
+        return smem2[stage * STAGE2 + afrag2 + q * KP + tap * (KP / 2) + gw * (KU / 2)];
+    };
+
+    x_load(0);
+#pragma unroll
+    for (int k = 0; k < NW; ++k) wcur[k] = wnxt[k] = w_load(k, 0);
+
+    // ---- epilogue ownership (decided up front so its global loads can fly under the K loop), as conv_gemm_f32 --
+    constexpr int ES = BM + 4;
+    constexpr int ECOPY = BN * ES;
+    constexpr int F4PL = (BN * BM / 4) / NT;
+    static_assert(F4PL >= 1 && (BN * BM / 4) % NT == 0 && (F4PL & (F4PL - 1)) == 0, "epilogue mapping");
+    const bool has_gn = p.gamma != nullptr;
+    const int cpg = has_gn ? p.cpg : BM;
+    const int cq = cpg >> 2;
+    const int cnt4 = has_gn ? (L * cq) : (BN * cq);
+    const int lpp = cnt4 >> (F4PL == 1 ? 0 : F4PL == 2 ? 1 : F4PL == 4 ? 2 : 3);
+    const int lpp_sh = 31 - __clz(lpp);
+    const int cq_sh = 31 - __clz(cq);
+    const int gpt_sh = 31 - __clz(BM) - (31 - __clz(cpg));
+    const int pr = tid >> lpp_sh;
+    const int lp = tid & (lpp - 1);
+    const int ps = has_gn ? pr >> gpt_sh : 0;
+    const int pg = has_gn ? pr & ((1 << gpt_sh) - 1) : 0;
+    int erow[F4PL], ecol[F4PL];
+    int eoff[F4PL];
+    float4 bias4[F4PL], gam4[F4PL], bet4[F4PL], temb4[F4PL], res4[F4PL];
+#pragma unroll
+    for (int k = 0; k < F4PL; ++k) {
+        const int j = lp + k * lpp;
+        const int r = j >> cq_sh;
+        erow[k] = ps * L + r;
+        ecol[k] = pg * cpg + (j & (cq - 1)) * 4;
+        const int s = erow[k] >> LSH;
+        eoff[k] = ((s0 + s) * L + (erow[k] & (L - 1))) * M + m0 + ecol[k];
+        if (s >= nvalid) eoff[k] = -1;
+    }
+    // every parameter load is unconditional: an absent operand reads the bias row and is cancelled by a select
+    const float* const gptr = has_gn ? p.gamma : p.bias;
+    const float* const bptr = has_gn ? p.beta : p.bias;
+    const float* const tptr = p.temb != nullptr ? p.temb : p.bias;
+    const bool has_res = p.res != nullptr;
+    const bool has_temb = p.temb != nullptr;
+#pragma unroll
+    for (int k = 0; k < F4PL; ++k) {
+        const int em = m0 + ecol[k];
+        long toff = 0;
+        if (p.trow != nullptr)                   // per-row timesteps
+            toff = (long)p.trow[min(s0 + (erow[k] >> LSH), p.B - 1)] * p.temb_stride;
+        bias4[k] = ldg4(p.bias + em);
+        gam4[k] = ldg4(gptr + em);
+        bet4[k] = ldg4(bptr + em);
+        temb4[k] = ldg4(tptr + toff + em);
+        res4[k] = ldg4(has_res ? p.res + max(eoff[k], 0) : p.bias + em);
+    }
+    // zero the halo rows of both X stages once (real rows are rewritten in full by every chunk's staging)
+    {
+        constexpr int KP4 = KP / 4;
+        constexpr int nz = SPT * (2 * PAD) * KP4;
+        for (int i = tid; i < nz; i += NT) {
+            const int hr = i / KP4, c4 = i - hr * KP4;
+            const int s = hr / (2 * PAD), j = hr - s * (2 * PAD);
+            const int row = s * SEG + (j < PAD ? j : L + j);
+            const int at = row * KP + c4 * 4 + (int)((p.xswz >> (4 * s)) & 15) * 4;
+            smem4[at >> 2] = make_float4(0.f, 0.f, 0.f, 0.f);
+            smem4[STAGE4 + (at >> 2)] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    x_store(0);
+    if (1 < nchunks) x_load(1);
+    __syncthreads();
+
+    // ---- main loop: a unit is 8 channels = 2 k-steps x 4 blocks of v_mfma_f32_16x16x4_f32, minus blocks 0 and 3 at
+    // tap index 0 (all halo).  During chunk ch the weights of ch + 1 arrive in wnxt, X of ch + 1 goes to the other
+    // stage and X of ch + 2 into xreg ------------------------------------------------------------------------------
+    constexpr int XU = (NW + 1) / 2;             // the unit after the last weight load
+    static_assert(XU < UW, "the X item rolls inside the chunk");
+    float2 a[4];
+    a[0] = a[3] = make_float2(0.f, 0.f);
+    a[1] = frag_a(0, 0, 1);
+    a[2] = frag_a(0, 0, 2);
+#define DAD8W_ROLL(STORE, LOAD)                                                                  \
+    _Pragma("unroll") for (int k = 0; k < NW; ++k) {                                             \
+        if (k / 2 != u) continue;                                                                \
+        if (STORE) wnxt[k] = w_load(k, ch + 1);                                                  \
+    }                                                                                            \
+    if (u == XU) {                                                                               \
+        if (STORE) x_store(cur ^ 1);                                                             \
+        if (LOAD) x_load(ch + 2);                                                                \
+    }
+#define DAD8W_READ(ST, U)                                                                        \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                \
+        if ((U) / GW != 0 || (q != 0 && q != 3)) na[q] = frag_a(ST, U, q);   /* tap index 0, blocks 0 and 3: never multiplied */
+#define DAD8W_STEP(ACC, S, C, B01, B23, SKIP)                                                    \
+    if (!(SKIP)) ACC[S][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0].C, B01.C, ACC[S][0], 0, 0, 0); \
+    ACC[S][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1].C, B01.C, ACC[S][1], 0, 0, 0);         \
+    ACC[S][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2].C, B23.C, ACC[S][2], 0, 0, 0);         \
+    if (!(SKIP)) ACC[S][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3].C, B23.C, ACC[S][3], 0, 0, 0);
+#define DAD8W_MFMA()                                                                             \
+    if (RES && u / GW == TAPS) {                                                                 \
+        const float2 b = wcur[u];                                                                \
+        DAD8W_STEP(accr, 0, x, b, b, false)                                                      \
+        DAD8W_STEP(accr, 1, y, b, b, false)                                                      \
+    } else {                                                                                     \
+        const float2 b01 = wcur[u], b23 = wcur[(TAPS - 1 - u / GW) * GW + u % GW];               \
+        DAD8W_STEP(acc, 0, x, b01, b23, u / GW == 0)                                             \
+        DAD8W_STEP(acc, 1, y, b01, b23, u / GW == 0)                                             \
+    }
+    // STORE: chunk ch+1 exists (its X rows go to the other stage, its weights to wnxt); LOAD: chunk ch+2 exists
+#define DAD8W_CHUNK(STORE, LOAD)                                                                 \
+    {                                                                                            \
+        const int cur = ch & 1;                                                                  \
+        _Pragma("unroll") for (int u = 0; u < UW; ++u) {                                         \
+            float2 na[4] = {a[0], a[1], a[2], a[3]};                                             \
+            DAD8W_ROLL(STORE, LOAD)                                                              \
+            if (u + 1 < UW) {                                                                    \
+                DAD8W_READ(cur, u + 1)                                                           \
+            } else {                                                                             \
+                __syncthreads();                                                                 \
+                if (STORE) { DAD8W_READ(cur ^ 1, 0) }                                            \
+            }                                                                                    \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+            DAD8W_MFMA()                                                                         \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+            _Pragma("unroll") for (int q = 0; q < 4; ++q) a[q] = na[q];                          \
+        }                                                                                        \
+        if (STORE) {                                                                             \
+            _Pragma("unroll") for (int k = 0; k < NW; ++k) wcur[k] = wnxt[k];                    \
+        }                                                                                        \
+    }
+    int ch = 0;
+    for (; ch + 2 < nchunks; ++ch) DAD8W_CHUNK(true, true)
+    if (ch + 1 < nchunks) { DAD8W_CHUNK(true, false) ++ch; }
+    if (ch < nchunks) DAD8W_CHUNK(false, false)
+#undef DAD8W_CHUNK
+#undef DAD8W_MFMA
+#undef DAD8W_STEP
+#undef DAD8W_READ
+#undef DAD8W_ROLL
+    __syncthreads();                             // all MFMAs retired before the stage memory is reused
+
+    // ---- epilogue: conv_halo8_f32's, with this kernel's accumulator -> tile row map ------------------------------
+    float* E = smem;                             // [SK][BN][ES]
+    float* red = smem + SK * ECOPY;              // [2][waves] cross-wave partials
+#define DAD8W_DROP(A)                                                                            \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                              \
+        const int i = 4 * kq + r;                /* MFMA row of accumulator register r */        \
+        const int row = halo8_sample(i) * L + halo8_pos(i, q);                                   \
+        const int col = tm * 16 + i16;                                                           \
+        E[ks * ECOPY + row * ES + col] = A[0][q][r] + A[1][q][r];                                \
+    }
+    DAD8W_DROP(acc)
+    __syncthreads();
+
+    float y[F4PL][4];
+#pragma unroll
+    for (int k = 0; k < F4PL; ++k) {
+        const float* q = E + erow[k] * ES + ecol[k];
+        float4 v = *reinterpret_cast<const float4*>(q);
+#pragma unroll
+        for (int c = 1; c < SK; ++c) {
+            const float4 u = *reinterpret_cast<const float4*>(q + c * ECOPY);
+            v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+        }
+        y[k][0] = v.x; y[k][1] = v.y; y[k][2] = v.z; y[k][3] = v.w;
+    }
+
+    if constexpr (RES) {
+        // the riding 1x1 conv: same exchange, same ownership, bias, store
+        __syncthreads();                         // every thread has read its main-tile values
+        DAD8W_DROP(accr)
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < F4PL; ++k) {
+            const float* q = E + erow[k] * ES + ecol[k];
+            float4 v = *reinterpret_cast<const float4*>(q);
+#pragma unroll
+            for (int c = 1; c < SK; ++c) {
+                const float4 u = *reinterpret_cast<const float4*>(q + c * ECOPY);
+                v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+            }
+            const float4 rb = ldg4(p.rbias + m0 + ecol[k]);
+            if (eoff[k] >= 0)
+                store_f4_sc1(p.rdst + eoff[k], make_float4(v.x + rb.x, v.y + rb.y, v.z + rb.z, v.w + rb.w));
+        }
+    }
+#undef DAD8W_DROP
 #pragma unroll
     for (int k = 0; k < F4PL; ++k) {
         y[k][0] += bias4[k].x; y[k][1] += bias4[k].y; y[k][2] += bias4[k].z; y[k][3] += bias4[k].w;

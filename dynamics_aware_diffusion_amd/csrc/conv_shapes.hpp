@@ -47,6 +47,9 @@ DAD_HD inline int halo8_tap(int tn, int t) { return tn ? 4 - t : t; }
 // in float4, a thread owns (64 * BM / 4) / threads of them.  A pair of more than 64 lanes spans lpp / 64 waves, whose
 // partial sums meet through LDS.
 DAD_HD inline int halo8_lanes_per_pair(int BM, int threads, int cpg) { return (8 * (cpg / 4)) / ((64 * BM / 4) / threads); }
+// LDS floats of a conv_halo8w_f32 block: its two stages hold the X rows alone (the weights never pass through LDS),
+// so the epilogue's exchange tile decides.
+DAD_HD inline size_t halo8w_lds_floats(int BM, int SK) { return conv_lds_floats(BM, 64, 32, 5, 8, 8, SK, /*bdir=*/true); }
 
 // conv_wgrad (train_bwd.hpp)
 constexpr int WG_THREADS = 512;             // 8 waves: TM x TN wave tiles of 32 x 32 (x TAPS), the rest split K

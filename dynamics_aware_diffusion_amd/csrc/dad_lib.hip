@@ -268,6 +268,20 @@ const void* find_kernel(int family, const int* k, int n) {
 }
 const void* find_kernel(int family, std::initializer_list<int> k) { return find_kernel(family, k.begin(), (int)k.size()); }
 
+// The register-weight form of a FAM_HALO8 key (conv_halo8.hpp, conv_halo8w_f32): a second instantiation under the same
+// (cfg, ride), generated from the family's predicate like the table — the registry's keys name the pair.
+template <int CFG, int RIDE>
+const void* halo8w_kernel_of() {
+    if constexpr (halo8_kernel_exists(CFG, RIDE != 0)) return (const void*)dad::conv_halo8w_f32<kTiles[CFG].BM, kTiles[CFG].SK, RIDE != 0>;
+    else return nullptr;
+}
+template <size_t... I>
+const void* find_halo8w(int cfg, bool ride, std::index_sequence<I...>) {
+    static const void* const fns[] = {halo8w_kernel_of<(int)I / 2, (int)I % 2>()...};
+    return cfg >= 0 && cfg < kNumTiles ? fns[2 * cfg + (ride ? 1 : 0)] : nullptr;
+}
+const void* find_halo8w(int cfg, bool ride) { return find_halo8w(cfg, ride, std::make_index_sequence<2 * kNumTiles>()); }
+
 // Every kernel may use up to the full 160 KiB of LDS; the dynamic-LDS limit is a per-device
 // function attribute, raised once per device (not lazily per launch, so that nothing but launches
 // happens under hipGraph capture).
@@ -286,6 +300,9 @@ int configure_kernels() {
                                     (const void*)dad::guide_mlp_kernel<dad::GUIDE_RELU>,
                                     (const void*)dad::guide_mlp_kernel<dad::GUIDE_MISH>};
     for (const KernelEntry& e : kernel_table()) fns.push_back(e.fn);      // every family
+    for (int cfg = 0; cfg < kNumTiles; ++cfg)
+        for (int ride = 0; ride < 2; ++ride)
+            if (const void* fn = find_halo8w(cfg, ride != 0)) fns.push_back(fn);
     for (const void* fn : fns)
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dad::kLdsBytes));
     done.insert(dev);
@@ -427,11 +444,12 @@ int launch_conv(dad_model* m, const ConvOp& op, const LaunchGeom& g, int batch, 
 #endif
     if (g.halo8) {                     // conv_halo8.hpp: same tile, grid, LDS and operands, its own slot shifts
         const void* fn = find_kernel(FAM_HALO8, {g.cfg, g.fused});
+        if (fn != nullptr && g.halo8w) fn = find_halo8w(g.cfg, g.fused);      // the register-weight form: its own LDS size
         if (fn == nullptr || gn_pass || p.pre != nullptr || p.stats != nullptr || p.kslices != 1)
-            return fail(DAD_E_INVALID, "no halo-skipping kernel for %s (tile %d res=%d)", op.name.c_str(), g.cfg, (int)g.fused);
+            return fail(DAD_E_INVALID, "no halo-skipping kernel for %s (tile %d res=%d wreg=%d)", op.name.c_str(), g.cfg, (int)g.fused, (int)g.halo8w);
         p.xswz = g.xswz8;
         void* hargs[] = {&p};
-        HIP_TRY(hipLaunchKernel(fn, dim3(g.gx, g.gy, g.gz), dim3(g.threads), hargs, g.lds_bytes, st));
+        HIP_TRY(hipLaunchKernel(fn, dim3(g.gx, g.gy, g.gz), dim3(g.threads), hargs, g.halo8w ? g.lds8w_bytes : g.lds_bytes, st));
         return DAD_OK;
     }
     const void* fn = find_kernel(FAM_GEMM, {g.cfg, op.taps, op.stride, launch_flags(op, g)});
@@ -951,7 +969,7 @@ int sampler_loop(dad_model* m, const FwdPlan& f, float* x, const dad_sampler_coe
     key.n_steps = n_steps; key.batch = batch; key.cond_per_row = cond_per_row;
     key.force_tile = m->force_tile;
     key.flags = (m->split_enabled ? 1 : 0) | (m->fuse_residual ? 2 : 0) | (m->xswz_enabled ? 4 : 0) |
-                (m->xcd_order ? 8 : 0) | (f.cc.ok ? 16 : 0) | (m->step_seam ? 32 : 0) | (m->split_target << 8);
+                (m->xcd_order ? 8 : 0) | (f.cc.ok ? 16 : 0) | (m->step_seam ? 32 : 0) | ((m->halo8_wreg + 1) << 6) | (m->split_target << 8);
     key.row_offset = row_offset;
     if (proj) key.alpha_hash = fnv1a_bytes(proj_alphas, (size_t)n_steps * sizeof(float));
     key.steps_hash = sampler_steps_hash(steps, n_steps);
@@ -1964,6 +1982,10 @@ int dad_debug_kernel_table_consistent(void) {
                      k[4], k[5], d.axes, (int)have);
                 return 0;
             }
+            if (fam == FAM_HALO8 && have != (find_halo8w(k[0], k[1] != 0) != nullptr)) {     // both forms of every key
+                fail(DAD_E_INVALID, "kernel table mismatch: conv_halo8w_f32 key (%d, %d) (registry %d)", k[0], k[1], (int)have);
+                return 0;
+            }
             n += have;
         }
         if (n != d.count) {
@@ -2024,6 +2046,7 @@ int dad_debug_set_option(dad_model* m, const char* name, int32_t value) {
     else if (key == "ccw_prefer16") m->ccw_prefer16 = value != 0;
     else if (key == "wgrad_blocks") m->wgrad_blocks = std::max(1, (int)value);
     else if (key == "halo8") m->halo8_enabled = value != 0;
+    else if (key == "halo8_wreg") m->halo8_wreg = value < 0 ? -1 : value != 0;
     else if (key == "step_seam") m->step_seam = value != 0;
     else return fail(DAD_E_INVALID, "unknown option '%s'", name);
     // every option changes which launches a captured loop holds, and not all of them are part of the

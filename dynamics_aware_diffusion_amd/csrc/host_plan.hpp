@@ -223,6 +223,8 @@ struct HostModel {
     mutable std::map<std::array<int, 5>, uint64_t> xswz_cache; // find_xswz memo: the cache of a pure function, filled by const planning
     bool halo8_enabled = true;                                 // 8-position 5-tap layers at full-chip batches take conv_halo8.hpp
     mutable std::map<std::array<int, 3>, uint64_t> xswz8_cache; // find_xswz_pairs memo
+    int halo8_wreg = -1;                                       //   ... as conv_halo8w_f32 (weights global -> register -> MFMA): 0 never,
+                                                               //   1 every form, -1 the forms measured faster (halo8w_faster)
     bool step_seam = true;                                     // dad_sample_loop: posterior + next first conv as one launch (plan_seam)
     // ---- backward pass (dad_model_set_training): data-gradient launches + the layout of the gradients
     bool training = false;
@@ -1091,6 +1093,8 @@ struct LaunchGeom {
     uint64_t xswz = 0;
     bool halo8 = false;      // launched as conv_halo8_f32<BM, SK, fused> (choose_halo8), not as the conv-GEMM kernel above
     uint64_t xswz8 = 0;      //   its slot shifts (find_xswz_pairs)
+    bool halo8w = false;     //   ... in its register-weight form conv_halo8w_f32, with
+    size_t lds8w_bytes = 0;  //   that form's dynamic LDS (X rows only: halo8w_lds_floats)
 };
 
 // The general staging path (RAGGED kernels): a K chunk may straddle the concat's seam or the end of the channels, or
@@ -1248,13 +1252,18 @@ inline bool halo8_layer(const ConvOp& op) {
     return op.kind == CONV_K5 && op.taps == 5 && op.stride == 1 && op.Lin == 8 && op.Lout == 8 && !op.x3 && !op.bdir &&
            !op.net_padded && !op.padded() && op.pre < 0 && op.stats < 0;
 }
+// The register-weight form conv_halo8w_f32 exists wherever conv_halo8_f32 does; which of the two a launch takes by
+// default is the measurement of DESIGN.md section 3 ("Weights straight into MFMA registers"), per (tile, ride).
+constexpr bool halo8w_faster(int cfg, bool /*ride*/) { return cfg == 0 || cfg == 1; }
 inline void choose_halo8(const HostModel& m, const ConvOp& op, LaunchGeom& g) {
-    g.halo8 = false; g.xswz8 = 0;
+    g.halo8 = false; g.xswz8 = 0; g.halo8w = false; g.lds8w_bytes = 0;
     if (!m.halo8_enabled || m.force_tile >= 0 || !m.split_enabled || g.cfg < 0 || !halo8_layer(op)) return;
     if (!halo8_kernel_exists(g.cfg, g.fused) || g.kc != 32 || g.ragged || g.padded || g.windowed || g.split.kslices != 1) return;
     if ((long)g.mtiles * g.ntiles_n < kSplitMaxTiles) return;
     g.halo8 = true;
     g.xswz8 = m.xswz_enabled ? find_xswz_pairs(m, op.Lout, op.taps / 2, (g.kc + 4) / 4) : 0;
+    g.halo8w = m.halo8_wreg < 0 ? halo8w_faster(g.cfg, g.fused) : m.halo8_wreg != 0;
+    if (g.halo8w) g.lds8w_bytes = dad::halo8w_lds_floats(kTiles[g.cfg].BM, kTiles[g.cfg].SK) * sizeof(float);
 }
 
 // ------------------------------------------------------------------ small-batch (CC) plan

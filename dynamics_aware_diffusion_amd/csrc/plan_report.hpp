@@ -201,7 +201,7 @@ inline void forward_plan_encode(const HostModel& m, int mode, int batch, const F
         rec[DAD_FP_REC_KC] = g.kc; rec[DAD_FP_REC_KSLICES] = g.split.kslices; rec[DAD_FP_REC_GN_NPT] = g.gn_npt;
         rec[DAD_FP_REC_NTILES_N] = g.ntiles_n; rec[DAD_FP_REC_MTILES] = g.mtiles;
         rec[DAD_FP_REC_PART_TILE] = g.cfg >= 0 && op.Lout <= bn && batch % (bn / op.Lout) != 0;
-        rec[DAD_FP_REC_FAMILY] = g.halo8 ? DAD_FP_FAMILY_HALO8 : DAD_FP_FAMILY_GEMM;
+        rec[DAD_FP_REC_FAMILY] = !g.halo8 ? DAD_FP_FAMILY_GEMM : g.halo8w ? DAD_FP_FAMILY_HALO8W : DAD_FP_FAMILY_HALO8;
     };
     r[DAD_FP_RECORD_INTS] = DAD_FP_REC_INTS;
     if (mode == 3) {

@@ -451,6 +451,8 @@ int dad_profile_read(dad_model* m, double* conv_ms, int64_t* conv_launches, doub
  * 16-row tiles instead of a 32-row tile whose K slice LDS would halve), "wgrad_blocks" (blocks a
  * weight-gradient launch of the backward pass aims for: tiles x batch splits), "halo8" (5-tap convs of
  * 8-position layers at full-chip batches under the heuristic take csrc/conv_halo8.hpp; 0 = the conv-GEMM kernels),
+ * "halo8_wreg" (which of those launches take the register-weight form conv_halo8w_f32: 1 all, 0 none, -1 = the default,
+ * the forms measured faster; the same bits either way),
  * "step_seam" (dad_sample_loop runs the posterior update of a step and the first conv of the next evaluation as one
  * launch, csrc/conv_seam.hpp, where dad_debug_seam_plan says so; 0 = the two launches; same bits either way).
  * Results do not depend on these choices beyond fp32 summation order. */
@@ -702,7 +704,8 @@ DAD_LAYOUT(DAD_FP_FINALS, 0);
 DAD_LAYOUT(DAD_FP_REC_INTS, 0);
 #define DAD_FP_FAMILIES_LIST(F) \
     F(DAD_FP_FAMILY_GEMM, gemm, 1, "conv_gemm_f32") \
-    F(DAD_FP_FAMILY_HALO8, halo8, 1, "conv_halo8_f32 of csrc/conv_halo8.hpp on the same tile, grid and ride")
+    F(DAD_FP_FAMILY_HALO8, halo8, 1, "conv_halo8_f32 of csrc/conv_halo8.hpp on the same tile, grid and ride") \
+    F(DAD_FP_FAMILY_HALO8W, halo8w, 1, "its register-weight form conv_halo8w_f32 under the same key (option halo8_wreg)")
 DAD_LAYOUT(DAD_FP_FAMILIES, 0);
 #define DAD_FP_CC_INTS_LIST(F) \
     F(DAD_FP_CC_CONV, conv, 1, "index into the plan") \
