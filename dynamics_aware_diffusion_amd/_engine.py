@@ -210,6 +210,18 @@ ABI = {
     "dad_train_objective_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                                C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dad_train_dynamics_objective_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(DadProjectArgs), C.c_int32, C.c_int32,
+                                                               C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "dad_train_dynamics_objective_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                       C.POINTER(DadProjectArgs), C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dad_train_dynamics_objective_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                        C.POINTER(DadProjectArgs), C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
+                                                        C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dad_debug_dynamics_objective_plan": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32,
+                                                                                      C.POINTER(C.c_int32)]),
     "dad_debug_objective_offsets": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "dad_debug_objective_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                            C.POINTER(C.c_int32)]),
@@ -1017,6 +1029,17 @@ class HipEngine:
         _require_device(d_loss, "d_loss")
         _, sc = self._objective_bytes(B)
         scratch = torch.empty(max(sc, 4) // 4 + 4, dtype=torch.float32, device=self.device)
+        flat, ptrs, tptrs, finish = self._grad_buffers(shapes)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_train_objective_backward(
+                self._h, x0.data_ptr(), noise.data_ptr(), _ptr(weights), int(loss_type), d_loss.data_ptr(),
+                ptrs, len(ptrs), tptrs, len(tptrs), B, saved.data_ptr(), saved.numel() * 4,
+                scratch.data_ptr(), scratch.numel() * 4, self._stream()))
+        return finish(flat)
+
+    def _grad_buffers(self, shapes):
+        """The flat gradient allocation of one objective backward: (flat, conv pointers, time pointers, finish), where
+        ``finish(flat)`` returns the tensors shaped like ``shapes`` (as :meth:`objective_backward` returns them)."""
         conv, conv_total = self.grad_layout()
         time, time_total = self.time_grad_layout()
         layout = list(conv) + [(k, conv_total + o, n) for k, o, n in time]
@@ -1034,17 +1057,98 @@ class HipEngine:
         base = flat.data_ptr()
         ptrs = (C.c_void_p * len(conv))(*[base + 4 * o for _, o, _ in layout[:len(conv)]])
         tptrs = (C.c_void_p * len(time))(*[base + 4 * o for _, o, _ in layout[len(conv):]])
+
+        def finish(flat):
+            if real is not None:
+                return real.gather(flat)
+            spans = [layout[i + 1][1] - layout[i][1] for i in range(len(layout) - 1)] + [total - layout[-1][1]]
+            return [(pc if pc.numel() == numel else pc[:numel]).view(tuple(shape))
+                    for pc, (_, _, numel), shape in zip(flat.split_with_sizes(spans), layout, shapes)]
+        return flat, ptrs, tptrs, finish
+
+    # ------------------------------------------------------------------ dynamics-aware objective
+    def _dynamics_bytes(self, state: "ProjectionState", form: int, batch: int):
+        """(saved, scratch) bytes of a dynamics-aware objective step (dad_train_dynamics_objective_workspace_bytes)."""
+        a = state.args
+        key = ("dyn", a.state_dim, a.observation_dim, a.action_dim, form, batch)
+        cache = self.__dict__.setdefault("_objective_sizes", {})
+        if key not in cache:
+            sv, sc = C.c_size_t(), C.c_size_t()
+            _check(self.lib, self.lib.dad_train_dynamics_objective_workspace_bytes(self._h, C.byref(a), form, batch,
+                                                                                   C.byref(sv), C.byref(sc)))
+            cache[key] = (sv.value, sc.value)
+        return cache[key]
+
+    def dynamics_objective_forward(self, x0: torch.Tensor, t32: torch.Tensor, noise: torch.Tensor,
+                                   weights: Optional[torch.Tensor], loss_type: int, state: "ProjectionState", form: int,
+                                   diffusion_weight: float, projection_weight: float,
+                                   timestep_weights: Optional[torch.Tensor]):
+        """The dynamics-aware objective of one batch (dad_train_dynamics_objective_forward): returns (parts, saved) —
+        the device float[3] (diffusion, weighted projection, total) and what :meth:`dynamics_objective_backward` needs."""
+        B = self._traj(x0, "x_start")
+        for name, ten in (("noise", noise), ("weights", weights)):
+            if ten is not None and self._traj(ten, name) != B:
+                raise RuntimeError(f"{name} batch mismatch")
+        if t32.dtype != torch.int32 or t32.numel() != B or t32.device != x0.device or not t32.is_contiguous():
+            raise RuntimeError("t must be (B) contiguous int32 on the trajectory's device")
+        if timestep_weights is not None:
+            _require_device(timestep_weights, "timestep_weights")
+            if timestep_weights.numel() != self.n_timesteps:
+                raise RuntimeError(f"timestep_weights has {timestep_weights.numel()} entries, expected {self.n_timesteps}")
+        if state.P.device != x0.device:
+            raise RuntimeError(f"x is on {x0.device}, the projector on {state.P.device}")
+        sv, _ = self._dynamics_bytes(state, form, B)
+        saved = torch.empty(max(sv, 4) // 4 + 4, dtype=torch.float32, device=self.device)
+        parts = torch.empty(3, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.dad_train_objective_backward(
-                self._h, x0.data_ptr(), noise.data_ptr(), _ptr(weights), int(loss_type), d_loss.data_ptr(),
-                ptrs, len(conv), tptrs, len(time), B, saved.data_ptr(), saved.numel() * 4,
+            _check(self.lib, self.lib.dad_train_dynamics_objective_forward(
+                self._h, x0.data_ptr(), t32.data_ptr(), noise.data_ptr(), _ptr(weights), int(loss_type),
+                C.byref(state.args), int(state.D), int(form), float(diffusion_weight), float(projection_weight),
+                _ptr(timestep_weights), parts.data_ptr(), B, saved.data_ptr(), saved.numel() * 4, self._stream()))
+        return parts, saved
+
+    def dynamics_objective_backward(self, x0: torch.Tensor, noise: torch.Tensor, weights: Optional[torch.Tensor],
+                                    loss_type: int, state: "ProjectionState", form: int, diffusion_weight: float,
+                                    projection_weight: float, timestep_weights: Optional[torch.Tensor],
+                                    d_loss: torch.Tensor, saved: torch.Tensor, shapes):
+        """Every parameter gradient of the total (dad_train_dynamics_objective_backward), as :meth:`objective_backward`
+        returns them.  ``d_loss``: autograd's incoming scalar, on the device; it is read there."""
+        B = self._traj(x0, "x_start")
+        _require_device(d_loss, "d_loss")
+        _, sc = self._dynamics_bytes(state, form, B)
+        scratch = torch.empty(max(sc, 4) // 4 + 4, dtype=torch.float32, device=self.device)
+        flat, ptrs, tptrs, finish = self._grad_buffers(shapes)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.dad_train_dynamics_objective_backward(
+                self._h, x0.data_ptr(), noise.data_ptr(), _ptr(weights), int(loss_type), C.byref(state.args), int(state.D),
+                int(form), float(diffusion_weight), float(projection_weight), _ptr(timestep_weights), d_loss.data_ptr(),
+                ptrs, len(ptrs), tptrs, len(tptrs), B, saved.data_ptr(), saved.numel() * 4,
                 scratch.data_ptr(), scratch.numel() * 4, self._stream()))
-        if real is not None:
-            return real.gather(flat)
-        spans = [layout[i + 1][1] - layout[i][1] for i in range(len(layout) - 1)] + [total - layout[-1][1]]
-        pieces = flat.split_with_sizes(spans)
-        return [(pc if pc.numel() == numel else pc[:numel]).view(tuple(shape))
-                for pc, (_, _, numel), shape in zip(pieces, layout, shapes)]
+        return finish(flat)
+
+    def dynamics_objective_plan(self, batch: int, state_dim: int = None, observation_dim: int = None, action_dim: int = None,
+                                form: Optional[str] = None, *, state: "ProjectionState" = None) -> dict:
+        """What one dynamics-aware objective step adds to the fused objective's (:meth:`objective_plan`) at `batch`, for a
+        projector over these widths (or ``state``'s) under ``form`` (None: planned, "row", "gemm"): host logic only
+        (dad_debug_dynamics_objective_plan).  Keys as DAD_DO_* of include/dad.h: ``form`` ("row" / "gemm"), ``D``,
+        ``horizon``, ``col_blocks``, ``refused``, the layout (``saved_base``, ``saved_bytes``, ``scratch_base``,
+        ``scratch_bytes`` in bytes; ``r_offset``, ``part_offset``, ``violation_offset``, ``g_offset`` in floats behind the
+        bases), ``objective_launches``, ``fwd_launches`` and ``launches``: one dict per launch of the step's own kernels,
+        the forward's first, with ``kind`` (a name of DAD_DO_KINDS), ``grid`` (x, y), ``threads``, ``lds_bytes`` and
+        ``rows_per_block``."""
+        if state is not None:
+            state_dim, observation_dim, action_dim = state.args.state_dim, state.args.observation_dim, state.args.action_dim
+        head, launches = decode_report(
+            _fetch(self.lib.dad_debug_dynamics_objective_plan, self._h, int(batch), int(state_dim), int(observation_dim),
+                   int(action_dim), _violation_form(form)), "DAD_DO_HEADER", "DAD_DO_REC_INTS")
+        assert head["launches"] == len(launches)
+        kinds = _names("DAD_DO_KINDS")
+        for q in launches:
+            q["kind"] = kinds[q["kind"]]
+            q["grid"] = (q.pop("gx"), q.pop("gy"))
+        head["form"], head["refused"] = _names("DAD_VG_FORMS")[head["form"]], bool(head["refused"])
+        head["launches"] = launches
+        return head
 
     def objective_saved_views(self, saved: torch.Tensor, batch: int):
         """(x_t, denoiser output) as the last objective_forward left them in ``saved`` (test hook)."""

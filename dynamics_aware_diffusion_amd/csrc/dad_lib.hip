@@ -90,6 +90,8 @@ struct dad_model : HostModel {
     float* d_h1 = nullptr;            // [T][4 time_dim] scratch of the table builder
     std::vector<float> train_sched[2];         // dad_model_load_train_schedule: sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod
     float* d_train_sched = nullptr;   // [2][T] their device copy (made when the model is finalized, or at the load after it)
+    float* d_recip_sched = nullptr;   // [2][T] device copy of sched[0], sched[1] (sqrt_recip / sqrt_recipm1_alphas_cumprod): made by the
+    bool recip_sched_stale = true;    //   first dynamics-aware objective call behind a dad_model_load_schedule
     std::vector<void*> owned;         // every hipMalloc to free
     void* d_repack = nullptr;         // dad_model_refresh_weights: descriptor table of the last refresh (device)
     size_t repack_cap = 0;
@@ -296,6 +298,10 @@ int configure_kernels() {
                                     (const void*)dad::project_kernel<4, 16>, (const void*)dad::project_kernel<1, 16>,
                                     (const void*)dad::violation_bwd_row_kernel, (const void*)dad::violation_fwd_gemm_kernel,
                                     (const void*)dad::violation_bwd_gemm_kernel,
+                                    (const void*)dad::dynamics_violation_fwd_row_kernel<1, dad::PROJ_KP>,
+                                    (const void*)dad::dynamics_violation_fwd_row_kernel<4, dad::PROJ_KP>,
+                                    (const void*)dad::dynamics_violation_fwd_gemm_kernel, (const void*)dad::dynamics_violation_bwd_row_kernel,
+                                    (const void*)dad::dynamics_violation_bwd_gemm_kernel,
                                     (const void*)dad::guide_mlp_kernel<dad::GUIDE_TANH>,
                                     (const void*)dad::guide_mlp_kernel<dad::GUIDE_RELU>,
                                     (const void*)dad::guide_mlp_kernel<dad::GUIDE_MISH>};
@@ -476,6 +482,24 @@ int upload_train_schedule(dad_model* m) {
     }
     HIP_TRY(hipMemcpy(m->d_train_sched, m->train_sched[0].data(), T * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->d_train_sched + T, m->train_sched[1].data(), T * sizeof(float), hipMemcpyHostToDevice));
+    return DAD_OK;
+}
+// device copy of the two schedule vectors predict_start_from_noise reads (the dynamics-aware objective's x0_hat), made on
+// first use behind a dad_model_load_schedule; a later load drains the device first, as above.
+int ensure_recip_schedule(dad_model* m) {
+    if (!m->have_sched) return fail(DAD_E_STATE, "schedule not loaded (dad_model_load_schedule)");
+    if (!m->recip_sched_stale) return DAD_OK;
+    const size_t T = m->sched[0].size();
+    if (m->d_recip_sched != nullptr) HIP_TRY(hipDeviceSynchronize());
+    if (m->d_recip_sched == nullptr) {
+        void* a = nullptr;
+        HIP_TRY(hipMalloc(&a, 2 * T * sizeof(float)));
+        m->owned.push_back(a);
+        m->d_recip_sched = (float*)a;
+    }
+    HIP_TRY(hipMemcpy(m->d_recip_sched, m->sched[0].data(), T * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_recip_sched + T, m->sched[1].data(), T * sizeof(float), hipMemcpyHostToDevice));
+    m->recip_sched_stale = false;
     return DAD_OK;
 }
 // The per-timestep tables follow the time-MLP tensors lazily (dad_model_refresh_weights marks them stale): every
@@ -1088,6 +1112,7 @@ int dad_model_load_schedule(dad_model* m, const float* a, const float* b, const 
     const float* src[5] = {a, b, c1, c2, lv};
     for (int i = 0; i < 5; ++i) m->sched[i].assign(src[i], src[i] + m->cfg.n_timesteps);
     m->have_sched = true;
+    m->recip_sched_stale = true;
     return DAD_OK;
 }
 
@@ -1840,22 +1865,13 @@ int training_report(const dad_model* m, int32_t batch, int (*report)(const HostM
     return rc != DAD_OK ? rc : copy_report(r, out, capacity, needed_out);
 }
 
-}  // namespace
-
-extern "C" {
-
-int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_rows, const float* noise,
-                                const float* weights, int32_t loss_type, float* loss_out, int32_t batch, void* saved,
-                                size_t saved_bytes, dad_stream_t stream) {
-    if (!m) return fail(DAD_E_INVALID, "null model");
-    if (!x0 || !t_rows || !noise || !loss_out || !saved) return fail(DAD_E_INVALID, "null pointer");
-    ObjectivePlan plan;
-    int rc = check_objective(m, batch, loss_type, false, plan);
+// The forward of the fused objective once it is planned and its arguments are checked: everything
+// dad_train_objective_forward launches (the dynamics-aware objective runs the same launches first).
+int objective_forward_run(dad_model* m, const ObjectivePlan& plan, const float* x0, const int32_t* t_rows, const float* noise,
+                          const float* weights, int32_t loss_type, float* loss_out, int32_t batch, void* saved, dad_stream_t stream) {
+    int rc = DAD_OK;
     const ObjectiveLayout& o = plan.o;
     const FwdPlan& f = plan.fwd;
-    if (rc != DAD_OK) return rc;
-    if (saved_bytes < o.saved_bytes)
-        return fail(DAD_E_WORKSPACE, "saved buffer has %zu bytes, the objective at batch %d needs %zu", saved_bytes, batch, o.saved_bytes);
     const dad_cfg& c = m->cfg;
     const int tdm = c.time_dim;
     const std::vector<TimeLaunch>& tl = plan.time;        // [0, 3): the forward's
@@ -1890,16 +1906,16 @@ int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_
     return DAD_OK;
 }
 
-int dad_train_objective_backward(dad_model* m, const float* x0, const float* noise, const float* weights, int32_t loss_type,
-                                 const float* d_loss, float* const* grad_tensors, int32_t n_grad_tensors,
-                                 float* const* time_grad_tensors, int32_t n_time_grad_tensors, int32_t batch, void* saved,
-                                 size_t saved_bytes, void* scratch, size_t scratch_bytes, dad_stream_t stream) {
-    if (!m) return fail(DAD_E_INVALID, "null model");
-    if (!x0 || !noise || !d_loss || !grad_tensors || !time_grad_tensors || !saved || !scratch) return fail(DAD_E_INVALID, "null pointer");
-    ObjectivePlan plan;
-    int rc = check_objective(m, batch, loss_type, true, plan);
+// The backward of the fused objective once it is planned: the rest of dad_train_objective_backward's refusals, then
+// its launches.  `need_saved` / `need_scratch`: what the caller's buffers must hold.  `head`: what writes d loss / d out
+// (enqueued behind every refusal of the denoiser's pass, ahead of its first launch) when it is not objective_dout_kernel.
+int objective_backward_run(dad_model* m, const ObjectivePlan& plan, const float* x0, const float* noise, const float* weights,
+                           int32_t loss_type, const float* d_loss, float* const* grad_tensors, int32_t n_grad_tensors,
+                           float* const* time_grad_tensors, int32_t n_time_grad_tensors, int32_t batch, void* saved,
+                           size_t saved_bytes, size_t need_saved, void* scratch, size_t scratch_bytes, size_t need_scratch,
+                           dad_stream_t stream, const std::function<int(const dad::ObjectiveParams&)>* head_of) {
+    int rc = DAD_OK;
     const ObjectiveLayout& o = plan.o;
-    if (rc != DAD_OK) return rc;
     // (both counts before either list is walked)
     if (n_grad_tensors != (int32_t)m->grad_slots.size())
         return fail(DAD_E_INVALID, "%d gradient tensors passed, the model has %zu (dad_train_grad_count)", n_grad_tensors, m->grad_slots.size());
@@ -1908,9 +1924,9 @@ int dad_train_objective_backward(dad_model* m, const float* x0, const float* noi
                     m->time_grad_slots.size());
     for (int32_t i = 0; i < n_time_grad_tensors; ++i)
         if (!time_grad_tensors[i]) return fail(DAD_E_INVALID, "time gradient tensor %d ('%s') is null", i, m->time_grad_slots[i].key.c_str());
-    if (saved_bytes < o.saved_bytes || scratch_bytes < o.scratch_bytes)
-        return fail(DAD_E_WORKSPACE, "objective workspaces too small (saved %zu / %zu, scratch %zu / %zu bytes)", saved_bytes, o.saved_bytes,
-                    scratch_bytes, o.scratch_bytes);
+    if (saved_bytes < need_saved || scratch_bytes < need_scratch)
+        return fail(DAD_E_WORKSPACE, "objective workspaces too small (saved %zu / %zu, scratch %zu / %zu bytes)", saved_bytes, need_saved,
+                    scratch_bytes, need_scratch);
     float* const sv = (float*)((char*)saved + o.saved_base);
     float* const sc = (float*)((char*)scratch + o.scratch_base);
     const int tdm = m->cfg.time_dim, W = m->tplan.temb_width;
@@ -1926,6 +1942,7 @@ int dad_train_objective_backward(dad_model* m, const float* x0, const float* noi
     // d loss / d out, scaled by autograd's incoming scalar on the device: enqueued by the denoiser's pass behind its own
     // refusals, ahead of its first launch
     const std::function<int()> head = [&]() -> int {
+        if (head_of != nullptr) return (*head_of)(q);
         hipLaunchKernelGGL(dad::objective_dout_kernel, dim3((unsigned)((q.n + 255) / 256)), dim3(dad::OBJ_THREADS), 0, st, q);
         HIP_TRY(hipGetLastError());
         return DAD_OK;
@@ -1952,6 +1969,185 @@ int dad_train_objective_backward(dad_model* m, const float* x0, const float* noi
     g.a = sc + o.dh1; g.lda = 4 * tdm; g.out = time_grad_tensors[0]; g.out2 = time_grad_tensors[1];
     return launch_time_gemm<dad::TG_BWD_DW1>(g, tl[8], st);                                 // d W1 = d h1^T emb, d b1
 }
+
+}  // namespace
+
+extern "C" {
+
+int dad_train_objective_forward(dad_model* m, const float* x0, const int32_t* t_rows, const float* noise,
+                                const float* weights, int32_t loss_type, float* loss_out, int32_t batch, void* saved,
+                                size_t saved_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (!x0 || !t_rows || !noise || !loss_out || !saved) return fail(DAD_E_INVALID, "null pointer");
+    ObjectivePlan plan;
+    const int rc = check_objective(m, batch, loss_type, false, plan);
+    if (rc != DAD_OK) return rc;
+    if (saved_bytes < plan.o.saved_bytes)
+        return fail(DAD_E_WORKSPACE, "saved buffer has %zu bytes, the objective at batch %d needs %zu", saved_bytes, batch, plan.o.saved_bytes);
+    return objective_forward_run(m, plan, x0, t_rows, noise, weights, loss_type, loss_out, batch, saved, stream);
+}
+
+int dad_train_objective_backward(dad_model* m, const float* x0, const float* noise, const float* weights, int32_t loss_type,
+                                 const float* d_loss, float* const* grad_tensors, int32_t n_grad_tensors,
+                                 float* const* time_grad_tensors, int32_t n_time_grad_tensors, int32_t batch, void* saved,
+                                 size_t saved_bytes, void* scratch, size_t scratch_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (!x0 || !noise || !d_loss || !grad_tensors || !time_grad_tensors || !saved || !scratch) return fail(DAD_E_INVALID, "null pointer");
+    ObjectivePlan plan;
+    const int rc = check_objective(m, batch, loss_type, true, plan);
+    if (rc != DAD_OK) return rc;
+    return objective_backward_run(m, plan, x0, noise, weights, loss_type, d_loss, grad_tensors, n_grad_tensors, time_grad_tensors,
+                                  n_time_grad_tensors, batch, saved, saved_bytes, plan.o.saved_bytes, scratch, scratch_bytes,
+                                  plan.o.scratch_bytes, stream, nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Every refusal the dynamics-aware entry points add to check_objective's, in the order the header documents, and the plan
+int check_dynamics(const dad_model* m, int batch, int loss_type, const dad_project_args* pa, int p_dim, int form, bool backward,
+                   DynamicsObjectivePlan& plan) {
+    if (loss_type != DAD_LOSS_L1 && loss_type != DAD_LOSS_L2)
+        return fail(DAD_E_INVALID, "unknown loss_type %d (DAD_LOSS_L1 = 1, DAD_LOSS_L2 = 2)", loss_type);
+    if (!m->training) return fail(DAD_E_INVALID, "training mode is off: dad_model_set_training(m, 1) before dad_model_finalize");
+    if (m->precision != DAD_PREC_FP32) return fail(DAD_E_INVALID, "the training objective exists for the fp32 arithmetic only, not split-f16");
+    if (batch <= 0) return fail(DAD_E_INVALID, "batch must be positive (got %d)", batch);
+    if (!pa || !pa->P || !pa->obs_mean || !pa->obs_std || !pa->act_mean || !pa->act_std)
+        return fail(DAD_E_INVALID, "dynamics objective: projection arguments missing");
+    // (the shape before the state of the model: what dad_debug_dynamics_objective_plan refuses is refused here too)
+    const int rc = dynamics_objective_plan(*m, batch, pa->state_dim, pa->observation_dim, pa->action_dim, form, backward, plan);
+    if (plan.launches.empty()) return rc;
+    if (p_dim != plan.D)
+        return fail(DAD_E_INVALID, "dynamics objective: the projector is (%d, %d), horizon %d needs (%d, %d)", p_dim, p_dim, plan.horizon,
+                    plan.D, plan.D);
+    if (plan.vg.refused)
+        return fail(DAD_E_INVALID, "dynamics objective: the row form at D=%d needs %zu bytes of LDS for one trajectory and its partial "
+                    "sums (a CU has %zu); the GEMM form (form 1, or -1) takes any D", plan.D, plan.vg.fwd.lds_bytes, dad::kLdsBytes);
+    if (!m->finalized) return fail(DAD_E_STATE, "dad_model_finalize has not been called");
+    if (m->d_train_sched == nullptr) return fail(DAD_E_STATE, "dad_model_load_train_schedule has not been called");
+    if (!m->have_sched) return fail(DAD_E_STATE, "schedule not loaded (dad_model_load_schedule)");
+    return rc;
+}
+
+// the kernels' arguments: `q` as the fused objective's run filled it (forward: objective_params), the plan's regions
+dad::DynamicsParams dynamics_params(const dad_model* m, const DynamicsObjectivePlan& plan, const dad::ObjectiveParams& q,
+                                    const dad_project_args* pa, float diffusion_weight, float projection_weight,
+                                    const float* timestep_weights, void* saved, void* scratch) {
+    dad::DynamicsParams d{};
+    const int T = m->cfg.n_timesteps, B = q.B;
+    float* const sv = (float*)((char*)saved + plan.saved_base);
+    const bool gemm = plan.vg.form == DAD_VG_GEMM;
+    d.obj = q;
+    dad::ProjParams& p = d.fwd.proj;
+    p.P = pa->P; p.obs_mean = pa->obs_mean; p.obs_std = pa->obs_std; p.act_mean = pa->act_mean; p.act_std = pa->act_std;
+    p.B = B; p.H = plan.horizon; p.n = pa->state_dim; p.od = pa->observation_dim; p.m = pa->action_dim; p.D = plan.D;
+    p.alpha = 1.0f; p.one_minus_alpha = 0.0f;
+    p.resid = sv + plan.r;
+    p.violation = gemm ? nullptr : sv + plan.violation;
+    d.fwd.part = gemm ? sv + plan.part : nullptr;
+    d.fwd.col_blocks = plan.vg.col_blocks;
+    dad::ViolationBwdParams& b = d.bwd;
+    b.P = pa->P; b.obs_std = pa->obs_std; b.act_std = pa->act_std;
+    b.r = sv + plan.r;
+    b.g = gemm && scratch != nullptr ? (float*)((char*)scratch + plan.scratch_base) + plan.g : nullptr;
+    b.B = B; b.H = plan.horizon; b.n = pa->state_dim; b.od = pa->observation_dim; b.m = pa->action_dim; b.D = plan.D;
+    b.row_elems = q.row_elems;
+    d.recip = m->d_recip_sched; d.recipm1 = m->d_recip_sched + T;
+    d.tw = timestep_weights;
+    d.diffusion_weight = diffusion_weight; d.projection_weight = projection_weight;
+    d.bd = (float)((double)B * (double)plan.D);
+    return d;
+}
+
+int launch_dynamics(const DynLaunch& l, const dad::DynamicsParams& d, hipStream_t st) {
+    const dim3 grid(l.gx, l.gy), block((unsigned)l.threads);
+    switch (l.kind) {
+        case DAD_DO_K_FWD_ROW:
+            if (l.rows_per_block == 1)
+                hipLaunchKernelGGL((dad::dynamics_violation_fwd_row_kernel<1, dad::PROJ_KP>), grid, block, l.lds_bytes, st, d);
+            else if (l.rows_per_block == 4)
+                hipLaunchKernelGGL((dad::dynamics_violation_fwd_row_kernel<4, dad::PROJ_KP>), grid, block, l.lds_bytes, st, d);
+            else return fail(DAD_E_STATE, "dynamics objective: %d trajectories per block planned", l.rows_per_block);
+            break;
+        case DAD_DO_K_FWD_GEMM: hipLaunchKernelGGL(dad::dynamics_violation_fwd_gemm_kernel, grid, block, l.lds_bytes, st, d); break;
+        case DAD_DO_K_FWD_PARTS: hipLaunchKernelGGL(dad::dynamics_parts_kernel, grid, block, 0, st, d); break;
+        case DAD_DO_K_BWD_ROW: hipLaunchKernelGGL(dad::dynamics_violation_bwd_row_kernel, grid, block, l.lds_bytes, st, d); break;
+        case DAD_DO_K_BWD_GEMM: hipLaunchKernelGGL(dad::dynamics_violation_bwd_gemm_kernel, grid, block, l.lds_bytes, st, d); break;
+        case DAD_DO_K_BWD_SCATTER: hipLaunchKernelGGL(dad::dynamics_scatter_dout_kernel, grid, block, 0, st, d); break;
+        default: return fail(DAD_E_STATE, "dynamics objective: launch kind %d", l.kind);
+    }
+    HIP_TRY(hipGetLastError());
+    return DAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dad_train_dynamics_objective_workspace_bytes(const dad_model* m, const dad_project_args* proj, int32_t form, int32_t batch,
+                                                 size_t* saved_bytes, size_t* scratch_bytes) {
+    if (!m || !proj) return fail(DAD_E_INVALID, "dynamics objective: null pointer");
+    DynamicsObjectivePlan plan;
+    const int rc = dynamics_objective_plan(*m, batch, proj->state_dim, proj->observation_dim, proj->action_dim, form, true, plan);
+    if (plan.launches.empty()) return rc;      // (the shape was refused; a batch the pass refuses still has a size)
+    if (saved_bytes) *saved_bytes = plan.saved_bytes;
+    if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+    return DAD_OK;
+}
+
+int dad_train_dynamics_objective_forward(dad_model* m, const float* x0, const int32_t* t_rows, const float* noise,
+                                         const float* weights, int32_t loss_type, const dad_project_args* proj, int32_t p_dim,
+                                         int32_t form, float diffusion_weight, float projection_weight,
+                                         const float* timestep_weights, float* parts, int32_t batch, void* saved,
+                                         size_t saved_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (!x0 || !t_rows || !noise || !parts || !saved) return fail(DAD_E_INVALID, "null pointer");
+    DynamicsObjectivePlan plan;
+    int rc = check_dynamics(m, batch, loss_type, proj, p_dim, form, false, plan);
+    if (rc != DAD_OK) return rc;
+    if (saved_bytes < plan.saved_bytes)
+        return fail(DAD_E_WORKSPACE, "saved buffer has %zu bytes, the dynamics objective at batch %d needs %zu", saved_bytes, batch,
+                    plan.saved_bytes);
+    if ((rc = configure_kernels()) != DAD_OK || (rc = ensure_recip_schedule(m)) != DAD_OK) return rc;
+    // the fused objective's own forward: parts[0] is its loss
+    if ((rc = objective_forward_run(m, plan.obj, x0, t_rows, noise, weights, loss_type, parts, batch, saved, stream)) != DAD_OK) return rc;
+    float* const sv = (float*)((char*)saved + plan.obj.o.saved_base);
+    dad::ObjectiveParams q = objective_params(m, plan.obj.o, sv, batch, loss_type, x0, noise, weights);
+    dad::DynamicsParams d = dynamics_params(m, plan, q, proj, diffusion_weight, projection_weight, timestep_weights, saved, nullptr);
+    d.parts = parts;
+    for (int i = 0; i < plan.fwd_launches; ++i)
+        if ((rc = launch_dynamics(plan.launches[(size_t)i], d, (hipStream_t)stream)) != DAD_OK) return rc;
+    return DAD_OK;
+}
+
+int dad_train_dynamics_objective_backward(dad_model* m, const float* x0, const float* noise, const float* weights, int32_t loss_type,
+                                          const dad_project_args* proj, int32_t p_dim, int32_t form, float diffusion_weight,
+                                          float projection_weight, const float* timestep_weights, const float* d_loss,
+                                          float* const* grad_tensors, int32_t n_grad_tensors, float* const* time_grad_tensors,
+                                          int32_t n_time_grad_tensors, int32_t batch, void* saved, size_t saved_bytes, void* scratch,
+                                          size_t scratch_bytes, dad_stream_t stream) {
+    if (!m) return fail(DAD_E_INVALID, "null model");
+    if (!x0 || !noise || !d_loss || !grad_tensors || !time_grad_tensors || !saved || !scratch) return fail(DAD_E_INVALID, "null pointer");
+    DynamicsObjectivePlan plan;
+    int rc = check_dynamics(m, batch, loss_type, proj, p_dim, form, true, plan);
+    if (rc != DAD_OK) return rc;
+    if ((rc = configure_kernels()) != DAD_OK || (rc = ensure_recip_schedule(m)) != DAD_OK) return rc;
+    // d total / d out: the violation backward, whose scatter epilogue adds the diffusion term's gradient, in place of
+    // objective_dout_kernel
+    const std::function<int(const dad::ObjectiveParams&)> head = [&](const dad::ObjectiveParams& q) -> int {
+        const dad::DynamicsParams d = dynamics_params(m, plan, q, proj, diffusion_weight, projection_weight, timestep_weights, saved, scratch);
+        for (size_t i = (size_t)plan.fwd_launches; i < plan.launches.size(); ++i) {
+            const int lrc = launch_dynamics(plan.launches[i], d, (hipStream_t)stream);
+            if (lrc != DAD_OK) return lrc;
+        }
+        return DAD_OK;
+    };
+    return objective_backward_run(m, plan.obj, x0, noise, weights, loss_type, d_loss, grad_tensors, n_grad_tensors, time_grad_tensors,
+                                  n_time_grad_tensors, batch, saved, saved_bytes, plan.saved_bytes, scratch, scratch_bytes,
+                                  plan.scratch_bytes, stream, &head);
+}
+
 
 int dad_fill_normal(float* x, int32_t batch, int32_t row_elems, uint64_t seed, uint64_t row_offset,
                     uint64_t draw, dad_stream_t stream) {
@@ -2116,6 +2312,16 @@ int dad_debug_backward_steps(dad_model* m, int32_t batch, int32_t* out, int32_t 
 
 int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out) {
     return training_report(m, batch, objective_plan_report, out, capacity, needed_out);
+}
+
+int dad_debug_dynamics_objective_plan(dad_model* m, int32_t batch, int32_t state_dim, int32_t observation_dim, int32_t action_dim,
+                                      int32_t form, int32_t* out, int32_t capacity, int32_t* needed_out) {
+    if (!m || capacity < 0 || (capacity > 0 && !out)) return fail(DAD_E_INVALID, "bad argument");
+    if (!m->training) return fail(DAD_E_STATE, "dad_model_set_training(m, 1) has not been called");
+    if (m->bwd_rc != DAD_OK) return fail(m->bwd_rc, "%s", m->bwd_err.c_str());
+    std::vector<int32_t> r;
+    const int rc = dynamics_objective_plan_report(*m, batch, state_dim, observation_dim, action_dim, form, r);
+    return rc != DAD_OK ? rc : copy_report(r, out, capacity, needed_out);
 }
 
 int dad_debug_forward_plan(dad_model* m, int32_t batch, int32_t mode, int32_t* out, int32_t capacity, int32_t* needed_out) {

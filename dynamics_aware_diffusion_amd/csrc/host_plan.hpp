@@ -2023,6 +2023,72 @@ inline int objective_layout(const HostModel& m, int B, ObjectiveLayout& o) {
     return rc;
 }
 
+// ---- the dynamics-aware objective (dad_train_dynamics_objective_forward / _backward): the fused objective above plus
+// the violation of the predicted plan x0_hat, sharing t, the noise, x_t and `out`
+// What it keeps beyond the fused objective's regions: offsets in floats from the start of its own part of `saved` /
+// `scratch`, which begins at the next multiple of 256 bytes behind the objective's; regions start at multiples of 64
+// floats.  One launch of its own kernels (csrc/train_objective.hpp) per DynLaunch, forward ones first.
+struct DynLaunch { int kind; unsigned gx, gy; int threads; size_t lds_bytes; int rows_per_block; };
+struct DynamicsObjectivePlan {
+    ObjectivePlan obj;
+    ViolationGradPlan vg;        // the form and the grids: plan_violation_grad's, for x0_hat's shape
+    int D = 0, horizon = 0;      // (H + 1) n + H m for the trajectories' real horizon H
+    // saved: the residual r (B, D) | gemm form: sums of r^2 per (trajectory, column block) | row form: violation (B)
+    long r = 0, part = 0, violation = 0, saved_floats = 0;
+    long g = 0, scratch_floats = 0;      // scratch: gemm form: g (B, D)
+    size_t saved_base = 0, scratch_base = 0;      // bytes of the fused objective's parts (rounded up to 256)
+    size_t saved_bytes = 0, scratch_bytes = 0;    // totals: what dad_train_dynamics_objective_workspace_bytes reports
+    int fwd_launches = 0;
+    std::vector<DynLaunch> launches;
+};
+// `form`: -1 planned, 0 row, 1 gemm (as dad_projection_violation_fwd).  The shape is checked first; a forced row form
+// beyond a CU's LDS is planned (vg.refused) and refused by the entry points, as the violation pair does.
+inline int dynamics_objective_plan(const HostModel& m, int B, int state_dim, int observation_dim, int action_dim, int form,
+                                   bool backward, DynamicsObjectivePlan& p) {
+    p = DynamicsObjectivePlan();
+    if (B <= 0) return fail(DAD_E_INVALID, "dynamics objective: batch must be positive (got %d)", B);
+    if (state_dim <= 0 || action_dim <= 0 || state_dim > observation_dim)
+        return fail(DAD_E_INVALID, "dynamics objective: state_dim=%d must lie in 1 .. observation_dim=%d, action_dim=%d be positive",
+                    state_dim, observation_dim, action_dim);
+    if (observation_dim + action_dim != m.cfg.transition_dim)
+        return fail(DAD_E_INVALID, "dynamics objective: observation_dim=%d + action_dim=%d is not the model's transition_dim=%d",
+                    observation_dim, action_dim, m.cfg.transition_dim);
+    if (form < -1 || form > 1) return fail(DAD_E_INVALID, "dynamics objective: form=%d is none of -1 (planned), 0 (row), 1 (gemm)", form);
+    const int H = traj_horizon(m), td = m.cfg.transition_dim;
+    const long D = (long)(H + 1) * state_dim + (long)H * action_dim;
+    if (D > INT32_MAX / 64) return fail(DAD_E_INVALID, "projection dimension D=%ld too large", D);
+    p.D = (int)D; p.horizon = H;
+    const int rc = objective_plan(m, B, backward, p.obj);
+    p.vg = plan_violation_grad(p.D, B, (long)H * td, form);
+    auto al = [](long v) { return (v + 63) / 64 * 64; };
+    long at = 0;
+    auto take = [&](long floats) { const long q = at; at += al(floats); return q; };
+    const bool gemm = p.vg.form == DAD_VG_GEMM;
+    p.r = take((long)B * D);
+    if (gemm) p.part = take((long)B * p.vg.col_blocks); else p.violation = take(B);
+    p.saved_floats = at;
+    at = 0;
+    if (gemm) p.g = take((long)B * D);
+    p.scratch_floats = at;
+    p.saved_base = (p.obj.o.saved_bytes + 255) / 256 * 256;
+    p.scratch_base = (p.obj.o.scratch_bytes + 255) / 256 * 256;
+    p.saved_bytes = p.saved_base + (size_t)p.saved_floats * sizeof(float);
+    p.scratch_bytes = p.scratch_base + (size_t)p.scratch_floats * sizeof(float);
+    const ViolationGradPass &f = p.vg.fwd, &b = p.vg.bwd;
+    if (gemm) {
+        p.launches = {{DAD_DO_K_FWD_GEMM, f.gx, f.gy, dad::PG_THREADS, f.lds_bytes, 32},
+                      {DAD_DO_K_FWD_PARTS, 1, 1, 256, 0, 0},
+                      {DAD_DO_K_BWD_GEMM, b.gx, b.gy, dad::PG_THREADS, b.lds_bytes, 32},
+                      {DAD_DO_K_BWD_SCATTER, b.tail_gx, 1, dad::VG_TAIL_THREADS, 0, 0}};
+    } else {
+        p.launches = {{DAD_DO_K_FWD_ROW, f.gx, f.gy, 64 * dad::PROJ_KP, f.lds_bytes, f.rows_per_block},
+                      {DAD_DO_K_FWD_PARTS, 1, 1, 256, 0, 0},
+                      {DAD_DO_K_BWD_ROW, b.gx, b.gy, 64 * dad::VG_ROW_WAVES, b.lds_bytes, 1}};
+    }
+    p.fwd_launches = 2;
+    return rc;
+}
+
 // What a BK_GN step hands gn_mish_bwd_kernel / gn_mish_bwd_wave_kernel besides its pointers: read from the forward conv
 // the step belongs to.  dad_unet_backward fills GnBwdParams from it, backward_steps_encode writes it down.
 struct GnBwdShape { int C, L, cpg, lreal, cpg_real; bool dtemb; };

@@ -28,6 +28,7 @@ constexpr const char* kReportLayouts[][kMaxReportSections] = {
     {S(DAD_KL_HEADER), S(DAD_FAMILIES)},
     {S(DAD_VG_INTS), S(DAD_VG_FORMS)},
     {S(DAD_GD_INTS), S(DAD_GD_ACTS), S(DAD_GD_REFUSALS)},
+    {S(DAD_DO_HEADER), S(DAD_DO_REC_INTS), S(DAD_DO_KINDS)},
 };
 #undef K
 #undef S
@@ -180,6 +181,33 @@ inline int objective_plan_report(const HostModel& m, int B, std::vector<int32_t>
         rec[DAD_OP_REC_GRID_X] = (int32_t)l.gx(); rec[DAD_OP_REC_GRID_Y] = (int32_t)l.gy(); rec[DAD_OP_REC_GRID_Z] = (int32_t)l.gz();
         rec[DAD_OP_REC_CHUNKS] = gemm ? (full + 31) / 32 : 0; rec[DAD_OP_REC_LAST_CHUNKS] = gemm ? (last + 31) / 32 : 0;
         rec[DAD_OP_REC_KTAIL] = gemm ? l.K % 32 : 0; rec[DAD_OP_REC_KSLICE] = l.kslice;
+    }
+    return rc;
+}
+
+// dad_debug_dynamics_objective_plan: what dad_train_dynamics_objective_forward / _backward lay out and launch beyond
+// the fused objective, read from the plan they replay (dynamics_objective_plan).
+inline int dynamics_objective_plan_report(const HostModel& m, int B, int state_dim, int observation_dim, int action_dim, int form,
+                                          std::vector<int32_t>& r) {
+    DynamicsObjectivePlan p;
+    const int rc = dynamics_objective_plan(m, B, state_dim, observation_dim, action_dim, form, true, p);
+    if (p.launches.empty()) return rc;             // (the shape itself was refused: nothing was planned)
+    const auto i32 = [](size_t v) { return (int32_t)std::min<size_t>(v, INT32_MAX); };
+    r.assign(DAD_DO_HEADER, 0);
+    r[DAD_DO_FORM] = p.vg.form; r[DAD_DO_D] = p.D; r[DAD_DO_HORIZON] = p.horizon; r[DAD_DO_COL_BLOCKS] = p.vg.col_blocks;
+    r[DAD_DO_REFUSED] = p.vg.refused;
+    r[DAD_DO_SAVED_BASE] = i32(p.saved_base); r[DAD_DO_SAVED_BYTES] = i32(p.saved_bytes);
+    r[DAD_DO_SCRATCH_BASE] = i32(p.scratch_base); r[DAD_DO_SCRATCH_BYTES] = i32(p.scratch_bytes);
+    r[DAD_DO_R_OFFSET] = i32((size_t)p.r); r[DAD_DO_PART_OFFSET] = i32((size_t)p.part);
+    r[DAD_DO_VIOLATION_OFFSET] = i32((size_t)p.violation); r[DAD_DO_G_OFFSET] = i32((size_t)p.g);
+    r[DAD_DO_OBJECTIVE_LAUNCHES] = (int32_t)p.obj.time.size();
+    r[DAD_DO_FWD_LAUNCHES] = p.fwd_launches;
+    r[DAD_DO_RECORD_INTS] = DAD_DO_REC_INTS;
+    r[DAD_DO_LAUNCHES] = (int32_t)p.launches.size();
+    for (const DynLaunch& l : p.launches) {
+        int32_t* rec = new_record(r, DAD_DO_REC_INTS);
+        rec[DAD_DO_REC_KIND] = l.kind; rec[DAD_DO_REC_GRID_X] = (int32_t)l.gx; rec[DAD_DO_REC_GRID_Y] = (int32_t)l.gy;
+        rec[DAD_DO_REC_THREADS] = l.threads; rec[DAD_DO_REC_LDS_BYTES] = i32(l.lds_bytes); rec[DAD_DO_REC_ROWS_PER_BLOCK] = l.rows_per_block;
     }
     return rc;
 }

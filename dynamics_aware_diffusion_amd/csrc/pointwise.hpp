@@ -232,31 +232,17 @@ struct ProjParams {
 // every CU from L2, one dependent-free load per FMA), so the work is spread as wide as it goes:
 // lane dl of wave kp accumulates column d = 64 s + dl over the kp-th slice of k; the KP slices
 // meet in LDS and are added in fixed order.  (4 waves: 11.8 us per call at B=256, D=196.)
-template <int RB, int KP>
-__global__ __launch_bounds__(64 * KP) void project_kernel(const ProjParams p) {
-    extern __shared__ __attribute__((aligned(16))) float v[];    // [RB][D] rows, then [KP][RB][D] partials
-    const int D = p.D, H = p.H, n = p.n, m = p.m, td = p.od + p.m;
-    float* part = v + RB * D;
+// The kernel's first half, v = gather, then the KP partial products of v @ P in LDS (`part`), behind a barrier;
+// `gather(b, d, nstate, td)`: element d of trajectory b in physical units.
+template <int RB, int KP, class Gather>
+__device__ __forceinline__ void project_rows_matvec(const ProjParams& p, float* v, float* part, const Gather& gather) {
+    const int D = p.D, H = p.H, n = p.n, td = p.od + p.m;
     const int b0 = blockIdx.x * RB;
     const int nstate = (H + 1) * n;
-    // gather + de-normalise: [s_0..s_{H-1}, s_{H-1}, a_0..a_{H-1}]  (policies.py:434-448)
     for (int e = threadIdx.x; e < RB * D; e += blockDim.x) {
         const int r = e / D, d = e - r * D;
         const int b = b0 + r;
-        float val = 0.0f;
-        if (b < p.B) {
-            const float* xb = p.x + (long)b * H * td;
-            if (d < nstate) {
-                const int ts = d / n, k = d - ts * n;
-                const int tsrc = ts < H ? ts : H - 1;
-                val = xb[tsrc * td + k] * p.obs_std[k] + p.obs_mean[k];
-            } else {
-                const int dd = d - nstate;
-                const int ts = dd / m, k = dd - ts * m;
-                val = xb[ts * td + p.od + k] * p.act_std[k] + p.act_mean[k];
-            }
-        }
-        v[e] = val;
+        v[e] = b < p.B ? gather(b, d, nstate, td) : 0.0f;
     }
     __syncthreads();
     const int dl = threadIdx.x & 63, kp = threadIdx.x >> 6;
@@ -277,24 +263,54 @@ __global__ __launch_bounds__(64 * KP) void project_kernel(const ProjParams p) {
         for (int r = 0; r < RB; ++r) part[(kp * RB + r) * D + d] = acc[r];
     }
     __syncthreads();
-    if (p.violation != nullptr) {
-        // ProjectionLoss: squared distance from the dynamics-consistent subspace, summed per row in a
-        // fixed order (wave 0, strided partials then a shuffle tree): deterministic
-        if (threadIdx.x < 64) {
-            for (int r = 0; r < RB; ++r) {
-                float acc = 0.0f;
-                for (int d = threadIdx.x; d < D; d += 64) {
-                    float proj = 0.0f;
+}
+// ProjectionLoss: squared distance from the dynamics-consistent subspace, summed per row in a
+// fixed order (wave 0, strided partials then a shuffle tree): deterministic
+template <int RB, int KP>
+__device__ __forceinline__ void project_rows_violation(const ProjParams& p, const float* v, const float* part) {
+    const int D = p.D;
+    const int b0 = blockIdx.x * RB;
+    if (threadIdx.x < 64) {
+        for (int r = 0; r < RB; ++r) {
+            float acc = 0.0f;
+            for (int d = threadIdx.x; d < D; d += 64) {
+                float proj = 0.0f;
 #pragma unroll
-                    for (int q = 0; q < KP; ++q) proj += part[(q * RB + r) * D + d];
-                    const float diff = v[r * D + d] - proj;
-                    if (p.resid != nullptr && b0 + r < p.B) p.resid[(long)(b0 + r) * D + d] = diff;
-                    acc = fmaf(diff, diff, acc);
-                }
-                for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-                if (threadIdx.x == 0 && b0 + r < p.B) p.violation[b0 + r] = acc;
+                for (int q = 0; q < KP; ++q) proj += part[(q * RB + r) * D + d];
+                const float diff = v[r * D + d] - proj;
+                if (p.resid != nullptr && b0 + r < p.B) p.resid[(long)(b0 + r) * D + d] = diff;
+                acc = fmaf(diff, diff, acc);
             }
+            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+            if (threadIdx.x == 0 && b0 + r < p.B) p.violation[b0 + r] = acc;
         }
+    }
+}
+
+// element d of trajectory row `xb` in physical units: [s_0..s_{H-1}, s_{H-1}, a_0..a_{H-1}]  (policies.py:434-448)
+__device__ __forceinline__ float proj_gather(const ProjParams& p, const float* xb, int d, int nstate, int td) {
+    if (d < nstate) {
+        const int ts = d / p.n, k = d - ts * p.n;
+        const int tsrc = ts < p.H ? ts : p.H - 1;
+        return xb[tsrc * td + k] * p.obs_std[k] + p.obs_mean[k];
+    }
+    const int dd = d - nstate;
+    const int ts = dd / p.m, k = dd - ts * p.m;
+    return xb[ts * td + p.od + k] * p.act_std[k] + p.act_mean[k];
+}
+
+template <int RB, int KP>
+__global__ __launch_bounds__(64 * KP) void project_kernel(const ProjParams p) {
+    extern __shared__ __attribute__((aligned(16))) float v[];    // [RB][D] rows, then [KP][RB][D] partials
+    const int D = p.D, H = p.H, n = p.n, m = p.m, td = p.od + p.m;
+    float* part = v + RB * D;
+    const int b0 = blockIdx.x * RB;
+    const int nstate = (H + 1) * n;
+    project_rows_matvec<RB, KP>(p, v, part, [&](int b, int d, int ns, int tdd) {
+        return proj_gather(p, p.x + (long)b * H * tdd, d, ns, tdd);
+    });
+    if (p.violation != nullptr) {
+        project_rows_violation<RB, KP>(p, v, part);
         return;
     }
     for (int e = threadIdx.x; e < RB * D; e += blockDim.x) {
@@ -338,18 +354,7 @@ __global__ __launch_bounds__(64 * KP) void project_kernel(const ProjParams p) {
 // x); the host copies it back.  No atomics: bit-reproducible.
 // (PG_THREADS, PG_KC, PG_AS, project_gemm_lds_floats: conv_shapes.hpp)
 
-// element d of trajectory row `xb` in physical units (policies.py:434-448)
-__device__ __forceinline__ float proj_gather(const ProjParams& p, const float* xb, int d, int nstate, int td) {
-    if (d < nstate) {
-        const int ts = d / p.n, k = d - ts * p.n;
-        const int tsrc = ts < p.H ? ts : p.H - 1;
-        return xb[tsrc * td + k] * p.obs_std[k] + p.obs_mean[k];
-    }
-    const int dd = d - nstate;
-    const int ts = dd / p.m, k = dd - ts * p.m;
-    return xb[ts * td + p.od + k] * p.act_std[k] + p.act_mean[k];
-}
-
+// (proj_gather, above: element d of a trajectory in physical units)
 __global__ __launch_bounds__(PG_THREADS) void project_gemm_kernel(const ProjParams p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63;

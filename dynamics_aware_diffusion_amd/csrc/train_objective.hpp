@@ -14,6 +14,7 @@
 #include "../../include/dad.h"
 #include "conv_gemm.hpp"
 #include "train_bwd.hpp"
+#include "violation_grad.hpp"
 
 namespace dad {
 
@@ -93,15 +94,142 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_loss_final_kernel(const
 }
 
 // d loss / d out = g * sign(d) w / n (L1; sign(0) = 0 as torch defines it) or g * 2 d w / n (L2), g read on the device
-__global__ __launch_bounds__(OBJ_THREADS) void objective_dout_kernel(const ObjectiveParams p) {
-    const long i = (long)blockIdx.x * OBJ_THREADS + threadIdx.x;
-    if (i >= p.n) return;
-    const float g = *p.d_loss;
+__device__ __forceinline__ float objective_unit_grad(const ObjectiveParams& p, long i) {
     const float* target = p.predict_epsilon ? p.noise : p.x0;
     const float d = p.out[i] - target[i];
     float u = p.l1 ? (d > 0.0f ? 1.0f : d < 0.0f ? -1.0f : 0.0f) : 2.0f * d;
     if (p.weights != nullptr) u *= p.weights[i];
-    p.d_out[i] = g * (u / (float)p.n);
+    return u;
+}
+__global__ __launch_bounds__(OBJ_THREADS) void objective_dout_kernel(const ObjectiveParams p) {
+    const long i = (long)blockIdx.x * OBJ_THREADS + threadIdx.x;
+    if (i >= p.n) return;
+    const float g = *p.d_loss;
+    p.d_out[i] = g * (objective_unit_grad(p, i) / (float)p.n);
+}
+
+// ------------------------------------------------------------------------------ dynamics-aware objective
+// dad_train_dynamics_objective_forward / _backward: the violation |v - vP|^2 of the predicted plan x0_hat beside the
+// objective above, from the same x_t and `out`.  x0_hat is never written: the violation kernels' gather forms
+//   v = std * x0_hat + mean,  x0_hat = a_b x_t - c_b out  (a_b = sqrt_recip_ac[t_b], c_b = sqrt_recipm1_ac[t_b]; two
+//   products and one difference, each rounded: torch's predict_start_from_noise bit for bit)  or  x0_hat = out,
+// t_b as objective_xt_kernel clamped it (ObjectiveParams.t_rows).  The forward kernels are project_kernel's gather,
+// mat-vec and violation branch (row form: the same device functions) and violation_fwd_gemm_kernel's body on that gather;
+// the backward kernels are the bodies of violation_grad.hpp with the per-trajectory factor
+// d_loss * projection_weight * tw[t_b] / (B D) formed on the device and an epilogue that writes d total / d out once:
+//   d_out = d_loss * diffusion_weight * u / n + s_b * d_x0hat,   s_b = -c_b, or 1 when the model predicts x_0.
+struct DynamicsParams {
+    ObjectiveParams obj;         // x_t, out, t_rows, d_loss, d_out, n and what the diffusion term's unit gradient reads
+    ViolationFwdParams fwd;      // P, the normaliser, the shape, r (resid), per-trajectory violation or column-block sums
+    ViolationBwdParams bwd;      // r, g
+    const float* recip;          // [T] sqrt_recip_alphas_cumprod
+    const float* recipm1;        // [T] sqrt_recipm1_alphas_cumprod
+    const float* tw;             // [T] timestep weights or nullptr (ones)
+    float* parts;                // device float[3]: Ld, projection_weight * Lp, total
+    float diffusion_weight, projection_weight;
+    float bd;                    // B * D
+};
+
+// element d of trajectory b of the predicted plan, in physical units (proj_gather on x0_hat)
+__device__ __forceinline__ float dynamics_gather(const DynamicsParams& q, int b, int d, int nstate, int td) {
+    const ProjParams& p = q.fwd.proj;
+    int ts, c;
+    float sd, mn;
+    if (d < nstate) {
+        ts = d / p.n;
+        c = d - ts * p.n;
+        if (ts >= p.H) ts = p.H - 1;
+        sd = p.obs_std[c]; mn = p.obs_mean[c];
+    } else {
+        const int dd = d - nstate;
+        ts = dd / p.m;
+        const int k = dd - ts * p.m;
+        c = p.od + k;
+        sd = p.act_std[k]; mn = p.act_mean[k];
+    }
+    const long i = ((long)b * p.H + ts) * td + c;
+    float x0h = q.obj.out[i];
+    if (q.obj.predict_epsilon) {
+        const int t = q.obj.t_rows[b];
+        x0h = __fsub_rn(__fmul_rn(q.recip[t], q.obj.xt[i]), __fmul_rn(q.recipm1[t], x0h));
+    }
+    return x0h * sd + mn;
+}
+// d L / d violation of trajectory b
+__device__ __forceinline__ float dynamics_row_weight(const DynamicsParams& q, int b) {
+    const float tw = q.tw != nullptr ? q.tw[q.obj.t_rows[b]] : 1.0f;
+    return *q.obj.d_loss * (q.projection_weight * tw / q.bd);
+}
+// d total / d out of element e of trajectory b, `dx`: the projection term's gradient with respect to x0_hat there
+__device__ __forceinline__ void dynamics_store_dout(const DynamicsParams& q, int b, int e, float dx) {
+    const ObjectiveParams& p = q.obj;
+    const long i = (long)b * p.row_elems + e;
+    const float s = p.predict_epsilon ? -q.recipm1[p.t_rows[b]] : 1.0f;
+    p.d_out[i] = (*p.d_loss * q.diffusion_weight) * (objective_unit_grad(p, i) / (float)p.n) + s * dx;
+}
+
+// Row form, forward: project_kernel's two halves (pointwise.hpp: the gather and mat-vec, then the violation branch, r
+// kept) on the predicted plan.  One block = RB trajectories.
+template <int RB, int KP>
+__global__ __launch_bounds__(64 * KP) void dynamics_violation_fwd_row_kernel(const DynamicsParams q) {
+    extern __shared__ __attribute__((aligned(16))) float v[];    // [RB][D] rows, then [KP][RB][D] partials
+    const ProjParams& p = q.fwd.proj;
+    float* part = v + RB * p.D;
+    project_rows_matvec<RB, KP>(p, v, part, [&](int b, int d, int nstate, int td) { return dynamics_gather(q, b, d, nstate, td); });
+    project_rows_violation<RB, KP>(p, v, part);
+}
+
+__global__ __launch_bounds__(PG_THREADS) void dynamics_violation_fwd_gemm_kernel(const DynamicsParams q) {
+    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+    violation_fwd_gemm_body(q.fwd, vg_sm, [&](int b, int d, int nstate, int td) { return dynamics_gather(q, b, d, nstate, td); });
+}
+
+// parts[1] = projection_weight * sum_b tw[t_b] violation_b / (B D), parts[2] = diffusion_weight * parts[0] + parts[1]
+// (parts[0]: objective_loss_final_kernel's, earlier on the stream).  One block; thread i adds trajectories i, i + 256, ...
+// in order (gemm form: each one's column-block sums first, in column-block order), then the block's fixed tree.
+__global__ __launch_bounds__(OBJ_THREADS) void dynamics_parts_kernel(const DynamicsParams q) {
+    __shared__ float red[OBJ_THREADS];
+    const int B = q.obj.B, cb = q.fwd.col_blocks;
+    float acc = 0.0f;
+    for (int b = threadIdx.x; b < B; b += OBJ_THREADS) {
+        float viol;
+        if (cb > 0) {
+            viol = 0.0f;
+            for (int c = 0; c < cb; ++c) viol += q.fwd.part[(long)b * cb + c];
+        } else {
+            viol = q.fwd.proj.violation[b];
+        }
+        acc += (q.tw != nullptr ? q.tw[q.obj.t_rows[b]] : 1.0f) * viol;
+    }
+    const float s = objective_block_sum(acc, red);
+    if (threadIdx.x == 0) {
+        const float lp = q.projection_weight * (s / q.bd);
+        q.parts[1] = lp;
+        q.parts[2] = q.diffusion_weight * q.parts[0] + lp;
+    }
+}
+
+__global__ __launch_bounds__(64 * VG_ROW_WAVES) void dynamics_violation_bwd_row_kernel(const DynamicsParams q) {
+    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+    violation_bwd_row_body(q.bwd, vg_sm, [&](int b) { return dynamics_row_weight(q, b); },
+                           [&](int b, int e, float v) { dynamics_store_dout(q, b, e, v); });
+}
+
+__global__ __launch_bounds__(PG_THREADS) void dynamics_violation_bwd_gemm_kernel(const DynamicsParams q) {
+    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+    violation_bwd_gemm_body(q.bwd, vg_sm, [&](int b) { return dynamics_row_weight(q, b); });
+}
+
+// d total / d out from g: one thread per element (violation_scatter_kernel's indexing)
+__global__ __launch_bounds__(VG_TAIL_THREADS) void dynamics_scatter_dout_kernel(const DynamicsParams q) {
+    const ViolationBwdParams& p = q.bwd;
+    const long i = (long)blockIdx.x * VG_TAIL_THREADS + threadIdx.x;
+    if (i >= (long)p.B * p.row_elems) return;
+    const int b = (int)(i / p.row_elems);
+    const int e = (int)(i - (long)b * p.row_elems);
+    const int td = p.od + p.m;
+    const int ts = e / td, c = e - ts * td;
+    dynamics_store_dout(q, b, e, vg_dx_elem(p, p.g + (long)b * p.D, ts, c));
 }
 
 // ------------------------------------------------------------------------------ time chain

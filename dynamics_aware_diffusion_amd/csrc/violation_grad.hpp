@@ -20,6 +20,10 @@
 //         transposed.  g goes to the workspace; violation_scatter_kernel writes d_x from it (the two entries of
 //         the last state lie in different column blocks).
 // No atomics anywhere: every sum has one order, the same inputs give the same bits.
+//
+// The three kernels written here are thin __global__ wrappers over *_body templates, which state the arithmetic once:
+// the dynamics-aware objective (train_objective.hpp) instantiates the same bodies with another gather (x0_hat formed
+// from x_t and the denoiser's output), another per-trajectory weight and another store (d total / d out).
 #pragma once
 #include "pointwise.hpp"
 
@@ -57,15 +61,16 @@ __device__ __forceinline__ float vg_dx_elem(const ViolationBwdParams& p, const f
 // ------------------------------------------------------------------------------------------ row form, backward
 // One block = one trajectory, VG_ROW_WAVES waves.  Wave q owns rows d = q, q + 16, ... of P, four at a time (four
 // independent streams of loads in flight); LDS: r_b [D], g_b [D].
-__global__ __launch_bounds__(64 * VG_ROW_WAVES) void violation_bwd_row_kernel(const ViolationBwdParams p) {
-    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+// `weight(b)`: d L / d violation of trajectory b; `store(b, e, v)`: what becomes of element e of its d_x.
+template <class Weight, class Store>
+__device__ __forceinline__ void violation_bwd_row_body(const ViolationBwdParams& p, float* vg_sm, const Weight& weight, const Store& store) {
     const int D = p.D, b = blockIdx.x;
     float* const rs = vg_sm;
     float* const gs = vg_sm + D;
     const float* rb = p.r + (long)b * D;
     for (int k = threadIdx.x; k < D; k += blockDim.x) rs[k] = rb[k];
     __syncthreads();
-    const float w2 = 2.0f * p.w[b];
+    const float w2 = 2.0f * weight(b);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int d = wave; d < D; d += 4 * VG_ROW_WAVES) {
@@ -90,18 +95,23 @@ __global__ __launch_bounds__(64 * VG_ROW_WAVES) void violation_bwd_row_kernel(co
     }
     __syncthreads();
     const int td = p.od + p.m;
-    float* dxb = p.dx + (long)b * p.row_elems;
     for (int e = threadIdx.x; e < p.row_elems; e += blockDim.x) {
         const int ts = e / td, c = e - ts * td;
-        dxb[e] = vg_dx_elem(p, gs, ts, c);
+        store(b, e, vg_dx_elem(p, gs, ts, c));
     }
+}
+__global__ __launch_bounds__(64 * VG_ROW_WAVES) void violation_bwd_row_kernel(const ViolationBwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+    violation_bwd_row_body(p, vg_sm, [&](int b) { return p.w[b]; },
+                           [&](int b, int e, float v) { p.dx[(long)b * p.row_elems + e] = v; });
 }
 
 // ------------------------------------------------------------------------------------------ gemm form, forward
 // project_gemm_kernel's K loop; the epilogue keeps r = v - vP and the sum of r^2 over this block's 32 columns, per
 // trajectory (a row of the tile is 32 consecutive lanes: a shuffle tree inside the half wave).
-__global__ __launch_bounds__(PG_THREADS) void violation_fwd_gemm_kernel(const ViolationFwdParams q) {
-    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+// `gather(b, d, nstate, td)`: element d of trajectory b in physical units.
+template <class Gather>
+__device__ __forceinline__ void violation_fwd_gemm_body(const ViolationFwdParams& q, float* vg_sm, const Gather& gather) {
     const ProjParams& p = q.proj;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -128,7 +138,7 @@ __global__ __launch_bounds__(PG_THREADS) void violation_fwd_gemm_kernel(const Vi
             for (int r = 0; r < 32; ++r) {
                 const int b = b0 + r;
                 float v = 0.0f;
-                if (k < D && b < p.B) v = proj_gather(p, p.x + (long)b * H * td, k, nstate, td);
+                if (k < D && b < p.B) v = gather(b, k, nstate, td);
                 As[lane * PG_AS + r] = v;
             }
         }
@@ -153,13 +163,20 @@ __global__ __launch_bounds__(PG_THREADS) void violation_fwd_gemm_kernel(const Vi
         if (b < p.B && d < D) {
             const float proj = ((E[r * PG_AS + cidx] + E[(32 + r) * PG_AS + cidx]) + E[(64 + r) * PG_AS + cidx]) +
                                E[(96 + r) * PG_AS + cidx];
-            diff = proj_gather(p, p.x + (long)b * H * td, d, nstate, td) - proj;
+            diff = gather(b, d, nstate, td) - proj;
             p.resid[(long)b * D + d] = diff;
         }
         float sq = diff * diff;
         for (int o = 16; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
         if (cidx == 0 && b < p.B) q.part[(long)b * q.col_blocks + blockIdx.y] = sq;
     }
+}
+__global__ __launch_bounds__(PG_THREADS) void violation_fwd_gemm_kernel(const ViolationFwdParams q) {
+    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+    const ProjParams& p = q.proj;
+    violation_fwd_gemm_body(q, vg_sm, [&](int b, int d, int nstate, int td) {
+        return proj_gather(p, p.x + (long)b * p.H * td, d, nstate, td);
+    });
 }
 
 // violation[b] = the column blocks' partial sums, added in column-block order
@@ -175,8 +192,8 @@ __global__ __launch_bounds__(VG_TAIL_THREADS) void violation_sum_kernel(const fl
 
 // ------------------------------------------------------------------------------------------ gemm form, backward
 // C[b][d] = sum_k r[b][k] P[d][k] for 32 trajectories x 32 rows d of P; g[b][d] = 2 w_b (r[b][d] - C[b][d]).
-__global__ __launch_bounds__(PG_THREADS) void violation_bwd_gemm_kernel(const ViolationBwdParams p) {
-    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+template <class Weight>
+__device__ __forceinline__ void violation_bwd_gemm_body(const ViolationBwdParams& p, float* vg_sm, const Weight& weight) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l32 = lane & 31, h = lane >> 5;
@@ -222,8 +239,12 @@ __global__ __launch_bounds__(PG_THREADS) void violation_bwd_gemm_kernel(const Vi
         if (b >= p.B || d >= D) continue;
         const float c = ((E[r * PG_AS + cidx] + E[(32 + r) * PG_AS + cidx]) + E[(64 + r) * PG_AS + cidx]) +
                         E[(96 + r) * PG_AS + cidx];
-        p.g[(long)b * D + d] = (2.0f * p.w[b]) * (p.r[(long)b * D + d] - c);
+        p.g[(long)b * D + d] = (2.0f * weight(b)) * (p.r[(long)b * D + d] - c);
     }
+}
+__global__ __launch_bounds__(PG_THREADS) void violation_bwd_gemm_kernel(const ViolationBwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) float vg_sm[];
+    violation_bwd_gemm_body(p, vg_sm, [&](int b) { return p.w[b]; });
 }
 
 // d_x from g: one thread per element of d_x

@@ -262,6 +262,30 @@ class TemporalUnet(nn.Module):
         t32 = t.reshape(-1).to(device=x0.device, dtype=torch.int32).contiguous()
         return _ObjectiveFunction.apply(eng, LOSS_TYPES[loss_type], x0, t32, noise.contiguous().float(), weights, *tensors)
 
+    def dynamics_objective(self, x_start: torch.Tensor, t: torch.Tensor, noise: torch.Tensor, weights, loss_type: str,
+                           sqrt_ac: torch.Tensor, sqrt_1m_ac: torch.Tensor, projection, form, diffusion_weight: float,
+                           projection_weight: float, timestep_weights) -> torch.Tensor:
+        """:meth:`objective` and the dynamics violation of the predicted plan as ONE autograd node
+        (dad_train_dynamics_objective_forward / _backward; ``losses.DynamicsAwareLoss`` on the library route).  Returns
+        the device float[3] (diffusion, projection_weight * projection, total); only entry 2, the total, carries the
+        graph to the parameters.  ``projection``: a ``ProjectionState``; ``form``: None (planned), "row" or "gemm"."""
+        from .._engine import LOSS_TYPES, _violation_form
+        x0 = x_start.contiguous().float()
+        eng = self.engine(int(x0.shape[1]), x0.device, training=True)
+        eng.bind_train_schedule(sqrt_ac, sqrt_1m_ac)
+        layout, _ = eng.grad_layout()
+        tlayout, _ = eng.time_grad_layout()
+        params = self._params()
+        tensors = [params[k] for k, _, _ in layout] + [params[k] for k, _, _ in tlayout]
+        if weights is not None:
+            weights = torch.as_tensor(weights, dtype=torch.float32, device=x0.device).expand(x0.shape).contiguous()
+        if timestep_weights is not None:
+            timestep_weights = timestep_weights.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        t32 = t.reshape(-1).to(device=x0.device, dtype=torch.int32).contiguous()
+        return _DynamicsObjectiveFunction.apply(eng, LOSS_TYPES[loss_type], projection, _violation_form(form),
+                                                float(diffusion_weight), float(projection_weight), timestep_weights, x0, t32,
+                                                noise.contiguous().float(), weights, *tensors)
+
     def forward(self, x: torch.Tensor, time: Union[int, torch.Tensor]) -> torch.Tensor:
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._params().values())):
             if isinstance(time, int):
@@ -329,3 +353,29 @@ class _ObjectiveFunction(torch.autograd.Function):
         grads = ctx.eng.objective_backward(x0, noise, weights, ctx.loss_type, d_loss.contiguous().float(), ctx.saved, ctx.shapes)
         ctx.saved = ctx.data = None
         return (None, None, None, None, None, None, *grads)
+
+
+class _DynamicsObjectiveFunction(torch.autograd.Function):
+    """``_ObjectiveFunction``'s sibling for the dynamics-aware objective: diffusion term and the violation of the
+    predicted plan from one evaluation of the denoiser.  The output is the device float[3] (diffusion,
+    projection_weight * projection, total); the backward reads the gradient of entry 2, the total, on the device (the
+    other two are reports: gradients sent into them are not propagated).  Differentiable inputs as ``_ObjectiveFunction``."""
+
+    @staticmethod
+    def forward(ctx, eng, loss_type, projection, form, dw, pw, tw, x0, t32, noise, weights, *params):
+        parts, saved = eng.dynamics_objective_forward(x0, t32, noise, weights, loss_type, projection, form, dw, pw, tw)
+        ctx.eng, ctx.saved = eng, saved
+        ctx.args = (loss_type, projection, form, dw, pw, tw)
+        ctx.data = (x0, noise, weights)
+        ctx.shapes = [tuple(p.shape) for p in params]
+        return parts
+
+    @staticmethod
+    def backward(ctx, d_parts):
+        x0, noise, weights = ctx.data
+        loss_type, projection, form, dw, pw, tw = ctx.args
+        d_total = d_parts[2].contiguous().float()
+        grads = ctx.eng.dynamics_objective_backward(x0, noise, weights, loss_type, projection, form, dw, pw, tw, d_total,
+                                                    ctx.saved, ctx.shapes)
+        ctx.saved = ctx.data = None
+        return (None,) * 11 + tuple(grads)

@@ -241,6 +241,43 @@ int dad_train_objective_backward(dad_model* m, const float* x0, const float* noi
                                  float* const* time_grad_tensors, int32_t n_time_grad_tensors, int32_t batch, void* saved,
                                  size_t saved_bytes, void* scratch, size_t scratch_bytes, dad_stream_t stream);
 
+struct dad_project_args;
+/* The dynamics-aware objective: the objective above and the dynamics violation of the plan the model predicts, from ONE
+ * evaluation of the denoiser (they share t, the noise, x_t and `out`):
+ *   total = diffusion_weight * Ld + projection_weight * Lp
+ *   Ld    = the loss of dad_train_objective_forward (same launches, same bits)
+ *   Lp    = sum_b tw[t_b] * violation(x0_hat_b) / (B * D),   violation as dad_projection_violation_fwd (physical units)
+ *   x0_hat = sqrt_recip_ac[t_b] x_t - sqrt_recipm1_ac[t_b] out  (cfg.predict_epsilon; the two tables of
+ *            dad_model_load_schedule; two products and one difference, each rounded, as torch's expression), else `out`;
+ *            never clamped.  It is formed inside the violation kernels' gather: no x0_hat tensor is written.
+ * `proj`: P (D, D), D = (H + 1) n + H m for the trajectories' horizon H, and the normaliser; `p_dim`: the side of P as
+ * the caller holds it (checked against D); observation_dim + action_dim must be the model's transition_dim.  `form`:
+ * -1 / 0 / 1 as dad_projection_violation_fwd.  `timestep_weights`: tw, (n_timesteps) device fp32, or NULL for all ones.
+ * `parts`: device float[3] = (Ld, projection_weight * Lp, total), written by the forward.
+ * The backward pass runs the violation backward of the same form with the per-trajectory factor
+ * d_loss * projection_weight * tw[t_b] / (B D) and writes d total / d out ONCE, in its scatter epilogue:
+ *   d_out = d_loss * diffusion_weight * u / n  +  s_b * (the scattered, de-normalised projection gradient)
+ * (u: the unit gradient of the L1 / L2 term, weights included; s_b = -sqrt_recipm1_ac[t_b], or 1 when the model predicts
+ * x_0), then the denoiser's and the time chain's backward exactly as dad_train_objective_backward.  P and x_0 get no
+ * gradient.  No atomics; every sum has one order.  Refusals come before the first launch, with a message: those of the
+ * objective above, then DAD_E_INVALID for missing projection arguments, a shape that does not fit (p_dim != D, the
+ * widths), an unknown form, a forced row form whose row does not fit a CU's LDS; DAD_E_STATE without
+ * dad_model_load_schedule; DAD_E_WORKSPACE for buffers smaller than dad_train_dynamics_objective_workspace_bytes reports. */
+int dad_train_dynamics_objective_workspace_bytes(const dad_model* m, const struct dad_project_args* proj, int32_t form,
+                                                 int32_t batch, size_t* saved_bytes, size_t* scratch_bytes);
+int dad_train_dynamics_objective_forward(dad_model* m, const float* x0, const int32_t* t_rows, const float* noise,
+                                         const float* weights, int32_t loss_type, const struct dad_project_args* proj,
+                                         int32_t p_dim, int32_t form, float diffusion_weight, float projection_weight,
+                                         const float* timestep_weights, float* parts, int32_t batch, void* saved,
+                                         size_t saved_bytes, dad_stream_t stream);
+int dad_train_dynamics_objective_backward(dad_model* m, const float* x0, const float* noise, const float* weights,
+                                          int32_t loss_type, const struct dad_project_args* proj, int32_t p_dim, int32_t form,
+                                          float diffusion_weight, float projection_weight, const float* timestep_weights,
+                                          const float* d_loss, float* const* grad_tensors, int32_t n_grad_tensors,
+                                          float* const* time_grad_tensors, int32_t n_time_grad_tensors, int32_t batch,
+                                          void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                          dad_stream_t stream);
+
 /* Arguments of one reverse step beyond (x, t). All pointers may be NULL unless noted. */
 typedef struct dad_step_args {
     const float* noise;      /* (B,H,td) injected z; NULL => in-kernel Philox            */
@@ -661,6 +698,49 @@ DAD_LAYOUT(DAD_OP_REC_INTS, 0);
     F(DAD_OP_TG_DTEMB, DTEMB, 1, "time_dtemb_kernel: M x N elements, K = slabs added")
 DAD_LAYOUT(DAD_OP_TG_MODES, 0);
 int dad_debug_objective_plan(dad_model* m, int32_t batch, int32_t* out, int32_t capacity, int32_t* needed_out);
+
+/* What one dynamics-aware objective step (dad_train_dynamics_objective_forward + _backward) adds to the fused objective
+ * step of the report above, for a projector over (state_dim, observation_dim, action_dim) under `form`: the layout of
+ * its own parts of `saved` / `scratch` and one record per launch of its own kernels, the forward's first (host logic
+ * only; needs what dad_debug_objective_plan needs; a shape the entry points refuse is refused here too, a forced row
+ * form that does not fit is reported, DAD_DO_REFUSED).  Sizes are capped at INT32_MAX. */
+#define DAD_DO_HEADER_LIST(F) \
+    F(DAD_DO_FORM, form, 1, "DAD_VG_ROW / DAD_VG_GEMM: the form both passes take (plan_violation_grad's choice for x0_hat's shape)") \
+    F(DAD_DO_D, D, 1, "(H + 1) state_dim + H action_dim") \
+    F(DAD_DO_HORIZON, horizon, 1, "H: the trajectories' horizon (the real one of a zero-padded model)") \
+    F(DAD_DO_COL_BLOCKS, col_blocks, 1, "gemm: 32-column blocks of P = partial sums per trajectory; row: 0") \
+    F(DAD_DO_REFUSED, refused, 1, "1: the calls fail with DAD_E_INVALID (a forced row form beyond one CU's LDS)") \
+    F(DAD_DO_SAVED_BASE, saved_base, 1, "bytes of `saved` the fused objective holds (dad_train_objective_workspace_bytes, rounded up to 256)") \
+    F(DAD_DO_SAVED_BYTES, saved_bytes, 1, "dad_train_dynamics_objective_workspace_bytes: saved") \
+    F(DAD_DO_SCRATCH_BASE, scratch_base, 1, "bytes of `scratch` the fused objective holds") \
+    F(DAD_DO_SCRATCH_BYTES, scratch_bytes, 1, "dad_train_dynamics_objective_workspace_bytes: scratch") \
+    F(DAD_DO_R_OFFSET, r_offset, 1, "saved, floats behind saved_base: the residual r (B, D)") \
+    F(DAD_DO_PART_OFFSET, part_offset, 1, "... gemm: sums of r^2 per (trajectory, column block)") \
+    F(DAD_DO_VIOLATION_OFFSET, violation_offset, 1, "... row: the violation per trajectory (B)") \
+    F(DAD_DO_G_OFFSET, g_offset, 1, "scratch, floats behind scratch_base: gemm: g (B, D)") \
+    F(DAD_DO_OBJECTIVE_LAUNCHES, objective_launches, 1, "launches of the time chain the step shares with the fused objective (dad_debug_objective_plan): 9") \
+    F(DAD_DO_FWD_LAUNCHES, fwd_launches, 1, "records that belong to the forward: 2") \
+    F(DAD_DO_RECORD_INTS, record_ints, 1, "ints per record") \
+    F(DAD_DO_LAUNCHES, launches, 1, "records: 3 (row) or 4 (gemm)")
+DAD_LAYOUT(DAD_DO_HEADER, 0);
+#define DAD_DO_REC_INTS_LIST(F) \
+    F(DAD_DO_REC_KIND, kind, 1, "DAD_DO_K_*") \
+    F(DAD_DO_REC_GRID_X, gx, 1, "grid x") \
+    F(DAD_DO_REC_GRID_Y, gy, 1, "grid y") \
+    F(DAD_DO_REC_THREADS, threads, 1, "threads per block") \
+    F(DAD_DO_REC_LDS_BYTES, lds_bytes, 1, "dynamic LDS of one block") \
+    F(DAD_DO_REC_ROWS_PER_BLOCK, rows_per_block, 1, "trajectories per block (0: an elementwise launch)")
+DAD_LAYOUT(DAD_DO_REC_INTS, 0);
+#define DAD_DO_KINDS_LIST(F) \
+    F(DAD_DO_K_FWD_ROW, fwd_row, 1, "dynamics_violation_fwd_row_kernel: project_kernel's violation branch with x0_hat formed in the gather, r kept") \
+    F(DAD_DO_K_FWD_GEMM, fwd_gemm, 1, "dynamics_violation_fwd_gemm_kernel: violation_fwd_gemm_kernel's body on the same gather") \
+    F(DAD_DO_K_FWD_PARTS, fwd_parts, 1, "dynamics_parts_kernel: Lp = sum_b tw violation_b / (B D) in one fixed order, and the total") \
+    F(DAD_DO_K_BWD_ROW, bwd_row, 1, "dynamics_violation_bwd_row_kernel: violation_bwd_row_kernel's body; its epilogue writes d total / d out") \
+    F(DAD_DO_K_BWD_GEMM, bwd_gemm, 1, "dynamics_violation_bwd_gemm_kernel: violation_bwd_gemm_kernel's body with the per-trajectory factor formed on the device") \
+    F(DAD_DO_K_BWD_SCATTER, bwd_scatter, 1, "dynamics_scatter_dout_kernel: d total / d out from g and the diffusion term's unit gradient")
+DAD_LAYOUT(DAD_DO_KINDS, 0);
+int dad_debug_dynamics_objective_plan(dad_model* m, int32_t batch, int32_t state_dim, int32_t observation_dim,
+                                      int32_t action_dim, int32_t form, int32_t* out, int32_t capacity, int32_t* needed_out);
 
 /* What one forward evaluation launches at a batch under the current debug options: the description the entry point
  * itself replays (csrc/host_plan.hpp: FwdPlan of plan_forward; mode 3: TrainScratch of train_scratch), written down
